@@ -6,6 +6,14 @@ One "step" = one fused forward pass (one kernel launch) over a batch of 65,536 s
 each rank owns its own 65,536-trial shard: config E's static split, weak scaling, no collectives).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config b22|c64|d22|p64|g19|g38|p64l] [--batch B]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, settles and warms up, times the K steps and prints the line; nothing else.
+``--dump-outputs DIR`` also writes the logits the last timed step left, as float32 [B][N], to
+``DIR/logits.npy`` (``DIR/logits_rank<r>.npy`` per rank when N > 1).  The inputs are a function
+of the arguments alone (seeded), so two builds can be compared output for output.  ``--full``
+adds the legs described below that take runs of their own: the CPU baseline, the logit parity
+against the oracle and, with --pcie, the host-buffer path.
 
 For N > 1 launch under ``torch.distributed.run`` (one process per GPU); rank 0 prints ONE JSON
 line.  ``value`` = trials processed by all ranks / max-over-ranks wall time of the K timed steps.
@@ -14,12 +22,14 @@ reduction and the per-rank record.  The data path has no collective (SURVEY §8(
 group is ever created, and nothing collective runs inside the K timed steps: each rank times its
 own steps (host clock around them, HIP events on its launch stream), then the ranks reduce.
 ``roofline.achieved`` = algorithmic bytes per launch (input 22*1125 B + 4 B logits per trial) /
-average kernel duration from HIP events on the launch stream.  ``cpu_baseline`` times the C
-restatement of the reference forward (oracle/, kind "port") on the host cores (rank 0, N = 1),
-and its logits on that sample are compared with the timed batch's: ``parity`` = trials checked and
-mismatches; any mismatch makes the run exit non-zero (after printing the line).  Without a timed
-baseline (--no-cpu-baseline, or N > 1) the oracle still checks the whole batch (rank 0's shard),
-untimed, after the timed steps.
+average kernel duration from HIP events on the launch stream.
+
+With --full, ``cpu_baseline`` times the C restatement of the reference forward (oracle/, kind
+"port") on the host cores (rank 0, N = 1), and its logits on that sample are compared with the
+timed batch's: ``parity`` = trials checked and mismatches; any mismatch makes the run exit
+non-zero (after printing the line).  Without a timed baseline (--full --no-cpu-baseline, or
+--full with N > 1) the oracle still checks the whole batch (rank 0's shard), untimed, after the
+timed steps.  Without --full both fields are null.
 """
 import argparse
 import json
@@ -73,17 +83,28 @@ def parse():
                          "the envelope, which the loader folds (float kernels)")
     ap.add_argument("--force-general", action="store_true",
                     help="run the run-time-dimension kernels even on a compiled geometry (comparison)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the CPU "
+                         "baseline, the logit parity against the oracle and (with --pcie) the host-buffer path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits of the last timed step as float32 to DIR/logits.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: do not time the CPU baseline; the oracle still checks the whole batch")
     ap.add_argument("--settle", type=float, default=0.25,
                     help="seconds of untimed launches before the warmup steps (GPU clock ramp)")
     ap.add_argument("--per-launch-events", action="store_true",
                     help="bracket every launch with its own HIP events (diagnostic; adds idle gaps)")
     ap.add_argument("--cpu-seconds", type=float, default=25.0, help="target CPU-baseline wall time")
     ap.add_argument("--pcie", action="store_true",
-                    help="also time the host-buffer path (pinned H2D + forward + D2H); reported as "
+                    help="with --full: also time the host-buffer path (pinned H2D + forward + D2H); reported as "
                          "'pcie_inclusive', never as value")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.pcie and not a.full:
+        ap.error("--pcie is a leg of --full")
+    return a
 
 
 # MIB_BENCH_STUB=1 (CPU tests only, tests/test_bench_cpu.py): the multi-rank bookkeeping with a
@@ -353,6 +374,13 @@ def main():
         dist.all_gather_object(per_rank, mine)
         elapsed = elapsed_max
 
+    if a.dump_outputs:
+        # what a caller of the timed path receives: the logits the last timed step wrote (before
+        # any --full leg touches the buffers), int8 values stored as float32
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        name = "logits.npy" if world == 1 else f"logits_rank{rank}.npy"
+        np.save(os.path.join(a.dump_outputs, name), y.cpu().numpy().astype(np.float32))
+
     failed = None
     info = {"grid": 0, "threads": 0, "lds_bytes": 0} if STUB else lib.launch_info(B, local, channel_major=a.layout != "tc")
     if rank == 0:
@@ -421,17 +449,21 @@ def main():
                                     "wall time; coordination over gloo (host) only, no RCCL"}
         if STUB:
             out["stub"] = "MIB_BENCH_STUB: host stand-in step, bookkeeping test only, not a measurement"
+        if STUB and a.full:
             yh = y.numpy().copy()
             if os.environ.get("MIB_BENCH_STUB_CORRUPT") == "1":
                 yh[B // 2, 0] ^= 1  # the parity check's failure path (tests/test_bench_cpu.py)
             out["parity"] = logit_parity(yh, x[:, :N].numpy())
             out["parity"]["against"] = "stub stand-in"
-        if a.pcie and not STUB:
+        # the --full legs; a plain run stops at the headline figure
+        if a.pcie and a.full and not STUB:
             out["pcie_inclusive"] = pcie_inclusive(x, y, B, local, sp, stream)
-        if world == 1 and not a.no_cpu_baseline and not STUB:
+        if STUB or not a.full:
+            pass
+        elif world == 1 and not a.no_cpu_baseline:
             want, out["cpu_baseline"] = cpu_baseline(ps, x, a.cpu_seconds)
             out["parity"] = logit_parity(y[: want.shape[0]].cpu().numpy(), want)
-        elif not STUB:  # no timed baseline: the whole batch (rank 0's shard) is still checked
+        else:  # no timed baseline: the whole batch (rank 0's shard) is still checked
             want = oracle_logits(ps, x, B)
             out["parity"] = logit_parity(y.cpu().numpy(), want)
             if world > 1:

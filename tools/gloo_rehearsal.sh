@@ -10,7 +10,7 @@ N=${1:-2}
 TAG=${2:-r03}
 mkdir -p gpurun_out
 timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus "$N" --steps 20 --warmup 3 \
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus "$N" --steps 20 --warmup 3 --full \
   > "gpurun_out/gloo_${TAG}_n${N}.json" 2> "gpurun_out/gloo_${TAG}_n${N}.err"
 rc=$?
 cat "gpurun_out/gloo_${TAG}_n${N}.json"

@@ -9,7 +9,7 @@ ROOT=$(pwd)
 TAG=${1:-r03}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
-B="python3 $ROOT/bench.py"
+B="python3 $ROOT/bench.py --full"  # the bench lines keep their CPU baseline and parity legs
 timeout -k 10 300 $B --steps 50 --warmup 5 > "$OUT/bench_b22.json" 2> "$OUT/bench_b22.err" || exit $?
 cat "$OUT/bench_b22.json"
 for cfg in c64 d22; do
