@@ -208,6 +208,47 @@ int net_model_compute_batch_ct(const int8_t* x, int8_t* y, size_t B, int device,
  * null stream), no host sync. */
 int net_model_compute_batch_f32(const float* x, int8_t* y, size_t B, float scale, int device, void* stream);
 
+/* ---- continuous recordings: the logits of every sliding window ------------------------------
+ * Window w of a recording of L samples covers samples w*hop .. w*hop + T - 1 (T of the loaded
+ * network).  Layer 1 and the float input quantiser act on each sample alone, so they run once per
+ * sample of the recording into a workspace, and each window's layers 2-5 read its 16 rows of T
+ * bytes from there: no materialised [W][C][T] batch, no layer 1 per window (INTEGRATION.md,
+ * "Continuous recordings"). */
+
+/* Windows of the loaded network's T samples at hop `hop` in a recording of L samples:
+ * L < T ? 0 : (L - T) / hop + 1   (0 if no set is loaded or hop == 0). */
+size_t net_windows_count(size_t L, size_t hop);
+
+/* Workspace layout: the layer-1 output of the whole recording, [F1 = 16][row_stride] int8 (row f
+ * = filter f, byte t = sample t). */
+size_t net_windows_row_stride(size_t L);      /* >= L, a multiple of 16 */
+size_t net_windows_workspace(size_t L);       /* 16 * row_stride bytes */
+
+/* layout: 0 = time-major recording [L][C] int8, 1 = channel-major [C][L] int8 (DEVICE pointers,
+ * any byte alignment).  y: DEVICE [W][N] int8, 4-byte aligned, W = net_windows_count(L, hop); row
+ * w is byte-identical to what net_model_compute_batch_ct returns for the trial x[:, w*hop :
+ * w*hop + T].  ws: DEVICE, 16-byte aligned, ws_bytes >= net_windows_workspace(L); after the call
+ * ws[f][t], t < L, is the reference net_layer1 output of sample t (bytes L .. row_stride - 1 of a
+ * row are zero), and no window's result depends on a byte at t >= L.  Enqueued on
+ * `stream` (NULL = null stream), no host sync, no allocation: capturable into a HIP graph after
+ * one eager call has uploaded the parameters, like the batched entries.
+ * Checks, all before any device call: NET_ERR_NO_PARAMS first; then NET_ERR_INVALID for hop == 0,
+ * a layout other than 0 or 1, a null x, y or ws with W > 0, a misaligned y, a ws that is
+ * misaligned or too small (for any W), W > INT32_MAX - 65,535, and
+ * L * max(16, C * sizeof(element)) >= 2^31: the kernels address the recording and the workspace
+ * through one buffer descriptor each, with 32-bit offsets.  Feed a longer recording in chunks that
+ * overlap by T - hop samples (chunk k + 1 starts at the sample where chunk k's last window + hop
+ * starts); the chunks' logit rows then concatenate to the recording's.  W == 0 returns NET_OK and
+ * writes nothing. */
+int net_model_compute_windows(const int8_t* x, int layout, size_t L, size_t hop, int8_t* y, void* ws,
+                              size_t ws_bytes, int device, void* stream);
+
+/* The same for a float32 channel-major recording [C][L] (4-byte aligned), quantised per sample
+ * exactly as net_model_compute_batch_f32 / net_quantize_input_f32 do: scale in [2^-60, 2^60],
+ * NET_ERR_RANGE otherwise (NET_ERR_INVALID for a scale that is not positive and finite). */
+int net_model_compute_windows_f32(const float* x, size_t L, size_t hop, float scale, int8_t* y, void* ws,
+                                  size_t ws_bytes, int device, void* stream);
+
 /* Several devices from one host thread (static split, no collectives): shard i is
  * x[i] / y[i] / B[i] on devices[i] (DEVICE pointers of that device).  Every shard is enqueued
  * before any is waited for, so the devices run concurrently.  streams == NULL: each device's null

@@ -24,6 +24,7 @@
 #include "../../include/mibminet_testing.h"
 #include "forward_wg.hpp"
 #include "forward_gen.hpp"
+#include "forward_win.hpp"
 #include "quantize.hpp"
 #include "classify.hpp"
 
@@ -980,6 +981,8 @@ struct DeviceState {
   std::mutex mu;
   uint64_t gen = 0;             // params generation of `cur`
   void* cur = nullptr;          // device copy of that generation (DevParams or gen::GenParams)
+  uint64_t wgen = 0;            // the same for the window kernels' gen::GenParams (net_model_compute_windows):
+  void* wcur = nullptr;         // cur itself on the general path, a copy of its own for a compiled geometry
   std::vector<DevImage> images; // the copies uploaded to this device
   uint64_t tick = 0;
   int8_t* d_in = nullptr;       // single-trial scratch
@@ -994,6 +997,7 @@ struct DeviceState {
 std::mutex g_mu;
 std::shared_ptr<const HostParams> g_host;
 Image g_img;
+Image g_win;  // the gen::GenParams of the window kernels: g_img on the general path (empty: none could be built)
 uint64_t g_gen = 0;
 DeviceState g_devs[MAX_DEVICES];
 std::atomic<int> g_single_device{0};  // net_set_device (read by every single-trial call)
@@ -1031,11 +1035,12 @@ struct Snapshot {
   std::shared_ptr<const HostParams> host;
   Image img;
   uint64_t gen;
+  Image win;
 };
 
 Snapshot snapshot() {
   std::lock_guard<std::mutex> lk(g_mu);
-  return Snapshot{g_host, g_img, g_gen};
+  return Snapshot{g_host, g_img, g_gen, g_win};
 }
 
 void free_image(DevImage& im) {
@@ -1053,14 +1058,14 @@ bool image_idle(const DevImage& im) {
   return true;
 }
 
-// Frees least-recently-used idle copies (never ds.cur) until fewer than MAX_IMAGES remain or none
+// Frees least-recently-used idle copies (never ds.cur or ds.wcur) until fewer than MAX_IMAGES remain or none
 // is idle.  No device synchronisation.
 void evict_idle(DeviceState& ds) {
   while (ds.images.size() >= MAX_IMAGES) {
     int victim = -1;
     for (int i = 0; i < (int)ds.images.size(); i++) {
       const DevImage& im = ds.images[i];
-      if (im.dev == ds.cur || !image_idle(im)) continue;
+      if (im.dev == ds.cur || im.dev == ds.wcur || !image_idle(im)) continue;
       if (victim < 0 || im.used < ds.images[victim].used) victim = i;
     }
     if (victim < 0) return;
@@ -1069,11 +1074,12 @@ void evict_idle(DeviceState& ds) {
   }
 }
 
-// After a batched launch with ds.cur on `st` (ds.mu held, device current): remember it, so that
-// the copy is freed only once the launch has finished.  Under stream capture the copy is pinned.
-void note_launch(DeviceState& ds, hipStream_t st) {
+// After a batched launch that reads the device copy `dev` on `st` (ds.mu held, device current):
+// remember it, so that the copy is freed only once the launch has finished.  Under stream capture
+// the copy is pinned.
+void note_launch(DeviceState& ds, const void* dev, hipStream_t st) {
   for (DevImage& im : ds.images) {
-    if (im.dev != ds.cur) continue;
+    if (im.dev != dev) continue;
     if (im.pinned) return;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
@@ -1100,31 +1106,30 @@ void note_launch(DeviceState& ds, hipStream_t st) {
   }
 }
 
-// Ensure `dev` holds the parameters of snapshot s (ds.cur); called with ds.mu held and the device
-// current.
-int ensure_device(DeviceState& ds, int dev, const Snapshot& s) {
-  if (!s.host) return NET_ERR_NO_PARAMS;
+// Ensure `dev` holds image img of generation gen, *cur pointing to its copy (*cur_gen: the
+// generation *cur belongs to); called with ds.mu held and the device current.
+int ensure_image(DeviceState& ds, int dev, const Image& img, uint64_t gen, void** cur, uint64_t* cur_gen) {
   if (ds.cus == 0) {
     int cus = 0;
     hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (e != hipSuccess) return hip_err(e);
     ds.cus = cus;
   }
-  if (ds.gen != s.gen || !ds.cur) {
+  if (*cur_gen != gen || !*cur) {
     for (DevImage& im : ds.images)  // a set loaded before: its copy is still there, unchanged
-      if (im.host.same(s.img)) {
-        ds.cur = im.dev;
-        ds.gen = s.gen;
+      if (im.host.same(img)) {
+        *cur = im.dev;
+        *cur_gen = gen;
         im.used = ++ds.tick;
         return NET_OK;
       }
     evict_idle(ds);
     DevImage im;
-    im.host = s.img;
+    im.host = img;
     im.used = ++ds.tick;
-    hipError_t e = hipMalloc(&im.dev, s.img.bytes);
+    hipError_t e = hipMalloc(&im.dev, img.bytes);
     if (e != hipSuccess) return hip_err(e);
-    e = hipMemcpy(im.dev, s.img.data.get(), s.img.bytes, hipMemcpyHostToDevice);
+    e = hipMemcpy(im.dev, img.data.get(), img.bytes, hipMemcpyHostToDevice);
     g_uploads++;
     if (t_enqueueing) g_uploads_enqueue++;
     if (e != hipSuccess) {
@@ -1132,10 +1137,24 @@ int ensure_device(DeviceState& ds, int dev, const Snapshot& s) {
       return hip_err(e);
     }
     ds.images.push_back(std::move(im));
-    ds.cur = ds.images.back().dev;
-    ds.gen = s.gen;
+    *cur = ds.images.back().dev;
+    *cur_gen = gen;
   }
   return NET_OK;
+}
+
+// Ensure `dev` holds the parameters of snapshot s (ds.cur); called with ds.mu held and the device
+// current.
+int ensure_device(DeviceState& ds, int dev, const Snapshot& s) {
+  if (!s.host) return NET_ERR_NO_PARAMS;
+  return ensure_image(ds, dev, s.img, s.gen, &ds.cur, &ds.gen);
+}
+
+// The same for the window kernels' image (ds.wcur): on the general path the copy ds.cur names.
+int ensure_device_win(DeviceState& ds, int dev, const Snapshot& s) {
+  if (!s.host) return NET_ERR_NO_PARAMS;
+  if (!s.win.data) return NET_ERR_UNSUPPORTED;
+  return ensure_image(ds, dev, s.win, s.gen, &ds.wcur, &ds.wgen);
 }
 
 // Single-trial scratch: device buffers, pinned host staging (the copies run as DMA without the
@@ -1294,6 +1313,94 @@ int launch_layer(const Variant& v, const void* himg, const void* p, const int8_t
   });
 }
 
+// ---- sliding windows over a recording (forward_win.hpp) --------------------------------------
+size_t windows_row_stride(size_t L) { return L > SIZE_MAX - 15 ? 0 : (L + 15) / 16 * 16; }
+
+// Layer 1 over the recording (layout as gen::Layout) into ws, then the W windows' layers 2-5.
+// hg: the host copy of the gen::GenParams p points to.
+template <int L, bool RB, bool XR, bool CB>
+int launch_windows_q(DeviceState& ds, const gen::GenParams& hg, const void* p, const int8_t* x, size_t Lr, size_t hop,
+                     size_t W, int8_t* y, int8_t* ws, hipStream_t st, float qs) {
+  const int rs = (int)windows_row_stride(Lr);
+  const size_t nb = (Lr + 15) / 16, wgs = (nb + win::NW1 - 1) / win::NW1;
+  const size_t cap1 = (size_t)ds.cus * 8;  // 8 workgroups of 4 waves fill a CU
+  const float qy = qs > 0.0f ? 1.0f / qs : 0.0f;  // RN(1 / scale), as the batched float kernels
+  hipLaunchKernelGGL((win::k_layer1_rec<L, XR, CB>), dim3((unsigned)std::min(wgs, cap1)), dim3(win::NT1), 0, st,
+                     (const gen::GenParams*)p, x, ws, (int)Lr, rs, qs, qy);
+  if (const int rc = hip_err(hipGetLastError())) return rc;
+  const int lds = gen::carve_of(hg.C, hg.T, hg.N, hg.T8, hg.T64A, hg.NB1, hg.MT, hg.NTT, 3).bytes;
+  const void* kern = (const void*)win::k_forward_y1<RB, XR, CB>;
+  const size_t cap = (size_t)ds.cus * (size_t)gen_blocks_per_cu(kern, lds);
+  const int grid = (int)(W < cap ? W : cap);
+  // hop > INT32_MAX: a single window (hop <= L - T < 2^27 otherwise), which never multiplies it
+  hipLaunchKernelGGL((win::k_forward_y1<RB, XR, CB>), dim3(grid), dim3(gen::NT), (size_t)lds, st,
+                     (const gen::GenParams*)p, (const int8_t*)ws, y, (int)W, (int)std::min(hop, (size_t)INT32_MAX), rs);
+  const int rc = hip_err(hipGetLastError());
+  note_launch(ds, p, st);  // the layer-1 kernel reads the copy even if the second launch failed
+  return rc;
+}
+
+template <int L>
+int launch_windows_t(DeviceState& ds, const gen::GenParams& hg, const void* p, const int8_t* x, size_t Lr, size_t hop,
+                     size_t W, int8_t* y, int8_t* ws, hipStream_t st, float qs) {
+  const int sel = (hg.rb ? 4 : 0) | (hg.xr ? 2 : 0) | (hg.lo == -127 ? 1 : 0);
+  switch (sel) {
+    case 0: return launch_windows_q<L, false, false, false>(ds, hg, p, x, Lr, hop, W, y, ws, st, qs);
+    case 1: return launch_windows_q<L, false, false, true>(ds, hg, p, x, Lr, hop, W, y, ws, st, qs);
+    case 2: return launch_windows_q<L, false, true, false>(ds, hg, p, x, Lr, hop, W, y, ws, st, qs);
+    case 3: return launch_windows_q<L, false, true, true>(ds, hg, p, x, Lr, hop, W, y, ws, st, qs);
+    case 4: return launch_windows_q<L, true, false, false>(ds, hg, p, x, Lr, hop, W, y, ws, st, qs);
+    case 5: return launch_windows_q<L, true, false, true>(ds, hg, p, x, Lr, hop, W, y, ws, st, qs);
+    case 6: return launch_windows_q<L, true, true, false>(ds, hg, p, x, Lr, hop, W, y, ws, st, qs);
+    default: return launch_windows_q<L, true, true, true>(ds, hg, p, x, Lr, hop, W, y, ws, st, qs);
+  }
+}
+
+size_t windows_count(const Dims& d, size_t L, size_t hop) {
+  return hop == 0 || L < (size_t)d.T ? 0 : (L - (size_t)d.T) / hop + 1;
+}
+
+// arg_layout: the int8 entry's layout argument (0 time-major, 1 channel-major); f32: the float32
+// entry (channel-major, scale qs).  Every argument and parameter check comes before the first
+// device call.
+int windows_async(const void* x, int arg_layout, bool f32, size_t L, size_t hop, float qs, int8_t* y, void* ws,
+                  size_t ws_bytes, int device, void* stream) {
+  const Snapshot s = snapshot();
+  if (!s.host) return NET_ERR_NO_PARAMS;
+  const Dims& d = s.host->d;
+  if (hop == 0 || (!f32 && arg_layout != 0 && arg_layout != 1)) return NET_ERR_INVALID;
+  const int layout = f32 ? (int)gen::F32 : arg_layout;  // gen::Layout
+  const size_t W = windows_count(d, L, hop);
+  if (W && (!x || !y || !ws)) return NET_ERR_INVALID;
+  if (L > SIZE_MAX / 32) return NET_ERR_INVALID;  // (far past the offset limit below; 16 rs cannot wrap)
+  const size_t rs = windows_row_stride(L);
+  if (((uintptr_t)ws & 15) != 0 || ws_bytes < 16 * rs) return NET_ERR_INVALID;
+  if (((uintptr_t)y & 3) != 0 || (layout == 2 && ((uintptr_t)x & 3) != 0)) return NET_ERR_INVALID;
+  if (device < 0 || device >= MAX_DEVICES) return NET_ERR_INVALID;
+  // window indices are int in the kernel: w + gridDim.x (grid <= 2 per CU) must not wrap
+  if (W > (size_t)INT32_MAX - 65535) return NET_ERR_INVALID;
+  // the recording and the workspace are each one buffer view with 32-bit offsets
+  const size_t per = std::max((size_t)16, (size_t)d.C * (layout == 2 ? sizeof(float) : 1));
+  if (L > (((size_t)1 << 31) - 1) / per) return NET_ERR_INVALID;
+  if (layout == 2 && !(qs > 0.0f && qs <= 3.4e38f)) return NET_ERR_INVALID;
+  if (layout == 2 && !(qs >= 0x1p-60f && qs <= 0x1p60f)) return NET_ERR_RANGE;  // batch_async_s's domain
+  if (!s.win.data) return NET_ERR_UNSUPPORTED;
+  if (W == 0) return NET_OK;
+  if (const int rc = check_device(device)) return rc;
+  DeviceState& ds = g_devs[device];
+  std::lock_guard<std::mutex> lk(ds.mu);
+  DeviceGuard guard(device);
+  if (guard.err != hipSuccess) return hip_err(guard.err);
+  int rc = ensure_device_win(ds, device, s);
+  if (rc) return rc;
+  const gen::GenParams& hg = *(const gen::GenParams*)s.win.data.get();
+  const hipStream_t st = (hipStream_t)stream;
+  if (layout == 2) rc = launch_windows_t<gen::F32>(ds, hg, ds.wcur, (const int8_t*)x, L, hop, W, y, (int8_t*)ws, st, qs);
+  else if (layout == 1) rc = launch_windows_t<gen::CT>(ds, hg, ds.wcur, (const int8_t*)x, L, hop, W, y, (int8_t*)ws, st, qs);
+  else rc = launch_windows_t<gen::TM>(ds, hg, ds.wcur, (const int8_t*)x, L, hop, W, y, (int8_t*)ws, st, qs);
+  return rc;
+}
+
 // Runs one reference-layout single-trial stage on the single-trial device.
 // stage 0 = whole model (input [T][C_ALIGN]); 1..5 = net_layerN; 6 = flip.
 int run_single(int stage, const int8_t* in, int8_t* out) {
@@ -1436,20 +1543,28 @@ namespace {
 // geometry has them, the general kernels otherwise.
 int install(std::shared_ptr<HostParams> hp) {
   hp->general = g_force_general.load() != 0 || compiled_shape(hp->d) < 0;
-  auto build = [&](HostParams& h, Image* img) -> int {
+  // win: the gen::GenParams the window kernels read (forward_win.hpp): the image itself on the
+  // general path; for a compiled geometry one built from a copy of the same host set (its own
+  // float / exact choice travels in the image; h's, which net_params_info reports, is DevParams').
+  // A set no GenParams can be built for keeps its DevParams and has no window kernels.
+  auto build = [&](HostParams& h, Image* img, Image* win) -> int {
     if (h.general) {
       auto gp = std::make_shared<gen::GenParams>();
       if (const int rc = build_genparams(h, *gp)) return rc;
       *img = make_image(gp);
+      *win = *img;
     } else {
       auto dp = std::make_shared<DevParams>();
       if (const int rc = build_devparams(h, *dp)) return rc;
       *img = make_image(dp);
+      HostParams hw = h;
+      auto gp = std::make_shared<gen::GenParams>();
+      *win = build_genparams(hw, *gp) == NET_OK ? make_image(gp) : Image();
     }
     return NET_OK;
   };
-  Image img;
-  if (const int rc = build(*hp, &img)) return rc;
+  Image img, win;
+  if (const int rc = build(*hp, &img, &win)) return rc;
   if (hp->xr) {
     // off the float envelope: fold the constant filters into an equivalent copy (the reference
     // ranges, NET_ERR_RANGE included, were checked on the set as given) and keep that image, float
@@ -1458,9 +1573,10 @@ int install(std::shared_ptr<HostParams> hp) {
     HostParams fh = *hp;
     Ranges rg;
     if (check_ranges(fh, rg) == NET_OK && (fh.folded = fold_constant_filters(fh, rg)) > 0) {
-      Image fimg;
-      if (build(fh, &fimg) == NET_OK) {
+      Image fimg, fwin;
+      if (build(fh, &fimg, &fwin) == NET_OK) {
         img = fimg;
+        win = fwin;
         hp->xr = fh.xr;
         hp->xr_layer = fh.xr_layer;
         hp->xr_filter = fh.xr_filter;
@@ -1471,6 +1587,7 @@ int install(std::shared_ptr<HostParams> hp) {
   std::lock_guard<std::mutex> lk(g_mu);
   g_host = hp;
   g_img = img;
+  g_win = win;
   g_gen++;
   return NET_OK;
 }
@@ -1539,6 +1656,7 @@ void net_params_unload(void) {
     std::lock_guard<std::mutex> lk(g_mu);
     g_host.reset();
     g_img = Image();
+    g_win = Image();
     g_gen++;
   }
   // free every device copy once the launches that may read it have finished
@@ -1551,6 +1669,7 @@ void net_params_unload(void) {
     for (DevImage& im : ds.images) free_image(im);
     ds.images.clear();
     ds.cur = nullptr;
+    ds.wcur = nullptr;
   }
 }
 
@@ -1614,7 +1733,7 @@ int batch_async_s(const Snapshot& s, const int8_t* x, int8_t* y, size_t B, int d
   int rc = ensure_device(ds, device, s);
   if (rc) return rc;
   rc = launch_forward(v, s.img.data.get(), ds, ds.cur, x, y, B, (hipStream_t)stream, nullptr, layout, qs);
-  if (rc == NET_OK && B) note_launch(ds, (hipStream_t)stream);
+  if (rc == NET_OK && B) note_launch(ds, ds.cur, (hipStream_t)stream);
   return rc;
 }
 
@@ -1656,6 +1775,28 @@ int net_model_compute_batch_ct(const int8_t* x, int8_t* y, size_t B, int device,
 
 int net_model_compute_batch_f32(const float* x, int8_t* y, size_t B, float scale, int device, void* stream) {
   return batch_async((const int8_t*)x, y, B, device, stream, 2, scale);
+}
+
+size_t net_windows_count(size_t L, size_t hop) {
+  const Snapshot s = snapshot();
+  return s.host ? windows_count(s.host->d, L, hop) : 0;
+}
+
+size_t net_windows_row_stride(size_t L) { return windows_row_stride(L); }
+
+size_t net_windows_workspace(size_t L) {
+  const size_t rs = windows_row_stride(L);
+  return rs > SIZE_MAX / 16 ? 0 : 16 * rs;
+}
+
+int net_model_compute_windows(const int8_t* x, int layout, size_t L, size_t hop, int8_t* y, void* ws, size_t ws_bytes,
+                              int device, void* stream) {
+  return windows_async(x, layout, false, L, hop, 0.0f, y, ws, ws_bytes, device, stream);
+}
+
+int net_model_compute_windows_f32(const float* x, size_t L, size_t hop, float scale, int8_t* y, void* ws,
+                                  size_t ws_bytes, int device, void* stream) {
+  return windows_async(x, 1, true, L, hop, scale, y, ws, ws_bytes, device, stream);
 }
 
 int net_quantize_input_f32(const float* x, int8_t* y, size_t B, int C, int T, float scale, int device, void* stream) {

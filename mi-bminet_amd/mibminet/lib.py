@@ -35,6 +35,8 @@ EXPORTED_SYMBOLS = (
     "net_pack_trials_i8", "net_model_compute_batch_multi", "net_model_compute_batch_ct",
     "net_model_compute_batch_multi_ct", "net_launch_info_ct", "net_model_compute_batch_f32",
     "net_model_compute_batch_ct_sync", "net_params_info", "net_params_load_arrays",
+    "net_windows_count", "net_windows_row_stride", "net_windows_workspace",
+    "net_model_compute_windows", "net_model_compute_windows_f32",
 )
 NET_PATH_FLOAT, NET_PATH_EXACT, NET_PATH_GENERAL = 0, 1, 2
 
@@ -117,6 +119,16 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     L.net_model_compute_batch_ct_sync.restype = i
     L.net_params_info.argtypes = [vp]
     L.net_params_info.restype = i
+    L.net_windows_count.argtypes = [sz, sz]
+    L.net_windows_count.restype = sz
+    L.net_windows_row_stride.argtypes = [sz]
+    L.net_windows_row_stride.restype = sz
+    L.net_windows_workspace.argtypes = [sz]
+    L.net_windows_workspace.restype = sz
+    L.net_model_compute_windows.argtypes = [vp, i, sz, sz, vp, vp, sz, i, vp]
+    L.net_model_compute_windows.restype = i
+    L.net_model_compute_windows_f32.argtypes = [vp, sz, sz, ctypes.c_float, vp, vp, sz, i, vp]
+    L.net_model_compute_windows_f32.restype = i
     # test hooks (include/mibminet_testing.h)
     L.mibminet_test_force_general.argtypes = [i]
     L.mibminet_test_folded_filters.argtypes = [vp]
@@ -363,6 +375,77 @@ def forward_f32_torch(x, scale: float, stream=None):
     s = torch.cuda.current_stream(x.device) if stream is None else stream
     _check(load().net_model_compute_batch_f32(x.data_ptr(), y.data_ptr(), B, scale, x.device.index or 0,
                                               s.cuda_stream), "net_model_compute_batch_f32")
+    return y
+
+
+def windows_count(L: int, hop: int) -> int:
+    """net_windows_count: windows of the loaded network's T samples at hop ``hop`` in L samples."""
+    return int(load().net_windows_count(L, hop))
+
+
+def windows_row_stride(L: int) -> int:
+    """net_windows_row_stride: bytes between the rows of the layer-1 workspace of L samples."""
+    return int(load().net_windows_row_stride(L))
+
+
+def windows_workspace(L: int) -> int:
+    """net_windows_workspace: bytes of the layer-1 workspace ([16][row_stride] int8) of L samples."""
+    return int(load().net_windows_workspace(L))
+
+
+def _check_recording(x, dtype: str, channels_first: bool):
+    """Raises ValueError unless ``x`` is a contiguous 2-D device tensor of ``dtype`` holding a
+    recording of the loaded network's C channels ([C][L] or [L][C]); returns L.  The C ABI sees
+    only a pointer and a length, so another element type or orientation would otherwise run."""
+    d = _dims()
+    want = f"[{d.C}][L]" if channels_first else f"[L][{d.C}]"
+    if str(getattr(x, "dtype", "")) != f"torch.{dtype}" or not x.is_cuda or not x.is_contiguous():
+        raise ValueError(f"the recording must be a contiguous {dtype} device tensor {want}")
+    if x.dim() != 2 or x.shape[0 if channels_first else 1] != d.C:
+        raise ValueError(f"the recording must be {want}, got {tuple(x.shape)}")
+    return int(x.shape[1 if channels_first else 0])
+
+
+def _windows_buffers(x, L: int, hop: int):
+    import torch
+
+    if hop < 1:
+        raise ValueError("hop must be at least 1")
+    W = windows_count(L, hop)
+    y = torch.empty((W, _dims().N), dtype=torch.int8, device=x.device)
+    ws = torch.empty((16, windows_row_stride(L)), dtype=torch.int8, device=x.device)
+    return y, ws
+
+
+def forward_windows_torch(x, hop: int, layout: str = "ct", stream=None, return_y1: bool = False):
+    """net_model_compute_windows: x is a CUDA/HIP int8 recording, ``layout`` "ct" = [C][L]
+    (channel-major) or "tc" = [L][C] (time-major), any byte alignment.  Returns the logits [W][N]
+    of the windows x[:, w*hop : w*hop + T], W = windows_count(L, hop), each row what
+    forward_ct_torch returns for that window; with ``return_y1`` also the workspace
+    [16][row_stride] int8, whose row f holds layer 1's filter f over the whole recording."""
+    if layout not in ("ct", "tc"):
+        raise ValueError('layout must be "ct" ([C][L]) or "tc" ([L][C])')
+    L = _check_recording(x, "int8", layout == "ct")
+    y, ws = _windows_buffers(x, L, hop)
+    import torch
+
+    s = torch.cuda.current_stream(x.device) if stream is None else stream
+    _check(load().net_model_compute_windows(x.data_ptr(), 1 if layout == "ct" else 0, L, hop, y.data_ptr(),
+                                            ws.data_ptr(), ws.numel(), x.device.index or 0, s.cuda_stream),
+           "net_model_compute_windows")
+    return (y, ws) if return_y1 else y
+
+
+def forward_windows_f32_torch(x, hop: int, scale: float, stream=None):
+    """net_model_compute_windows_f32: x is a CUDA/HIP float32 recording [C][L], quantised per
+    sample as forward_f32_torch does; returns the logits [W][N] of its sliding windows."""
+    L = _check_recording(x, "float32", True)
+    y, ws = _windows_buffers(x, L, hop)
+    import torch
+
+    s = torch.cuda.current_stream(x.device) if stream is None else stream
+    _check(load().net_model_compute_windows_f32(x.data_ptr(), L, hop, scale, y.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                x.device.index or 0, s.cuda_stream), "net_model_compute_windows_f32")
     return y
 
 
