@@ -249,6 +249,39 @@ int net_model_compute_windows(const int8_t* x, int layout, size_t L, size_t hop,
 int net_model_compute_windows_f32(const float* x, size_t L, size_t hop, float scale, int8_t* y, void* ws,
                                   size_t ws_bytes, int device, void* stream);
 
+/* ---- epochs from a wider array: channel map, row stride and onsets --------------------------
+ * The source x is a flat DEVICE array of n_elems elements; epoch e, network channel c, sample t is
+ * element onsets[e] + channels[c]*row_stride + t.  One formula covers a recording [R][L] with cue
+ * markers (row_stride = L, onsets = sample indices), a batch [B][R][Tf] cropped at t0 with a
+ * channel subset (row_stride = Tf, onsets[b] = b*R*Tf + t0) and overlapping or irregular windows;
+ * the kernel reads each epoch's rows where they lie, so no gathered [E][C][T] copy is written
+ * ("Epochs from a wider array").  Duplicate and unsorted channels and onsets are
+ * allowed.
+ * x (int8, any byte alignment), onsets (E int64, 8-byte aligned), y ([E][N] int8, 4-byte aligned)
+ * and n_bad (one int32, 4-byte aligned, or NULL) are DEVICE pointers; channels is a HOST array of
+ * the loaded network's C entries, NULL = 0 .. C-1.  span = max(channels)*row_stride + T elements,
+ * and an onset is valid iff 0 <= onset <= n_elems - span.  Logit row e of a valid onset is
+ * byte-identical to what net_model_compute_batch_ct returns for the materialised [C][T] trial.
+ * The onsets live on the device, so the kernel checks them: from an invalid onset no address is
+ * formed, its logit row is written as N zeros, and *n_bad (if non-NULL; the caller zeroes it) is
+ * incremented once per invalid onset.  Enqueued on `stream` (NULL = null stream), no host sync, no
+ * allocation: capturable into a HIP graph after one eager call has uploaded the parameters.
+ * Checks, all before any device call: NET_ERR_NO_PARAMS first; then NET_ERR_INVALID for a null x,
+ * y or onsets with E > 0, a misaligned y, n_bad or onsets, row_stride == 0, a negative channel, a
+ * span that overflows or exceeds n_elems, sizeof(element)*span + 6 >= 2^31 (each epoch is one
+ * buffer view with 32-bit offsets; n_elems itself has no limit), E > INT32_MAX - 65,535 and a bad
+ * device; NET_ERR_UNSUPPORTED for a network outside the general kernels' family.  E == 0 returns
+ * NET_OK and touches nothing. */
+int net_model_compute_epochs(const int8_t* x, size_t n_elems, size_t row_stride, const int32_t* channels,
+                             const int64_t* onsets, size_t E, int8_t* y, int32_t* n_bad, int device, void* stream);
+
+/* The same for a float32 source (4-byte aligned), quantised per sample exactly as
+ * net_model_compute_batch_f32 / net_quantize_input_f32 do: scale in [2^-60, 2^60], NET_ERR_RANGE
+ * otherwise (NET_ERR_INVALID for a scale that is not positive and finite). */
+int net_model_compute_epochs_f32(const float* x, size_t n_elems, size_t row_stride, const int32_t* channels,
+                                 const int64_t* onsets, size_t E, float scale, int8_t* y, int32_t* n_bad,
+                                 int device, void* stream);
+
 /* Several devices from one host thread (static split, no collectives): shard i is
  * x[i] / y[i] / B[i] on devices[i] (DEVICE pointers of that device).  Every shard is enqueued
  * before any is waited for, so the devices run concurrently.  streams == NULL: each device's null

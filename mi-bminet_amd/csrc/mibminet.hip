@@ -25,6 +25,7 @@
 #include "forward_wg.hpp"
 #include "forward_gen.hpp"
 #include "forward_win.hpp"
+#include "forward_ep.hpp"
 #include "quantize.hpp"
 #include "classify.hpp"
 
@@ -1401,6 +1402,91 @@ int windows_async(const void* x, int arg_layout, bool f32, size_t L, size_t hop,
   return rc;
 }
 
+// ---- epochs cut out of a wider array (forward_ep.hpp) -----------------------------------------
+// hg: the host copy of the gen::GenParams p points to; last = n_elems - span.
+template <int L, bool RB, bool XR, bool CB>
+int launch_epochs_q(DeviceState& ds, const gen::GenParams& hg, const void* p, const int8_t* x, const int64_t* onsets,
+                    size_t E, int8_t* y, int32_t* n_bad, long long last, unsigned span_bytes, size_t row_stride,
+                    const ep::ChanTab& tab, hipStream_t st, float qs) {
+  const int lds = gen::carve_of(hg.C, hg.T, hg.N, hg.T8, hg.T64A, hg.NB1, hg.MT, hg.NTT, gen::F32).bytes;
+  const void* kern = (const void*)ep::k_forward_ep<L, RB, XR, CB>;
+  const size_t cap = (size_t)ds.cus * (size_t)gen_blocks_per_cu(kern, lds);
+  const int grid = (int)(E < cap ? E : cap);
+  const float qy = qs > 0.0f ? 1.0f / qs : 0.0f;  // RN(1 / scale), as the batched float kernels
+  hipLaunchKernelGGL((ep::k_forward_ep<L, RB, XR, CB>), dim3(grid), dim3(gen::NT), (size_t)lds, st,
+                     (const gen::GenParams*)p, x, (const long long*)onsets, y, (int*)n_bad, (int)E, last, span_bytes,
+                     (unsigned long long)row_stride, tab, qs, qy);
+  const int rc = hip_err(hipGetLastError());
+  if (rc == NET_OK) note_launch(ds, p, st);
+  return rc;
+}
+
+template <int L>
+int launch_epochs_t(DeviceState& ds, const gen::GenParams& hg, const void* p, const int8_t* x, const int64_t* onsets,
+                    size_t E, int8_t* y, int32_t* n_bad, long long last, unsigned span_bytes, size_t row_stride,
+                    const ep::ChanTab& tab, hipStream_t st, float qs) {
+  const int sel = (hg.rb ? 4 : 0) | (hg.xr ? 2 : 0) | (hg.lo == -127 ? 1 : 0);
+  switch (sel) {
+    case 0: return launch_epochs_q<L, false, false, false>(ds, hg, p, x, onsets, E, y, n_bad, last, span_bytes, row_stride, tab, st, qs);
+    case 1: return launch_epochs_q<L, false, false, true>(ds, hg, p, x, onsets, E, y, n_bad, last, span_bytes, row_stride, tab, st, qs);
+    case 2: return launch_epochs_q<L, false, true, false>(ds, hg, p, x, onsets, E, y, n_bad, last, span_bytes, row_stride, tab, st, qs);
+    case 3: return launch_epochs_q<L, false, true, true>(ds, hg, p, x, onsets, E, y, n_bad, last, span_bytes, row_stride, tab, st, qs);
+    case 4: return launch_epochs_q<L, true, false, false>(ds, hg, p, x, onsets, E, y, n_bad, last, span_bytes, row_stride, tab, st, qs);
+    case 5: return launch_epochs_q<L, true, false, true>(ds, hg, p, x, onsets, E, y, n_bad, last, span_bytes, row_stride, tab, st, qs);
+    case 6: return launch_epochs_q<L, true, true, false>(ds, hg, p, x, onsets, E, y, n_bad, last, span_bytes, row_stride, tab, st, qs);
+    default: return launch_epochs_q<L, true, true, true>(ds, hg, p, x, onsets, E, y, n_bad, last, span_bytes, row_stride, tab, st, qs);
+  }
+}
+
+// f32: the float32 entry (scale qs).  Every argument and parameter check comes before the first
+// device call.
+int epochs_async(const void* x, bool f32, size_t n_elems, size_t row_stride, const int32_t* channels,
+                 const int64_t* onsets, size_t E, float qs, int8_t* y, int32_t* n_bad, int device, void* stream) {
+  const Snapshot s = snapshot();
+  if (!s.host) return NET_ERR_NO_PARAMS;
+  const Dims& d = s.host->d;
+  if (E && (!x || !y || !onsets)) return NET_ERR_INVALID;
+  if (((uintptr_t)y & 3) != 0 || ((uintptr_t)n_bad & 3) != 0 || ((uintptr_t)onsets & 7) != 0) return NET_ERR_INVALID;
+  if (f32 && ((uintptr_t)x & 3) != 0) return NET_ERR_INVALID;
+  if (row_stride == 0) return NET_ERR_INVALID;
+  size_t cmax = (size_t)d.C - 1;  // channels == NULL: rows 0 .. C - 1
+  if (channels) {
+    cmax = 0;
+    for (int c = 0; c < d.C; c++) {
+      if (channels[c] < 0) return NET_ERR_INVALID;
+      cmax = std::max(cmax, (size_t)channels[c]);
+    }
+  }
+  // span = max(channels) row_stride + T elements, inside the source
+  if (cmax && row_stride > (SIZE_MAX - (size_t)d.T) / cmax) return NET_ERR_INVALID;
+  const size_t span = cmax * row_stride + (size_t)d.T;
+  if (span > n_elems) return NET_ERR_INVALID;
+  // each epoch is one buffer view with 32-bit offsets (delta <= 3 and the dword rounding on top)
+  const size_t esz = f32 ? sizeof(float) : 1;
+  if (span > (((size_t)1 << 31) - 7) / esz) return NET_ERR_INVALID;
+  // epoch indices are int in the kernel: e + gridDim.x (grid <= 2 per CU) must not wrap
+  if (E > (size_t)INT32_MAX - 65535) return NET_ERR_INVALID;
+  if (device < 0 || device >= MAX_DEVICES) return NET_ERR_INVALID;
+  if (f32 && !(qs > 0.0f && qs <= 3.4e38f)) return NET_ERR_INVALID;
+  if (f32 && !(qs >= 0x1p-60f && qs <= 0x1p60f)) return NET_ERR_RANGE;  // batch_async_s's domain
+  if (!s.win.data) return NET_ERR_UNSUPPORTED;
+  if (E == 0) return NET_OK;
+  ep::ChanTab tab;
+  for (int c = 0; c < 64; c++) tab.c[c] = c < d.C ? (channels ? channels[c] : c) : 0;
+  const long long last = (long long)std::min(n_elems - span, (size_t)INT64_MAX);
+  if (const int rc = check_device(device)) return rc;
+  DeviceState& ds = g_devs[device];
+  std::lock_guard<std::mutex> lk(ds.mu);
+  DeviceGuard guard(device);
+  if (guard.err != hipSuccess) return hip_err(guard.err);
+  if (const int rc = ensure_device_win(ds, device, s)) return rc;
+  const gen::GenParams& hg = *(const gen::GenParams*)s.win.data.get();
+  const hipStream_t st = (hipStream_t)stream;
+  const unsigned sb = (unsigned)(esz * span);
+  if (f32) return launch_epochs_t<gen::F32>(ds, hg, ds.wcur, (const int8_t*)x, onsets, E, y, n_bad, last, sb, row_stride, tab, st, qs);
+  return launch_epochs_t<gen::CT>(ds, hg, ds.wcur, (const int8_t*)x, onsets, E, y, n_bad, last, sb, row_stride, tab, st, qs);
+}
+
 // Runs one reference-layout single-trial stage on the single-trial device.
 // stage 0 = whole model (input [T][C_ALIGN]); 1..5 = net_layerN; 6 = flip.
 int run_single(int stage, const int8_t* in, int8_t* out) {
@@ -1797,6 +1883,17 @@ int net_model_compute_windows(const int8_t* x, int layout, size_t L, size_t hop,
 int net_model_compute_windows_f32(const float* x, size_t L, size_t hop, float scale, int8_t* y, void* ws,
                                   size_t ws_bytes, int device, void* stream) {
   return windows_async(x, 1, true, L, hop, scale, y, ws, ws_bytes, device, stream);
+}
+
+int net_model_compute_epochs(const int8_t* x, size_t n_elems, size_t row_stride, const int32_t* channels,
+                             const int64_t* onsets, size_t E, int8_t* y, int32_t* n_bad, int device, void* stream) {
+  return epochs_async(x, false, n_elems, row_stride, channels, onsets, E, 0.0f, y, n_bad, device, stream);
+}
+
+int net_model_compute_epochs_f32(const float* x, size_t n_elems, size_t row_stride, const int32_t* channels,
+                                 const int64_t* onsets, size_t E, float scale, int8_t* y, int32_t* n_bad,
+                                 int device, void* stream) {
+  return epochs_async(x, true, n_elems, row_stride, channels, onsets, E, scale, y, n_bad, device, stream);
 }
 
 int net_quantize_input_f32(const float* x, int8_t* y, size_t B, int C, int T, float scale, int device, void* stream) {

@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = (
     "net_model_compute_batch_ct_sync", "net_params_info", "net_params_load_arrays",
     "net_windows_count", "net_windows_row_stride", "net_windows_workspace",
     "net_model_compute_windows", "net_model_compute_windows_f32",
+    "net_model_compute_epochs", "net_model_compute_epochs_f32",
 )
 NET_PATH_FLOAT, NET_PATH_EXACT, NET_PATH_GENERAL = 0, 1, 2
 
@@ -129,6 +130,10 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     L.net_model_compute_windows.restype = i
     L.net_model_compute_windows_f32.argtypes = [vp, sz, sz, ctypes.c_float, vp, vp, sz, i, vp]
     L.net_model_compute_windows_f32.restype = i
+    L.net_model_compute_epochs.argtypes = [vp, sz, sz, vp, vp, sz, vp, vp, i, vp]
+    L.net_model_compute_epochs.restype = i
+    L.net_model_compute_epochs_f32.argtypes = [vp, sz, sz, vp, vp, sz, ctypes.c_float, vp, vp, i, vp]
+    L.net_model_compute_epochs_f32.restype = i
     # test hooks (include/mibminet_testing.h)
     L.mibminet_test_force_general.argtypes = [i]
     L.mibminet_test_folded_filters.argtypes = [vp]
@@ -447,6 +452,92 @@ def forward_windows_f32_torch(x, hop: int, scale: float, stream=None):
     _check(load().net_model_compute_windows_f32(x.data_ptr(), L, hop, scale, y.data_ptr(), ws.data_ptr(), ws.numel(),
                                                 x.device.index or 0, s.cuda_stream), "net_model_compute_windows_f32")
     return y
+
+
+def _channel_table(channels, C: int):
+    """The ctypes int32[C] host table of ``channels`` (None: NULL, rows 0 .. C-1)."""
+    if channels is None:
+        return None
+    ch = [int(c) for c in (channels.tolist() if hasattr(channels, "tolist") else channels)]
+    if len(ch) != C:
+        raise ValueError(f"channels must list the network's {C} channels, got {len(ch)}")
+    if min(ch) < 0 or max(ch) >= 2**31:
+        raise ValueError("channels must be non-negative row indices")
+    return (ctypes.c_int32 * C)(*ch)
+
+
+def forward_epochs_torch(x, onsets, channels=None, row_stride: Optional[int] = None, scale: Optional[float] = None,
+                         stream=None, check: bool = True):
+    """net_model_compute_epochs / _f32: epochs of the loaded network's C x T read straight out of a
+    wider array.  ``x`` is any contiguous CUDA/HIP int8 or float32 tensor, used flat (``scale`` is
+    required iff it is float32: the input quantiser's, as forward_f32_torch); epoch e, channel c,
+    sample t is flat element ``onsets[e] + channels[c] * row_stride + t``.  ``row_stride`` defaults
+    to ``x.shape[-1]``, ``channels`` (C row indices on the host) to 0 .. C-1, and ``onsets`` is an
+    int64 tensor or a sequence.  Returns the logits [E][N] int8, row e what forward_ct_torch
+    returns for the materialised epoch.  The rows of onsets outside the source are zero; with
+    ``check`` their count is read back (a host sync) and a ValueError names it."""
+    import torch
+
+    d = _dims()
+    if not hasattr(x, "is_cuda") or x.dtype not in (torch.int8, torch.float32) or not x.is_cuda or not x.is_contiguous():
+        raise ValueError("x must be a contiguous int8 or float32 device tensor")
+    f32 = x.dtype == torch.float32
+    if f32 != (scale is not None):
+        raise ValueError("scale is required for a float32 source and not accepted for an int8 one")
+    if x.dim() < 1:
+        raise ValueError("x must have at least one dimension")
+    rs = int(x.shape[-1]) if row_stride is None else int(row_stride)
+    if rs < 1:
+        raise ValueError("row_stride must be at least 1")
+    tab = _channel_table(channels, d.C)
+    if isinstance(onsets, torch.Tensor):
+        if onsets.dtype != torch.int64 or onsets.dim() != 1:
+            raise ValueError("onsets must be a 1-D int64 tensor or a sequence of ints")
+    else:
+        onsets = torch.as_tensor([int(o) for o in onsets], dtype=torch.int64).reshape(-1)
+    s = torch.cuda.current_stream(x.device) if stream is None else stream
+    with torch.cuda.stream(s):  # the onsets' copy and the counter's zeroing precede the launch on its stream
+        on = onsets.to(x.device).contiguous()
+        nbad = torch.zeros((1,), dtype=torch.int32, device=x.device) if check else None
+    E = int(on.numel())
+    y = torch.empty((E, d.N), dtype=torch.int8, device=x.device)
+    head = (x.data_ptr(), x.numel(), rs, tab, on.data_ptr() if E else None, E)
+    tail = (y.data_ptr() if E else None, nbad.data_ptr() if nbad is not None else None, x.device.index or 0, s.cuda_stream)
+    if f32:
+        _check(load().net_model_compute_epochs_f32(*head, scale, *tail), "net_model_compute_epochs_f32")
+    else:
+        _check(load().net_model_compute_epochs(*head, *tail), "net_model_compute_epochs")
+    if nbad is not None and E:
+        s.synchronize()
+        bad = int(nbad.item())
+        if bad:
+            raise ValueError(f"{bad} of {E} onsets lie outside the source (their logit rows are zero)")
+    return y
+
+
+def forward_crop_torch(x, t0: int, channels=None, scale: Optional[float] = None, stream=None):
+    """Every trial of a batch ``x`` [B][R][Tf] (int8, or float32 with ``scale``) cropped to samples
+    t0 .. t0 + T - 1 of the rows ``channels`` (C row indices < R; default 0 .. C-1), through
+    forward_epochs_torch: row_stride = Tf, onsets[b] = b R Tf + t0, built on the device.  Returns
+    the logits [B][N]."""
+    import torch
+
+    d = _dims()
+    if not hasattr(x, "dim") or x.dim() != 3:
+        raise ValueError("x must be a batch [B][R][Tf]")
+    B, R, Tf = (int(v) for v in x.shape)
+    if t0 < 0 or t0 + d.T > Tf:
+        raise ValueError(f"the crop t0 = {t0}, T = {d.T} does not fit in Tf = {Tf}")
+    ch = list(range(d.C)) if channels is None else [int(c) for c in channels]
+    if len(ch) != d.C or min(ch) < 0 or max(ch) >= R:
+        raise ValueError(f"channels must be {d.C} row indices below R = {R}")
+    if not x.is_cuda:
+        raise ValueError("x must be a device tensor")
+    s = torch.cuda.current_stream(x.device) if stream is None else stream
+    with torch.cuda.stream(s):
+        onsets = torch.arange(B, dtype=torch.int64, device=x.device) * (R * Tf) + t0
+    # every onset is in range by the checks above: no counter, no host sync
+    return forward_epochs_torch(x, onsets, channels=ch, row_stride=Tf, scale=scale, stream=s, check=False)
 
 
 def quantize_input_torch(x, scale: float, stream=None):
