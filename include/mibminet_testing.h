@@ -48,7 +48,7 @@ int mibminet_test_device_images(int device);
 
 /* Exact-division builds (Cfg::XR, parameter sets outside the float requant envelope): the
  * integer division the kernels use at layers 1, 2 and 4 (forward_common.hpp, xdiv; constants from
- * mibminet.hip, xdiv_consts).  _host: the device instruction sequence emulated on the host,
+ * requant_host.hpp, xdiv_consts).  _host: the device instruction sequence emulated on the host,
  * q[i] = xdiv(e[i], d) for i < n (no device needed).  _gpu: the device function itself over
  * e = e0 .. e0 + count - 1 against C division in 64 bits, on `device`; *mismatches = the number of
  * e where they differ.  d != 0 (NET_ERR_INVALID otherwise). */
@@ -73,6 +73,13 @@ int mibminet_test_force_general(int on);
 /* FNV-1a digest of the loaded set's device parameter image (the bytes uploaded to every device):
  * equal digests mean the two loads produce the same kernels' inputs. */
 int mibminet_test_image_digest(uint64_t* digest);
+
+/* The bytes of one parameter image of the loaded set: which = 0 the batched kernels' image (what
+ * mibminet_test_image_digest hashes), 1 the window and epoch kernels' image.  *bytes is always set:
+ * the image's size, or 0 when there is none (NET_ERR_NO_PARAMS; NET_ERR_UNSUPPORTED for a set
+ * without a window image).  buf == NULL only asks for the size; otherwise cap >= *bytes
+ * (NET_ERR_INVALID if not) and the image is copied to buf. */
+int mibminet_test_image_copy(int which, void* buf, size_t cap, size_t* bytes);
 
 /* Number of constant filters the loaded set had folded (zero weights, offset +-y, factor +-1) to
  * stay on the float requant kernels: 0 unless the set as given needed exact division. */

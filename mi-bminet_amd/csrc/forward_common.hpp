@@ -2,7 +2,7 @@
 // (forward_wg.hpp).
 //
 // Requantisation y = clip(trunc((acc + off) / fac), -128, 127) is computed as
-// clip(int(float(acc + off) * r)) with r chosen on the host (mibminet.hip: choose_reciprocal) and
+// clip(int(float(acc + off) * r)) with r chosen on the host (requant_host.hpp: choose_reciprocal) and
 // verified at every step boundary of the clipped output range, so it is bit-exact to C's integer
 // division for every reachable accumulator.  Parameter sets outside that float envelope run the
 // exact-division builds (Cfg::XR: xdiv below) at layers 1, 2 and 4.
@@ -12,18 +12,17 @@
 
 #include <type_traits>
 
+#include "net_consts.hpp"  // F2, N_OUT, FMAGIC_I
+
 namespace mib {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-constexpr int F2 = 16;          // filters (F1 == F2, D == 1)
-constexpr int N_OUT = 4;        // classes
 constexpr int L2_TAPS = 64;
 constexpr int L3_TAPS = 16;
 constexpr int ND5_MAX = 96;     // dwords of the layer-4 output [F2][T64_ALIGN] (F2*T64_ALIGN <= 384)
-constexpr int FMAGIC_I = 0x4B400000;   // bit pattern of 1.5 * 2^23
 constexpr float FMAGIC_F = 12582912.0f; // 1.5 * 2^23
 // REORDER_BN pooling bias: the layer-2 MFMA chains start from a bias B (the bits of a
 // float MFMA srcC inline constant), so every conv value a lies at a + B with no wrap (|a| < 2^22),
@@ -82,14 +81,14 @@ struct SmallParams {
   v4i l2_tpar[F2];        // layer-2 tail per filter: {PBIAS_TAIL + thr, off + 8 thr, bits of r, 0}
                           // (thr = -(net_l2_offset >> 3); off + 8 thr = net_l2_offset & 7);
                           // XR: {.., .., xdiv magic, shift word}
-  int l4_thr[F2];         // -(net_l4_offset >> 3), clamped to the conv range (mibminet.hip)
+  int l4_thr[F2];         // -(net_l4_offset >> 3), clamped to the conv range (images.hpp)
   int l4_offm[F2];        // net_l4_offset + 8 thr
   union {
     float l4_r[F2];
     unsigned l4_m[F2];    // XR: xdiv magic
   };
   // plain (non-REORDER_BN) layer-2/4 branches: per-element BN with offset >> 3 and factor >> 3 in
-  // the floor form (mibminet.hip, choose_floor_form): MFMA C-init = per-filter magic bits + offset,
+  // the floor form (requant_host.hpp, choose_floor_form): MFMA C-init = per-filter magic bits + offset,
   // reciprocal r and integer-valued c, so that fma(acc bits, r, c) = FMAGIC + floor(element).
   // XR: C-init = offset >> 3, xdiv magic and shift word; l2_xs / l4_xs are also the shift words of
   // the REORDER_BN builds' layer-2 / layer-4 requant (whose plain fields are unused)
@@ -218,12 +217,12 @@ __device__ __forceinline__ f2 mul2(float a, float b, float r) { return (f2){a * 
 
 // Exact C division trunc(e / d) for every int32 e and d != 0 (the reference's int32 division;
 // INT_MIN / -1 is refused at load), for the exact-division builds (Cfg::XR).  (lo, hi) are the two
-// halves of the double r = sign(d) RU(1 / |d|) (mibminet.hip, xdiv_consts): trunc(e r) in double
+// halves of the double r = sign(d) RU(1 / |d|) (requant_host.hpp, xdiv_consts): trunc(e r) in double
 // (v_cvt_f64_i32, v_mul_f64, v_cvt_i32_f64) equals trunc(e / d).  For e, d > 0 with e / d = q + f:
 // e r >= e / d, so the rounded product is >= q; e r - e / d <= e 2^-52 / d, and the distance from
 // q + f to q + 1 is >= 1 / d > 1.5 (e / d) 2^-52 for |e| <= 2^31, more than the error plus half an
 // ulp of the product, so it stays below q + 1.  The other signs are the mirror image.  Proof and
-// host emulation: mibminet.hip, xdiv_consts / xdiv_host; every int32 dividend on the device for
+// host emulation: requant_host.hpp, xdiv_consts / xdiv_host; every int32 dividend on the device for
 // three divisors and every quotient step for many more: tests/test_gpu_xr.py.  (Round 5 used a
 // 32 x 32 -> 64-bit integer multiply-shift, about twice the issue cycles.)
 __device__ __forceinline__ int xdiv(int e, unsigned lo, int hi) {

@@ -32,7 +32,7 @@
 //   layer5  N-class linear layer: four classes per pass, 16 lanes each, v_dot4 + a DPP prefix.
 //                                                               (reference: layer5.c:43-89)
 // Requantisation as in the compiled kernels: where the host proves the float form exact on every
-// reachable value (mibminet.hip: choose_reciprocal, choose_floor_form) the XR = false build runs
+// reachable value (requant_host.hpp: choose_reciprocal, choose_floor_form) the XR = false build runs
 // it; any requant without a proven float form sends the set to the XR = true build, exact
 // division (xdiv, forward_common.hpp) at layers 1-4.  Layer 5 always divides exactly (its
 // sums pass 2^24 at T = 4096).  CB: balanced clipping ([-127, 127], golden model clip_balanced).
@@ -66,7 +66,7 @@ struct SmallG {
 };
 static_assert(sizeof(SmallG) % 16 == 0, "SmallG is copied in 16-byte pieces");
 
-// Device parameter image of the general path (built on the host: mibminet.hip, build_genparams).
+// Device parameter image of the general path (built on the host: images.hpp, build_genparams).
 struct GenParams {
   int C, T, N, T8;
   int T64, T64A, NB1, MT;       // NB1: layer-1 blocks of 16 samples; MT: full layer-2 tiles of 1024 outputs
@@ -353,7 +353,7 @@ struct L2C {  // a wave's layer-2 constants (filters 2 wave, 2 wave + 1)
   float r[2], c[2];
 };
 
-// floor form of one plain-branch element (mibminet.hip, choose_floor_form): acc holds the bits of
+// floor form of one plain-branch element (requant_host.hpp, choose_floor_form): acc holds the bits of
 // float(M + x) (MFMA C-init M + offset), and bits(fmed3(fma(acc, r, c), K, K + emax)) - bits(K) =
 // clamp(floor(x / fac), 0, emax) = the element after its clip and ReLU
 template <int EMAX>

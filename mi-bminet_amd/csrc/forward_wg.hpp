@@ -1044,7 +1044,7 @@ __device__ __forceinline__ void layer1(Rsrc rcur, Rsrc rnext, int8_t* smem_y1, R
 // ---- layer 2 ---------------------------------------------------------------------------------
 // Plain (non-REORDER_BN) branch, layer2.c:139-210: each element requantised and clipped
 // (func_xcorr_scale -> transform.c:224), ReLU, sum of 8, >> 3.  Behind the ReLU, trunc equals
-// floor, so each element is the floor form of mibminet.hip (choose_floor_form): acc holds the float
+// floor, so each element is the floor form of requant_host.hpp (choose_floor_form): acc holds the float
 // bits of M + x (C-init = per-filter magic + offset) and fma(bits, r, c) = FMAGIC + floor(x / f) on
 // every reachable x (host-verified); fmed3 to [FMAGIC, FMAGIC + 127] is the clip and the ReLU, and
 // the bits of FMAGIC + e are FMAGIC_I + e, so a window's sum is its bits' integer sum minus

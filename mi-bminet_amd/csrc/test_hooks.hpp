@@ -1,0 +1,139 @@
+// test_hooks.hpp — the hooks of include/mibminet_testing.h.  Included last by mibminet.hip: they
+// call into its internals and the headers it includes.
+#pragma once
+
+extern "C" {
+
+int mibminet_test_reciprocal(int32_t fac, int64_t vmax, int32_t kmax, int32_t magic, float* r, float* c) {
+  if (!r || (magic && !c) || vmax < 0 || vmax >= (1 << 24)) return NET_ERR_INVALID;
+  return choose_reciprocal(fac, r, magic ? c : nullptr, kmax, vmax) ? NET_OK : NET_ERR_RANGE;
+}
+
+int mibminet_test_quantize_f32(const float* x, int8_t* q, size_t n, float scale, int device, void* stream) {
+  if ((!x || !q) && n) return NET_ERR_INVALID;
+  if (const int rc = check_scale(scale)) return rc;
+  if (const int rc = check_device(device)) return rc;
+  if (n == 0) return NET_OK;
+  DeviceGuard guard(device);
+  if (guard.err != hipSuccess) return hip_err(guard.err);
+  hipLaunchKernelGGL(wg::k_quantize_flat, dim3(4096), dim3(256), 0, (hipStream_t)stream, x, q, (long long)n, scale,
+                     recip_scale(scale));
+  return hip_err(hipGetLastError());
+}
+
+int mibminet_test_floor_form(int32_t fac, int64_t emax, int64_t vmax, int32_t* mbits, float* r, float* c) {
+  if (!mbits || !r || !c || vmax < 0 || emax < 0) return NET_ERR_INVALID;
+  return choose_floor_form(fac, emax, vmax, mbits, r, c) ? NET_OK : NET_ERR_RANGE;
+}
+
+int mibminet_test_multi_order(int ndev, const int* devices, int fail_at, char* log, size_t len) {
+  if (!log || !len || ndev < 1 || ndev > MAX_DEVICES || !devices) return NET_ERR_INVALID;
+  std::string out;
+  auto prep = [&](int d) { out += "P" + std::to_string(d) + " "; return NET_OK; };
+  auto enq = [&](int i) {
+    out += "E" + std::to_string(i) + " ";
+    return i == fail_at ? NET_ERR_INVALID : NET_OK;
+  };
+  auto wait = [&](int n) { out += "W" + std::to_string(n) + " "; return NET_OK; };
+  const int rc = multi_driver(ndev, devices, true, prep, enq, wait);
+  std::snprintf(log, len, "%s", out.c_str());
+  return rc;
+}
+
+int mibminet_test_upload_stats(int64_t* uploads, int64_t* uploads_while_enqueueing) {
+  if (!uploads || !uploads_while_enqueueing) return NET_ERR_INVALID;
+  *uploads = g_uploads.load();
+  *uploads_while_enqueueing = g_uploads_enqueue.load();
+  return NET_OK;
+}
+
+int mibminet_test_xdiv_host(const int32_t* e, size_t n, int32_t d, int32_t* q) {
+  if ((!e || !q) && n) return NET_ERR_INVALID;
+  if (d == 0) return NET_ERR_INVALID;
+  const XDiv c = xdiv_consts(d);
+  for (size_t i = 0; i < n; i++) q[i] = xdiv_host(e[i], c);
+  return NET_OK;
+}
+
+int mibminet_test_xdiv_gpu(int32_t d, int64_t e0, int64_t count, int64_t* mismatches, int device) {
+  if (!mismatches || d == 0 || count < 0 || e0 < INT32_MIN || e0 + count - 1 > INT32_MAX) return NET_ERR_INVALID;
+  if (const int rc = check_device(device)) return rc;
+  DeviceGuard guard(device);
+  if (guard.err != hipSuccess) return hip_err(guard.err);
+  constexpr int GRID = 2048, THREADS = 256;
+  unsigned long long* dn = nullptr;
+  hipError_t e = hipMalloc((void**)&dn, sizeof(unsigned long long) * GRID * THREADS);
+  if (e != hipSuccess) return hip_err(e);
+  const XDiv c = xdiv_consts(d);
+  hipLaunchKernelGGL(k_xdiv_check, dim3(GRID), dim3(THREADS), 0, nullptr, d, c.m, c.xs, (long long)e0, (long long)count, dn);
+  e = hipGetLastError();
+  std::vector<unsigned long long> h((size_t)GRID * THREADS);
+  if (e == hipSuccess) e = hipMemcpy(h.data(), dn, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost);
+  (void)hipFree(dn);
+  if (e != hipSuccess) return hip_err(e);
+  int64_t n = 0;
+  for (unsigned long long v : h) n += (int64_t)v;
+  *mismatches = n;
+  return NET_OK;
+}
+
+int mibminet_test_pool_consts(int32_t off, int32_t layer, int32_t* thr, int32_t* offm) {
+  if (!thr || !offm || (layer != 2 && layer != 4)) return NET_ERR_INVALID;
+  pool_consts(off, layer == 2 ? (1 << 20) : (1 << 18), thr, offm);
+  return NET_OK;
+}
+
+int mibminet_test_image_digest(uint64_t* digest) {
+  if (!digest) return NET_ERR_INVALID;
+  Snapshot s = snapshot();
+  if (!s.host) return NET_ERR_NO_PARAMS;
+  uint64_t h = 1469598103934665603ull;  // FNV-1a over the image bytes
+  const Image& img = s.img[IMG_KERNELS];
+  const uint8_t* p = (const uint8_t*)img.data.get();
+  for (size_t i = 0; i < img.bytes; i++) h = (h ^ p[i]) * 1099511628211ull;
+  *digest = h;
+  return NET_OK;
+}
+
+int mibminet_test_image_copy(int which, void* buf, size_t cap, size_t* bytes) {
+  if (!bytes) return NET_ERR_INVALID;
+  *bytes = 0;
+  if (which != IMG_KERNELS && which != IMG_WINDOWS) return NET_ERR_INVALID;
+  Snapshot s = snapshot();
+  if (!s.host) return NET_ERR_NO_PARAMS;
+  const Image& img = s.img[which];
+  if (!img.data) return NET_ERR_UNSUPPORTED;
+  *bytes = img.bytes;
+  if (!buf) return NET_OK;
+  if (cap < img.bytes) return NET_ERR_INVALID;
+  std::memcpy(buf, img.data.get(), img.bytes);
+  return NET_OK;
+}
+
+int mibminet_test_folded_filters(int32_t* count) {
+  if (!count) return NET_ERR_INVALID;
+  Snapshot s = snapshot();
+  if (!s.host) return NET_ERR_NO_PARAMS;
+  *count = s.host->folded;
+  return NET_OK;
+}
+
+int mibminet_test_force_general(int on) {
+  g_force_general.store(on ? 1 : 0);
+  return NET_OK;
+}
+
+int mibminet_test_params_xr(void) {
+  Snapshot s = snapshot();
+  if (!s.host) return NET_ERR_NO_PARAMS;
+  return s.host->xr ? 1 : 0;
+}
+
+int mibminet_test_device_images(int device) {
+  if (device < 0 || device >= MAX_DEVICES) return NET_ERR_INVALID;
+  DeviceState& ds = g_devs[device];
+  std::lock_guard<std::mutex> lk(ds.mu);
+  return (int)ds.images.size();
+}
+
+}  // extern "C"

@@ -83,7 +83,7 @@ def test_reload_while_computing(gpu):
     """One thread alternates two parameter sets; two threads keep launching on their own streams.
     Each batch's logits must equal the oracle's for set 1 or for set 2 as a whole.  (The hazard
     this guards, a reload's upload overwriting the device copy under a kernel that is still
-    reading it at its start, has a window of microseconds: ensure_device closes it by
+    reading it at its start, has a window of microseconds: ensure_image (device_state.hpp) closes it by
     construction with a device synchronisation before the upload; this test pins the contract.)"""
     import torch
 

@@ -155,7 +155,7 @@ def test_extreme_full_batch(gpu):
                                        (64, 480, False, False), (19, 480, True, False), (38, 1125, False, False)])
 def test_folded_rail_sets_on_the_float_kernels(C, T, rb, cb, gpu):
     """Sets whose out-of-envelope filters are all constant load on the float kernels with those
-    filters folded (mibminet.hip, fold_constant_filters); the outputs equal the C oracle on the set
+    filters folded (params_host.hpp, fold_constant_filters); the outputs equal the C oracle on the set
     as given, batched (both layouts) and through the reference's single-trial and layer entries."""
     import torch
 

@@ -191,7 +191,7 @@ def test_pool_constants_keep_the_pooled_sum():
 
 
 def _fold(ps):
-    """Python restatement of the loader's constant-filter folding (mibminet.hip,
+    """Python restatement of the loader's constant-filter folding (params_host.hpp,
     fold_constant_filters): a filter whose clipped output is one value y over its whole reachable
     numerator range gets zero weights and offset/factor that reproduce y."""
     import copy
