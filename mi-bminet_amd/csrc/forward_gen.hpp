@@ -153,33 +153,53 @@ typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
 // 16 bytes at byte offset o of the view, from five aligned dwords: each dword lies wholly inside
 // or wholly outside num_records (which is a multiple of 4), so the range check zeroes no byte the
-// trial holds.  v_alignbyte_b32(hi, lo, s) = bytes s .. s + 3 of hi:lo.
-__device__ __forceinline__ v4i load16u(wg::Rsrc r, int o) {
-  const int o4 = o & ~3;
-  const unsigned s = (unsigned)(o & 3);
-  const v4u a = __builtin_amdgcn_raw_buffer_load_b128(r, o4, 0, 0);
-  const unsigned e = __builtin_amdgcn_raw_buffer_load_b32(r, o4 + 16, 0, 0);
+// trial holds.  v_alignbyte_b32(hi, lo, s) = bytes s .. s + 3 of hi:lo.  The offset is unsigned (the
+// builtin's operand is the same 32 bits, and the hardware compares it with num_records unsigned):
+// the arithmetic stays defined for the offsets just past 2^31 that the recording and epoch
+// fetches form (forward_win.hpp, forward_ep.hpp).
+__device__ __forceinline__ v4i load16u(wg::Rsrc r, unsigned o) {
+  const unsigned o4 = o & ~3u, s = o & 3u;
+  const v4u a = __builtin_amdgcn_raw_buffer_load_b128(r, (int)o4, 0, 0);
+  const unsigned e = __builtin_amdgcn_raw_buffer_load_b32(r, (int)(o4 + 16u), 0, 0);
   return (v4i){(int)__builtin_amdgcn_alignbyte(a[1], a[0], s), (int)__builtin_amdgcn_alignbyte(a[2], a[1], s),
                (int)__builtin_amdgcn_alignbyte(a[3], a[2], s), (int)__builtin_amdgcn_alignbyte(e, a[3], s)};
 }
 
-// The view of trial b: base = the trial's first byte rounded down to a dword, delta = the rest,
-// num_records = the trial's bytes from base rounded up to a dword (a dword holding a trial byte is
-// inside the page of that byte, so the rounding reads no unmapped memory).
+// 16 float32 samples at byte offset o (a multiple of 4) of the view -> 16 int8: the reference's
+// input quantisation (gen_input_header.py:66-76); the truncating convert lies in [-127, 127]
+__device__ __forceinline__ v4i load16f(wg::Rsrc r, unsigned o, float qs, float qy) {
+  v4i w;
+#pragma unroll
+  for (int m = 0; m < 4; m++) {
+    const v4u f = __builtin_amdgcn_raw_buffer_load_b128(r, (int)(o + 16u * m), 0, 0);
+    int q[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) q[i] = (int)wg::quantize1_f(__uint_as_float(f[i]), qs, qy);
+    w[m] = (int)pack4(q[0], q[1], q[2], q[3]);
+  }
+  return w;
+}
+
+// The view of `bytes` bytes from p: base = p rounded down to a dword, delta = the rest,
+// num_records = the bytes from base rounded up to a dword (a dword holding a byte of the span is
+// inside the page of that byte, so the rounding reads no unmapped memory).  Unsigned: delta +
+// bytes + 3 may pass 2^31 - 1 (a recording, forward_win.hpp).
 struct View {
   wg::Rsrc r;
   int delta;
 };
+__device__ __forceinline__ View make_view(const int8_t* p, unsigned bytes) {
+  const unsigned delta = (unsigned)((size_t)p & 3);
+  View v;
+  v.r = __builtin_amdgcn_make_buffer_rsrc((void*)(p - delta), (short)0, (int)((delta + bytes + 3u) & ~3u), 0x00020000);
+  v.delta = (int)delta;
+  return v;
+}
+// The view of trial b.
 template <int L>
 __device__ __forceinline__ View trial_view(const int8_t* x, long long b, int C, int T, int xstride) {
   const long long ct = (long long)C * T;
-  const int8_t* p = L == TM ? x + b * xstride : L == CT ? x + b * ct : x + 4 * b * ct;
-  const int delta = (int)((size_t)p & 3);
-  const int bytes = (int)((L == F32 ? 4 : 1) * ct);
-  View v;
-  v.r = __builtin_amdgcn_make_buffer_rsrc((void*)(p - delta), (short)0, (delta + bytes + 3) & ~3, 0x00020000);
-  v.delta = delta;
-  return v;
+  return make_view(L == TM ? x + b * xstride : L == CT ? x + b * ct : x + 4 * b * ct, (unsigned)((L == F32 ? 4 : 1) * ct));
 }
 
 // Time-major K groups: with C <= 32 channels 0..15 go to K group 0 and 16..31 to K group 2, and
@@ -190,31 +210,25 @@ __device__ __forceinline__ View trial_view(const int8_t* x, long long b, int C, 
 __host__ __device__ inline int l1_chunk(int g, int C) { return C <= 32 ? g >> 1 : g; }
 
 // The A fragment of layer-1 block blk (samples 16 blk .. +15), before staging: time-major, lane
-// (j, g) holds channels 16 c .. +15 (c = l1_chunk(g, C)) of sample 16 blk + j; channel-major, lane c holds samples
-// 16 blk .. +15 of channel c.  K-slots past C meet zero weights, so what those lanes read does not
+// (j, g) holds channels 16 c .. +15 (c = l1_chunk(g, C)) of sample 16 blk + j; channel-major,
+// lane c holds samples 16 blk .. +15 of channel c.  K-slots past C meet zero weights, so what those lanes read does not
 // matter: the loads are unconditional (no per-lane branch between one block's loads and the next
-// block's), and channel-major rows past C re-read row C - 1.
+// block's), and channel-major rows past C re-read row C - 1.  T: the row stride of the
+// channel-major layouts, the trial's length or a whole recording's (win::k_layer1_rec).  The byte
+// offsets are computed unsigned: the host admits recordings up to 2^31 - 1 bytes, so the offsets
+// of the partial last block (samples >= T, rows past the last) reach a little past 2^31 (below
+// 2^31 + 2^11).  The hardware compares the offset with num_records unsigned, so those loads return
+// zeros; unsigned, the arithmetic that gets there is defined too.
 template <int L>
 __device__ __forceinline__ v4i l1_fetch(const View& v, int blk, int C, int T, int lane, float qs, float qy) {
+  const unsigned uC = (unsigned)C, uT = (unsigned)T, ub = 16u * (unsigned)blk, d = (unsigned)v.delta;
   if constexpr (L == TM) {
-    const int j = lane & 15, g = lane >> 4;
-    return load16u(v.r, v.delta + (16 * blk + j) * C + 16 * l1_chunk(g, C));
+    const unsigned j = lane & 15, g = lane >> 4;
+    return load16u(v.r, d + (ub + j) * uC + 16u * (unsigned)l1_chunk((int)g, C));
   } else if constexpr (L == CT) {
-    return load16u(v.r, v.delta + min(lane, C - 1) * T + 16 * blk);
+    return load16u(v.r, d + (unsigned)min(lane, C - 1) * uT + ub);
   } else {
-    const int c = min(lane, C - 1);
-    v4i w;
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-      const v4u f = __builtin_amdgcn_raw_buffer_load_b128(v.r, 4 * (c * T + 16 * blk) + 16 * m, 0, 0);
-      // the reference's input quantisation (gen_input_header.py:66-76), wg::quantize1_f; the
-      // truncating convert lies in [-127, 127]
-      int q[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) q[i] = (int)wg::quantize1_f(__uint_as_float(f[i]), qs, qy);
-      w[m] = (int)pack4(q[0], q[1], q[2], q[3]);
-    }
-    return w;
+    return load16f(v.r, 4u * ((unsigned)min(lane, C - 1) * uT + ub), qs, qy);
   }
 }
 
@@ -268,8 +282,6 @@ __device__ __forceinline__ void stage_trial(const View& v, int8_t* raw, int chun
   for (int i = wave; i < chunks; i += NW) wg::dma_b128(v.r, 1024 * i + 16 * lane, 0, base + 1024 * i);
 }
 
-// Layer 1: the blocks first, first + nw, ... < end -> y1 rows (position 32 + t).  Loads of
-// U blocks are issued before their MFMAs.
 // Requant of one layer-1 output (acc = dot + offset, or its float-magic form): exact division
 // (XR) or fma(acc bits, r, c) = RN((dot + off) r), truncated (the host proves it equals C's
 // division on every reachable value).  Both clip to [LO, 127] (the upper bound and -128 by the
@@ -294,7 +306,35 @@ struct L1C {  // a lane's layer-1 constants (filter lane & 15)
   unsigned m;
   float r, c;
 };
+// layout L's: time-major fragments take the K order of l1_chunk, the others the natural one
+template <int L>
+__device__ __forceinline__ L1C l1_consts(const GenParams* __restrict__ gp, int lane) {
+  const int j = lane & 15;
+  return L1C{L == TM ? gp->l1_b[lane] : gp->l1_bn[lane], gp->l1_off[j], gp->l1_xs[j], gp->l1_m[j], gp->l1_r[j], gp->l1_c[j]};
+}
 
+// One layer-1 block: the fragment `raw` of samples 16 blk .. +15 (l1_fetch; transposed through
+// the wave's staging area stg unless time-major) -> bytes 16 blk .. +15 of the sixteen filters'
+// rows, `row` being that of the lane's filter lane & 15 (g = lane >> 4).  last: the block holds
+// samples >= lim, which are stored as zeros.
+template <int L, bool XR, bool CB>
+__device__ __forceinline__ void l1_block(v4i raw, int8_t* stg, const L1C& k, int blk, bool last, int lim, int8_t* row,
+                                         int g, int lane) {
+  const v4i a = L == TM ? raw : wg::stage_block<TrK>(raw, stg, lane);
+  const v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, k.wf, (v4i){k.off, k.off, k.off, k.off}, 0, 0, 0);
+  // lane column j = filter j, rows 4 g + r = samples 16 blk + 4 g + r
+  const int t0 = 16 * blk + 4 * g;
+  int y[4];
+#pragma unroll
+  for (int r = 0; r < 4; r++) y[r] = rq1<XR, CB>(acc[r], k.m, k.xs, k.r, k.c);
+  if (last) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) y[r] = t0 + r < lim ? y[r] : 0;
+  }
+  *(unsigned*)(row + t0) = sat4(y[0], y[1], y[2], y[3]);
+}
+
+// Layer 1: the blocks first, first + nw, ... < end -> y1 rows (position 32 + t).
 // ST: the trial is staged in LDS (sraw).  The U blocks' loads are all issued before the first MFMA
 // (slots past NB1 re-read the last block; their results are not stored).  U4: four blocks per
 // group, else two (float32: always two).
@@ -324,20 +364,8 @@ __device__ __forceinline__ void layer1(const GenParams* __restrict__ gp, const V
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const int blk = b0 + u * nw;
-      if (blk < end) {  // wave-uniform
-        const v4i a = L == TM ? raw[u] : wg::stage_block<TrK>(raw[u], stg, lane);
-        const v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, k.wf, (v4i){k.off, k.off, k.off, k.off}, 0, 0, 0);
-        // lane column j = filter j, rows 4 g + r = samples 16 blk + 4 g + r
-        const int t0 = 16 * blk + 4 * g;
-        int y[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) y[r] = rq1<XR, CB>(acc[r], k.m, k.xs, k.r, k.c);
-        if (blk == NB1 - 1) {  // the trial's last block: samples >= T are zero (the xcorr's pad)
-#pragma unroll
-          for (int r = 0; r < 4; r++) y[r] = t0 + r < T ? y[r] : 0;
-        }
-        *(unsigned*)(y1 + j * y1s + 32 + t0) = sat4(y[0], y[1], y[2], y[3]);
-      }
+      // (wave-uniform)  the trial's last block: samples >= T are zero (the xcorr's pad)
+      if (blk < end) l1_block<L, XR, CB>(raw[u], stg, k, blk, blk == NB1 - 1, T, y1 + j * y1s + 32, g, lane);
     }
   }
 }
@@ -571,16 +599,21 @@ __device__ __forceinline__ void layer5(const GenParams* __restrict__ gp, const i
   }
 }
 
-// Per-lane constants and the LDS initialisation shared by both kernels.
-__device__ __forceinline__ void setup(const GenParams* __restrict__ gp, int8_t* smem, const Carve& cv, L1C& k1,
-                                      L2C& k2, int tid, int wave, int lane) {
-  const int j = lane & 15;
-  k1.wf = gp->l1_b[lane];
-  k1.off = gp->l1_off[j];
-  k1.m = gp->l1_m[j];
-  k1.xs = gp->l1_xs[j];
-  k1.r = gp->l1_r[j];
-  k1.c = gp->l1_c[j];
+// The workgroup's LDS areas (carve_of; layout: its argument).
+struct Lds {
+  Carve cv;
+  SmallG* sg;
+  int8_t *y1, *y2, *y3, *y4;
+  int8_t* w5;  // the layer-5 weight rows, then the biases
+};
+__device__ __forceinline__ Lds lds_of(const GenParams* __restrict__ gp, int8_t* smem, int layout) {
+  const Carve cv = carve_of(gp->C, gp->T, gp->N, gp->T8, gp->T64A, gp->NB1, gp->MT, gp->NTT, layout);
+  return Lds{cv, (SmallG*)(smem + cv.sg), smem, smem + cv.y2, smem + cv.y3, smem + cv.y4, smem + cv.w5};
+}
+
+// The wave's layer-2 constants and the LDS initialisation shared by every kernel of the family.
+__device__ __forceinline__ void setup(const GenParams* __restrict__ gp, const Lds& m, L2C& k2, int tid, int wave,
+                                      int lane) {
 #pragma unroll
   for (int fi = 0; fi < 2; fi++) {
     const int f = 2 * wave + fi;
@@ -596,18 +629,26 @@ __device__ __forceinline__ void setup(const GenParams* __restrict__ gp, int8_t* 
     k2.c[fi] = gp->l2_c[f];
   }
   // zero pads of every row (positions past the data are never rewritten), then the small params
-  v4i* z = (v4i*)smem;
-  for (int i = tid; i < cv.sg / 16; i += NT) z[i] = (v4i){0, 0, 0, 0};
+  v4i* z = (v4i*)m.y1;
+  for (int i = tid; i < m.cv.sg / 16; i += NT) z[i] = (v4i){0, 0, 0, 0};
   const v4i* src = (const v4i*)&gp->sg;
-  v4i* dst = (v4i*)(smem + cv.sg);
+  v4i* dst = (v4i*)m.sg;
   for (int i = tid; i < (int)(sizeof(SmallG) / 16); i += NT) dst[i] = src[i];
   const int row5 = F2 * gp->T64A, rp = w5_row(gp->T64A) / 4;  // layer-5 weight rows, [N][rp dwords]
-  int* w5 = (int*)(smem + cv.w5);
+  int* w5 = (int*)m.w5;
   for (int i = tid; i < gp->N * rp; i += NT) {
     const int n = i / rp, d = i - n * rp;
     w5[i] = 4 * d < row5 ? ((const int*)gp->l5_w[n])[d] : 0;
   }
   for (int n = tid; n < gp->N; n += NT) w5[gp->N * rp + n] = gp->l5_b[n];
+}
+
+// Layers 4-5 of the trial whose layer-3 rows are in y3, on one wave: its logits -> out[N].
+template <bool RB, bool XR, bool CB>
+__device__ __forceinline__ void finish_trial(const GenParams* __restrict__ gp, const Lds& m, int8_t* out, int lane) {
+  layer4<RB, XR, CB>(gp, m.y3, m.y4, m.sg, lane, 0, 1);
+  wg::wave_sync_lds();
+  layer5<CB>(gp, m.y4, m.w5, out, 0, 1, lane);
 }
 
 // Fused forward over a batch of B trials (layout L), logits [B][N].
@@ -622,16 +663,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   int8_t* smem = (int8_t*)smem_v;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const Carve cv = carve_of(gp->C, gp->T, gp->N, gp->T8, gp->T64A, gp->NB1, gp->MT, gp->NTT, L);
-  L1C k1;
+  const Lds m = lds_of(gp, smem, L);
+  const Carve& cv = m.cv;
+  const L1C k1 = l1_consts<L>(gp, lane);
   L2C k2;
-  setup(gp, smem, cv, k1, k2, tid, wave, lane);
-  if constexpr (L != TM) k1.wf = gp->l1_bn[lane];  // channel-major fragments keep the natural K order
-  const SmallG* sg = (const SmallG*)(smem + cv.sg);
-  int8_t* y1 = smem;
-  int8_t* y2 = smem + cv.y2;
-  int8_t* y3 = smem + cv.y3;
-  int8_t* y4 = smem + cv.y4;
+  setup(gp, m, k2, tid, wave, lane);
   int8_t* stg = smem + cv.stg + 1024 * wave;
   // layer-1 groups of two blocks when two workgroups share the CU (the other one's waves cover the
   // latency; a wave's ~10 blocks then leave no slot re-reading the last block), of four at one
@@ -659,25 +695,27 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   int bprev = -1;
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
     const View v = trial_view<L>(x, b, C, T, xstride);
+    // layer-1 groups of two or of four blocks.  Captures by value: by reference the kernels came
+    // out up to about 60 instructions longer and two VGPRs wider ("One layer-1 block")
+    const auto l1 = [=](int first, int nw, int end) __attribute__((always_inline)) {
+      if (two_wg) layer1<L, ST, XR, CB, false>(gp, v, sraw, m.y1, cv.y1s, stg, k1, first, nw, end, lane, qs, qy);
+      else layer1<L, ST, XR, CB>(gp, v, sraw, m.y1, cv.y1s, stg, k1, first, nw, end, lane, qs, qy);
+    };
     MIB_STAMP(7)
     // priorities as in the compiled kernels (wg::PRIO_*): the last wave's layers 4-5 are the longest
     // dependency chain of the interval and issue first; layer 1 ahead of the other workgroup's 2-3
     if (wave < NW - 1) {
       __builtin_amdgcn_s_setprio(wg::PRIO_L1);
-      if (two_wg) layer1<L, ST, XR, CB, false>(gp, v, sraw, y1, cv.y1s, stg, k1, wave, NW - 1, NB1 - K7, lane, qs, qy);
-      else layer1<L, ST, XR, CB>(gp, v, sraw, y1, cv.y1s, stg, k1, wave, NW - 1, NB1 - K7, lane, qs, qy);
+      l1(wave, NW - 1, NB1 - K7);
     } else {
       if (bprev >= 0) {
         __builtin_amdgcn_s_setprio(wg::PRIO_L45);
-        layer4<RB, XR, CB>(gp, y3, y4, sg, lane, 0, 1);
-        wg::wave_sync_lds();
-        layer5<CB>(gp, y4, smem + cv.w5, out + (size_t)bprev * N, 0, 1, lane);
+        finish_trial<RB, XR, CB>(gp, m, out + (size_t)bprev * N, lane);
       }
       // then the trial's last K7 layer-1 blocks (host-balanced against layers 4-5)
       if (K7 > 0) {
         __builtin_amdgcn_s_setprio(wg::PRIO_L1);
-        if (two_wg) layer1<L, ST, XR, CB, false>(gp, v, sraw, y1, cv.y1s, stg, k1, NB1 - K7, 1, NB1, lane, qs, qy);
-        else layer1<L, ST, XR, CB>(gp, v, sraw, y1, cv.y1s, stg, k1, NB1 - K7, 1, NB1, lane, qs, qy);
+        l1(NB1 - K7, 1, NB1);
       }
     }
     __builtin_amdgcn_s_setprio(0);
@@ -686,11 +724,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     const int bn = b + (int)gridDim.x;
     if (ST && bn < B) stage_trial(trial_view<L>(x, bn, C, T, xstride), sraw, cv.chunks, wave, lane);
     MIB_STAMP(1)
-    layer2<RB, XR, CB>(gp, y1, cv.y1s, y2, cv.y2s, k2, wave, lane);
+    layer2<RB, XR, CB>(gp, m.y1, cv.y1s, m.y2, cv.y2s, k2, wave, lane);
     wg::wave_sync_lds();  // layer 3 of filter f reads only y2 row f, written by this wave
     MIB_STAMP(2)
     __builtin_amdgcn_s_setprio(wg::PRIO_L3);
-    layer3<XR, CB>(gp, sg, y2, cv.y2s, y3, wave, lane);
+    layer3<XR, CB>(gp, m.sg, m.y2, cv.y2s, m.y3, wave, lane);
     __builtin_amdgcn_s_setprio(0);
     MIB_STAMP(3)
     if (ST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's part of the next trial
@@ -698,11 +736,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     MIB_STAMP(4)
     bprev = b;
   }
-  if (wave == NW - 1 && bprev >= 0) {  // the last trial's layers 4-5
-    layer4<RB, XR, CB>(gp, y3, y4, sg, lane, 0, 1);
-    wg::wave_sync_lds();
-    layer5<CB>(gp, y4, smem + cv.w5, out + (size_t)bprev * N, 0, 1, lane);
-  }
+  // the last trial's layers 4-5
+  if (wave == NW - 1 && bprev >= 0) finish_trial<RB, XR, CB>(gp, m, out + (size_t)bprev * N, lane);
   MIB_STAMP_FLUSH(lane == 0, wave)
 }
 
@@ -716,60 +751,56 @@ __global__ __launch_bounds__(NT) void k_layer(const GenParams* __restrict__ gp, 
   int8_t* smem = (int8_t*)smem_v;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const Carve cv = carve_of(gp->C, gp->T, gp->N, gp->T8, gp->T64A, gp->NB1, gp->MT, gp->NTT, 3);
-  L1C k1;
+  const Lds m = lds_of(gp, smem, 3);
+  const Carve& cv = m.cv;
+  const L1C k1 = l1_consts<TM>(gp, lane);
   L2C k2;
-  setup(gp, smem, cv, k1, k2, tid, wave, lane);
-  const SmallG* sg = (const SmallG*)(smem + cv.sg);
-  int8_t* y1 = smem;
-  int8_t* y2 = smem + cv.y2;
-  int8_t* y3 = smem + cv.y3;
-  int8_t* y4 = smem + cv.y4;
+  setup(gp, m, k2, tid, wave, lane);
   const int C = gp->C, T = gp->T, T8 = gp->T8, T64 = gp->T64, T64A = gp->T64A;
   const int TA = (T + 3) & ~3, T8A = (T8 + 3) & ~3;
   __syncthreads();
   if (stage == 1) {  // [T][C] packed -> [F1][T_ALIGN]
     const View v = trial_view<TM>(in, 0, C, T, gp->xstride);
-    layer1<TM, false, XR, CB>(gp, v, nullptr, y1, cv.y1s, nullptr, k1, wave, NW, gp->NB1, lane, 0.0f, 0.0f);
+    layer1<TM, false, XR, CB>(gp, v, nullptr, m.y1, cv.y1s, nullptr, k1, wave, NW, gp->NB1, lane, 0.0f, 0.0f);
     __syncthreads();
     for (int i = tid; i < F2 * TA; i += NT) {
       const int f = i / TA, t = i - f * TA;
-      out[i] = t < T ? y1[f * cv.y1s + 32 + t] : 0;
+      out[i] = t < T ? m.y1[f * cv.y1s + 32 + t] : 0;
     }
   } else if (stage == 2) {  // [F1][T_ALIGN] -> [F2][T8_ALIGN]
     for (int i = tid; i < F2 * T; i += NT) {
       const int f = i / T, t = i - f * T;
-      y1[f * cv.y1s + 32 + t] = in[f * TA + t];
+      m.y1[f * cv.y1s + 32 + t] = in[f * TA + t];
     }
     __syncthreads();
-    layer2<RB, XR, CB>(gp, y1, cv.y1s, y2, cv.y2s, k2, wave, lane);
+    layer2<RB, XR, CB>(gp, m.y1, cv.y1s, m.y2, cv.y2s, k2, wave, lane);
     __syncthreads();
     for (int i = tid; i < F2 * T8A; i += NT) {
       const int f = i / T8A, u = i - f * T8A;
-      out[i] = u < T8 ? y2[f * cv.y2s + 8 + u] : 0;
+      out[i] = u < T8 ? m.y2[f * cv.y2s + 8 + u] : 0;
     }
   } else if (stage == 3) {  // [F2][T8_ALIGN] -> [F2][T8_ALIGN]
     for (int i = tid; i < F2 * T8; i += NT) {
       const int f = i / T8, u = i - f * T8;
-      y2[f * cv.y2s + 8 + u] = in[f * T8A + u];
+      m.y2[f * cv.y2s + 8 + u] = in[f * T8A + u];
     }
     __syncthreads();
-    layer3<XR, CB>(gp, sg, y2, cv.y2s, y3, wave, lane);
+    layer3<XR, CB>(gp, m.sg, m.y2, cv.y2s, m.y3, wave, lane);
     __syncthreads();
     for (int i = tid; i < F2 * T8A; i += NT) {
       const int f = i / T8A, u = i - f * T8A;
-      out[i] = u < T8 ? y3[16 * u + f] : 0;
+      out[i] = u < T8 ? m.y3[16 * u + f] : 0;
     }
   } else if (stage == 4) {  // [T8][F2] -> [F2][T64_ALIGN]
-    for (int i = tid; i < T8 * F2; i += NT) y3[i] = in[i];
+    for (int i = tid; i < T8 * F2; i += NT) m.y3[i] = in[i];
     __syncthreads();
-    layer4<RB, XR, CB>(gp, y3, y4, sg, lane, wave, NW);
+    layer4<RB, XR, CB>(gp, m.y3, m.y4, m.sg, lane, wave, NW);
     __syncthreads();
-    for (int i = tid; i < F2 * T64A; i += NT) out[i] = y4[i];
+    for (int i = tid; i < F2 * T64A; i += NT) out[i] = m.y4[i];
   } else if (stage == 5) {  // [F2][T64_ALIGN] -> [N] (the pad columns read as zero)
-    for (int i = tid; i < F2 * T64A; i += NT) y4[i] = (i % T64A) < T64 ? in[i] : 0;
+    for (int i = tid; i < F2 * T64A; i += NT) m.y4[i] = (i % T64A) < T64 ? in[i] : 0;
     __syncthreads();
-    layer5<CB>(gp, y4, smem + cv.w5, out, wave, NW, lane);  // class group w on wave w
+    layer5<CB>(gp, m.y4, m.w5, out, wave, NW, lane);  // class group w on wave w
   } else if (stage == 6) {  // flip [F2][T8_ALIGN] -> [T8][F2]
     for (int i = tid; i < F2 * T8A; i += NT) {
       const int u = i / F2, f = i - u * F2;

@@ -7,8 +7,8 @@ V = {
     "base": [],
     "nol1rd": [("if constexpr (ST) raw[u] = l1_fetch_lds<false>(src, blk);",
                 "if constexpr (ST) raw[u] = (v4i){blk, lane, C, T};")],
-    "nol1st": [("*(unsigned*)(y1 + j * y1s + 32 + t0) = sat4(y[0], y[1], y[2], y[3]);",
-                "if (y[0] == 12345) *(unsigned*)(y1 + j * y1s + 32 + t0) = sat4(y[0], y[1], y[2], y[3]);")],
+    "nol1st": [("*(unsigned*)(row + t0) = sat4(y[0], y[1], y[2], y[3]);",  # gen::l1_block
+                "if (y[0] == 12345) *(unsigned*)(row + t0) = sat4(y[0], y[1], y[2], y[3]);")],
     "nol2rd": [("bs[fi][s] = *(const v4i*)(y1 + (2 * wave + fi) * y1s + 1024 * mt + 32 * n + 16 * h + 32 * s);",
                 "bs[fi][s] = (v4i){mt, n, h, s};"),
                ("for (int s = 0; s < 2; s++) bt[fi][s] = *(const v4i*)(y1 + (2 * wave + fi) * y1s + p0 + 64 * s + 16 * g);",
