@@ -55,7 +55,6 @@ constexpr int LDS_WG_MAX = 160 * 1024 / 2;  // LDS per workgroup at two workgrou
 constexpr int PF_MAX = 9;             // layer-1 blocks per wave prefetched one trial ahead
 constexpr int PF_MAX_PLAIN = 3;       // plain BN: fewer, no spills (config B -5.4 %, C -13.6 %; 4, 5
                                       // measured slower with the LDS-DMA of the rest)
-constexpr int PF_MAX_PLAIN_CT = 2;
 static_assert(FPW == 2, "tail-tile and layer-3 mapping assume two filters per wave");
 // Wave priorities (s_setprio): the last wave's layers 4-5 are the longest dependency chain of the
 // layer-1 interval, so that wave issues first while on them; layer 1 (HBM fragments, next-trial
@@ -122,7 +121,7 @@ struct Cfg {
   // of which prefetched a trial ahead (the plain-BN and 22-channel exact-division builds hold more
   // per-lane state; the rest of their blocks go by LDMA below)
   // (float input: the first block's four 16-byte pieces; the others load one block ahead)
-  static constexpr int PF = FQ_ ? 4 : cmin(NBW, RB && !(XR_ && P == 2) ? PF_MAX : CT_ ? PF_MAX_PLAIN_CT : PF_MAX_PLAIN);
+  static constexpr int PF = FQ_ ? 4 : cmin(NBW, RB && !(XR_ && P == 2) ? PF_MAX : PF_MAX_PLAIN);
   // Channel-major int8, 22 channels, through LDS-DMA (layer1): each block's rows go from HBM straight
   // into an LDS ring with buffer_load_dwordx4 ... lds, a trial ahead, and the A fragments come back
   // with ds_read_b64_tr_b16: no VGPR round trip, no ds_write (RS ring slots, LDS carve below).  The
@@ -156,15 +155,19 @@ struct Cfg {
   static constexpr int XTRIAL = FQ ? 4 * C * T : CT ? C * T : align16(T * C);
   // Channel-major int8, 64 channels, either BN branch (RX): whole-row loads.  Wave w loads channel rows
   // w + 8 h + 16 m (h < 2, m < 4) in 512-byte phases (2 rows x 512 bytes per load, lane-contiguous,
-  // where single-block loads read 16 bytes from each of 64 rows), and the waves exchange them
+  // where a load per block reads 16 bytes from each of 64 rows), and the waves exchange them
   // through a 32 KB LDS image of one phase: [64 rows][512 bytes], read back with ds_read_b64_tr_b8
   // (rx_*, layer1).  Phase 0 of the next trial is stored before barrier B; each further phase
   // costs two barriers (the image consumed, the image complete).  Config C -19.6 %;
-  // the plain-BN build since round 5: C -23.0 %, 64x480 -11.0 %.  The float-input 64-channel build
-  // stages one block at a time (stage_block), double-buffered in two 1 KB areas per wave.
+  // the plain-BN build since round 5: C -23.0 %, 64x480 -11.0 %.
   static constexpr bool RX = CT_ && !FQ_ && P == 1 && C == 64 && SPL.cl == 0 && (C * T) % 4 == 0;
+  // Channel-major trials are float, 22-channel int8 (the ring) or 64-channel int8 (whole rows).  A
+  // block-at-a-time int8 path for other shapes existed until RX took the plain-BN build over.
+  static_assert(!CT_ || FQ_ || DMA || RX, "no layer-1 path for this channel-major int8 geometry");
   static constexpr int NPH = RX ? (16 * NB1 + 511) / 512 : 0;  // image phases of 512 samples
-  static constexpr int STG = RX ? 32768 / NWAVES : 2048;  // staging bytes per wave
+  // bytes per wave at OFF_STG: an eighth of the phase image (RX), or the float path's block image
+  // (stage_block: 1 KB, in a 2 KB area)
+  static constexpr int STG = RX ? 32768 / NWAVES : FQ ? 2048 : 0;
   static constexpr int NB3 = (T8 + 15) / 16;            // layer-3 column blocks of 16 outputs
   // layer 3: tile 1 = the first L3C blocks of both filters side by side (one 16x16x64 MFMA),
   // tile 2 = the L3R outputs past 128, four per column in register 0 only (layer3)
@@ -206,7 +209,7 @@ struct Cfg {
   static constexpr bool LDMA = !CT_ && (!RB_ || XR_) && P == 2 && NBW > PF;
   static constexpr int NLD = LDMA ? NBW - PF : 0;
 
-  static constexpr int LDS = OFF_STG + (DMA ? NWAVES * RS * 1024 : CT ? NWAVES * STG : NWAVES * NLD * 1024);
+  static constexpr int LDS = OFF_STG + NWAVES * (DMA ? RS * 1024 : LDMA ? NLD * 1024 : STG);
   static_assert(!LDMA || LDS <= LDS_WG_MAX, "two workgroups per CU");
   static_assert(!DMA || RS == NBW, "the DMA ring holds every layer-1 block of a wave");
   static_assert(!DMA || LDS <= LDS_WG_MAX, "two workgroups per CU");
@@ -414,8 +417,8 @@ __device__ __forceinline__ Rsrc trial_rsrc(const int8_t* xt, int trials_left, in
     // row segments running past T read the next row (samples >= T, whose outputs are masked).
     // Rows start at any byte, and the range check is per dword OF THE LOAD (tools/ct_probe.hip):
     // a dword straddling num_records reads as zeros.  So the view runs 3 bytes past the trial,
-    // into the next trial's bytes, except for the batch's last trial, whose straddling dword is
-    // completed by byte loads (ct_tail).
+    // into the next trial's bytes, except for the batch's last trial, whose straddling dword the
+    // ring path completes by byte loads (layer1).  Whole rows need none: C * T % 4 == 0 (Cfg::RX).
     // (float input: dword-aligned rows, so the view is exactly the trial)
     const int n = trials_left <= 0 ? 0 : (trials_left == 1 || K::FQ) ? K::XTRIAL : K::XTRIAL + 3;
     return __builtin_amdgcn_make_buffer_rsrc((void*)xt, (short)0, n, 0x00020000);
@@ -463,24 +466,6 @@ __device__ __forceinline__ v4i load_a(Rsrc r, int xoff, int i) {
   return (v4i)v;
 }
 
-// The batch's last trial, channel-major: the one dword of the view that holds the trial's last
-// byte(s) and straddles its end read as zeros (trial_rsrc); the lane holding it reloads those 1-3
-// bytes one at a time (byte loads are range-checked per byte).  Once per launch.
-template <class K>
-__device__ __forceinline__ v4i ct_tail(v4i a, Rsrc r, int o) {
-  constexpr int N = K::C * K::T;
-  if (o < N && N < o + 16 && ((N - o) & 3)) {
-    const int k0 = (N - o) & ~3;
-    unsigned w = 0;
-    for (int m = 0; o + k0 + m < N; m++)
-      w |= (unsigned)__builtin_amdgcn_raw_buffer_load_b8(r, o + k0 + m, 0, 0) << (8 * m);
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-      if (4 * q == k0) a[q] = (int)w;
-  }
-  return a;
-}
-
 // Channel-major staging (K::CT).  The hardware executes a wave's LDS accesses in order, so an A
 // read sees the stores before it and the next stores follow it; wave_sync_lds tells the compiler.
 __device__ __forceinline__ void wave_sync_lds() {
@@ -502,7 +487,6 @@ __device__ __forceinline__ void wave_sync_lds() {
 // 16 g + 8 .. 16 g + 15 (tools/tr8_probe.hip checks the form).  Physical row of K-slot
 // k = 16 g + 8 r + q is stg_pos(k) = 16 g + 8 (r ^ (g & 1)) + q: the two groups of a 32-lane half
 // then read different bank halves (conflict-free); stg_pos is its own inverse.
-// (stg_pos is defined above lane_xoff, whose DMA offsets use it)
 
 // byte offsets of lane (i, g)'s two transposed reads: lane i of a group supplies the address of
 // row q = i >> 1, bytes 8 p .. 8 p + 7 (p = i & 1) of its 8-row block
@@ -613,58 +597,93 @@ __device__ __forceinline__ v4i load_f(Rsrc r, int xoff, int i, int m) {
   return (v4i)__builtin_amdgcn_raw_buffer_load_b128(r, xoff + 64 * K::P * i + 16 * m, 0, 0);
 }
 
+// The layer-1 input area of the LDS carve (Cfg::OFF_STG), one use per path.
 // LDS slots of wave `wave` filled by LDS-DMA (K::DMA: the channel-major ring; K::LDMA: the plain
 // build's blocks past PF)
 template <class K>
 __device__ __forceinline__ int8_t* ring_base(int8_t* smem, int wave) {
   return smem + K::OFF_STG + wave * (K::DMA ? K::RS : K::NLD) * 1024;
 }
-
+// the wave's block image (K::FQ, stage_block)
 template <class K>
-__device__ __forceinline__ void prefetch_l1(Rsrc r, Regs<K>& R, int lane = 0, int wave = 0,
-                                            int8_t* smem = nullptr) {
-  int8_t* ring = (K::DMA || K::LDMA) ? ring_base<K>(smem, wave) : nullptr;
-  // laundered: otherwise xoff + 16 GS i is hoisted out of the trial loop into a register per slot
-  // instead of riding in the loads' immediate offsets
+__device__ __forceinline__ int8_t* stg_base(int8_t* smem, int wave) {
+  return smem + K::OFF_STG + wave * K::STG;
+}
+// the phase image all waves share (K::RX)
+template <class K>
+__device__ __forceinline__ int8_t* img_base(int8_t* smem) {
+  return smem + K::OFF_STG;
+}
+
+// ---- layer-1 requests ------------------------------------------------------------------------
+// One function per input path; it serves the workgroup's first trial (prefetch_l1) and, from the
+// path's layer 1, the next trial.
+// The lane offset, laundered: otherwise xoff + (block stride) i is hoisted out of the trial loop
+// into a register per slot instead of riding in the loads' immediate offsets.
+template <class K>
+__device__ __forceinline__ int xoff_now(const Regs<K>& R) {
   int xo = R.xoff;
   asm volatile("" : "+v"(xo));
-  if constexpr (K::DMA) {
-    // ring slots 0 .. RS - 1 by LDS-DMA (the first trial of a workgroup; layer1 refills each slot
-    // for the next trial).  The wait keeps a DMA write from racing an LDS access still queued.
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const unsigned rb = lds_addr(ring);
-    const int n = l1_count<K>(wave);  // slots past the wave's blocks stay unfilled (wave-uniform)
+  return xo;
+}
+
+// Ring slots 0 .. RS - 1 by LDS-DMA: the first trial of a workgroup (l1_ring refills each slot for
+// the next trial as it frees).  The wait keeps a DMA write from racing an LDS access still queued.
+template <class K>
+__device__ __forceinline__ void request_ring(Rsrc r, const Regs<K>& R, int wave, int8_t* smem) {
+  const int xo = xoff_now(R);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  const unsigned rb = lds_addr(ring_base<K>(smem, wave));
+  const int n = l1_count<K>(wave);  // slots past the wave's blocks stay unfilled (wave-uniform)
 #pragma unroll
-    for (int i = 0; i < K::RS; i++)
-      if (i < n) dma_b128(r, xo, 16 * K::P * i, rb + 1024 * i);
-    return;
-  }
-  if constexpr (K::FQ) {  // the first block's four pieces
+  for (int i = 0; i < K::RS; i++)
+    if (i < n) dma_b128(r, xo, 16 * K::P * i, rb + 1024 * i);
+}
+
+// Float input: the four pieces of the wave's first block in walking order.
+template <class K>
+__device__ __forceinline__ void request_float(Rsrc r, Regs<K>& R) {
+  const int xo = xoff_now(R);
 #pragma unroll
-    for (int m = 0; m < 4; m++) R.pf[m] = load_f<K>(r, xo, R.fq0, m);
-    return;
-  }
-  if constexpr (K::RX) {
-    int ln = lane;  // the row offset recomputed per trial (a register across the loop spills)
-    asm volatile("" : "+v"(ln));
-    const int xr = rx_lane_off<K>(ln, wave);
+  for (int m = 0; m < 4; m++) R.pf[m] = load_f<K>(r, xo, R.fq0, m);
+}
+
+// Whole rows: every phase of the wave's eight rows.
+template <class K>
+__device__ __forceinline__ void request_rows(Rsrc r, Regs<K>& R, int lane, int wave) {
+  int ln = lane;  // the row offset recomputed per trial (a register across the loop spills)
+  asm volatile("" : "+v"(ln));
+  const int xr = rx_lane_off<K>(ln, wave);
 #pragma unroll
-    for (int ph = 0; ph < K::NPH; ph++)
+  for (int ph = 0; ph < K::NPH; ph++)
 #pragma unroll
-      for (int m = 0; m < 4; m++)
-        R.pf[4 * ph + m] = (v4i)__builtin_amdgcn_raw_buffer_load_b128(r, xr, 16 * m * K::T + 512 * ph, 0);
-    return;
-  }
+    for (int m = 0; m < 4; m++)
+      R.pf[4 * ph + m] = (v4i)__builtin_amdgcn_raw_buffer_load_b128(r, xr, 16 * m * K::T + 512 * ph, 0);
+}
+
+// Time-major: the first PF blocks into VGPRs; K::LDMA: the rest into the wave's LDS slots.
+template <class K>
+__device__ __forceinline__ void request_tm(Rsrc r, Regs<K>& R, int wave, int8_t* smem) {
+  const int xo = xoff_now(R);
   if constexpr (K::LDMA) {
     // issued before the VGPR loads: the compiler's vmcnt waits for those then also cover these
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slots' reads of this trial have returned
-    const unsigned rb = lds_addr(ring);
+    const unsigned rb = lds_addr(ring_base<K>(smem, wave));
 #pragma unroll
     for (int i = 0; i < K::NLD; i++) dma_b128(r, xo + (K::PF + i) * 16 * K::GS, 0, rb + 1024 * i);
   }
 #pragma unroll
   for (int i = 0; i < K::PF; i++) R.pf[i] = load_a<K>(r, xo, i);
 }
+
+template <class K>
+__device__ __forceinline__ void prefetch_l1(Rsrc r, Regs<K>& R, int lane, int wave, int8_t* smem) {
+  if constexpr (K::FQ) request_float<K>(r, R);
+  else if constexpr (K::DMA) request_ring<K>(r, R, wave, smem);
+  else if constexpr (K::RX) request_rows<K>(r, R, lane, wave);
+  else request_tm<K>(r, R, wave, smem);
+}
+
 
 template <class K>
 __device__ __forceinline__ void setup(const DevParams* __restrict__ prm, int8_t* smem, Regs<K>& R,
@@ -726,8 +745,8 @@ __device__ __forceinline__ void setup(const DevParams* __restrict__ prm, int8_t*
   for (int i = tid; i < K::OFF_SP / 16; i += NTHREADS) z[i] = (v4i){0, 0, 0, 0};
   if constexpr (K::DMA) {
     // the wave's own ring slots (rows that no lane fills, C = 22: K-slots 44..63, stay zero either
-    // way); the wave's first fill waits for these stores (prefetch_l1)
-    v4i* rz = (v4i*)(smem + K::OFF_STG + wave * K::RS * 1024);
+    // way); the wave's first fill waits for these stores (request_ring)
+    v4i* rz = (v4i*)ring_base<K>(smem, wave);
     for (int i = lane; i < K::RS * 64; i += 64) rz[i] = (v4i){0, 0, 0, 0};
   }
 }
@@ -777,8 +796,6 @@ __device__ __forceinline__ void l1_block(v4i a, int blk, int8_t* smem_y1, const 
   }
 }
 
-// Layer 1: x[T][C] (HBM, via R.pf) -> y1 rows (LDS, position 32 + t).  Prefetches the next
-// trial's fragments (rnext) into R.pf once the current ones are consumed.
 // Float input (K::FQ): 4 float32 samples (raw bits) -> 4 int8 bytes, the reference's input
 // quantisation (gen_input_header.py:66-76, functional.py:308-334: x / s, clip to [-1, 1], * 254 / 2,
 // truncate; each step rounded in float32), the same function as quant::quantize_one<float>.  The
@@ -829,216 +846,183 @@ __global__ void k_quantize_flat(const float* __restrict__ x, int8_t* __restrict_
   }
 }
 
+// One block that may be the trial's last (samples >= T masked).  maybe_last is wave-uniform; where
+// a caller's unrolled loop passes a constant false, only the unmasked copy remains there.
 template <class K>
-__device__ __forceinline__ void layer1(Rsrc rcur, Rsrc rnext, int8_t* smem_y1, Regs<K>& R, int wave, int lane,
-                                       bool last_trial = false) {
-  if constexpr (K::FQ) {
-    // float32 rows: the lane's 16 samples of a block are 64 bytes (4 loads), quantised to the
-    // 16 int8 bytes the channel-major staging takes.  Block 0 is requested here (R.pf); block
-    // i + 1 is loaded while block i is quantised and computed.
-    const int n = l1_count<K>(wave);
-    int8_t* stg = smem_y1 - K::OFF_Y1 + K::OFF_STG + wave * K::STG;
-    prefetch_l1<K>(rcur, R);  // no trial-ahead request: the first block now
-    v4i cur[4] = {R.pf[0], R.pf[1], R.pf[2], R.pf[3]};
-    // odd waves walk their blocks backwards (slot n - 1 first), so that both sides of every wave
-    // border are read in the same phase of the trial (float input)
-    const bool back = wave & 1;
-    // (a branch-free copy for waves with all NBW blocks, as in the channel-major int8 paths,
-    // measured +2.7 % here: not kept)
+__device__ __forceinline__ void l1_block_at(bool maybe_last, v4i a, int blk, int8_t* y1, const Regs<K>& R, int lane) {
+  if (maybe_last && blk == K::NB1 - 1) l1_block<K, true>(a, blk, y1, R, lane);
+  else l1_block<K, false>(a, blk, y1, R, lane);
+}
+
+// Look-ahead walk over a wave's n <= NMAX blocks (n wave-uniform): block i + 1's fragment is
+// fetched before body(i, block i's fragment, maybe_last), the block's MFMAs and requant.  A wave
+// with all NMAX blocks runs them straight, with no wave-uniform branches between them (only the
+// last can be the trial's last block, a wave's blocks being contiguous); at every such branch the
+// compiler drains the LDS counter (lgkmcnt(0)), exposing the reads' latency.  (Reading the
+// fragments 2 or 3 blocks ahead measured slower: DESIGN.md §3.)
+template <int NMAX, class Fetch, class Body>
+__device__ __forceinline__ void walk_ahead(int n, Fetch fetch, Body body) {
+  auto blocks = [&](auto full) {
+    constexpr bool F = decltype(full)::value;
+    v4i nx;
+    if (F || 0 < n) nx = fetch(0);
 #pragma unroll
-    for (int i = 0; i < K::NBW; i++) {
-      if (i < n) {  // wave-uniform
-        const int blk = l1_blk<K>(wave, back ? n - 1 - i : i);
-        v4i nxt[4] = {cur[0], cur[1], cur[2], cur[3]};
-        if (i + 1 < n)
-#pragma unroll
-          for (int m = 0; m < 4; m++) nxt[m] = load_f<K>(rcur, R.xoff, back ? n - 2 - i : i + 1, m);
-        v4i raw;
-#pragma unroll
-        for (int m = 0; m < 4; m++) raw[m] = (int)quantize4(cur[m], R.qs, R.qy);
-        const v4i a = stage_block<K>(raw, stg, lane);
-        if (blk == K::NB1 - 1) {
-          l1_block<K, true>(a, blk, smem_y1, R, lane);
-        } else {
-          l1_block<K, false>(a, blk, smem_y1, R, lane);
-        }
-#pragma unroll
-        for (int m = 0; m < 4; m++) cur[m] = nxt[m];
+    for (int i = 0; i < NMAX; i++) {
+      if (F || i < n) {  // wave-uniform
+        const v4i a = nx;
+        if (F ? i + 1 < NMAX : i + 1 < n) nx = fetch(i + 1);
+        body(i, a, !F || i == NMAX - 1);
       }
     }
-    return;
-  }
-  if constexpr (K::DMA) {
-    // Channel-major through the LDS-DMA ring: slots 0 .. RS - 1 hold blocks 0 .. RS - 1, filled a
-    // trial ahead (the first trial by prefetch_l1; after that, slot i during the previous trial's
-    // layer 1, right after block i's MFMAs).  Block i + 1's fragment is read before block i's MFMAs
-    // and requant.
-    const int n = l1_count<K>(wave);
-    int8_t* ring = smem_y1 - K::OFF_Y1 + K::OFF_STG + wave * K::RS * 1024;
-    // this trial's fill has landed.  Issued after it on the last wave: the previous trial's logits
-    // store, which need not complete (a vmcnt(0) there waited for that store's write
-    // acknowledgement on the critical last wave: +1,200 cycles per trial)
-    static_assert(K::PFV == 0, "no VGPR loads behind the ring fill");
-    if (wave == NWAVES - 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (last_trial) {
-      // the batch's last trial: its view ends at its last byte, so the one dword straddling that
-      // end landed as zeros; the lane holding it patches the 1-3 real bytes in (byte loads and
-      // stores, once per launch)
-      constexpr int N = K::C * K::T;
-#pragma unroll
-      for (int i = 0; i < K::RS; i++) {
-        const int o = R.xoff + 16 * K::P * i;
-        if (i < n && l1_blk<K>(wave, i) == K::NB1 - 1 && o < N && N < o + 16 && ((N - o) & 3)) {
-          const int k0 = (N - o) & ~3;
-          for (int m = 0; o + k0 + m < N; m++)
-            ring[1024 * i + 16 * lane + k0 + m] = (int8_t)__builtin_amdgcn_raw_buffer_load_b8(rcur, o + k0 + m, 0, 0);
-        }
-      }
-      wave_sync_lds();
-    }
-    // FULL: the wave has all NBW blocks (config B: waves 0-6), so the blocks run straight, with no
-    // wave-uniform branches between them (only the last may be the trial's last block); at every
-    // such branch the compiler drains the LDS counter (lgkmcnt(0)), exposing the reads' latency.
-    // (Reading the fragments 2 or 3 blocks ahead measured slower: DESIGN.md §3.)
-    auto blocks = [&](auto full) {
-      constexpr bool F = decltype(full)::value;
-      v4i fr;
-      if (F || 0 < n) fr = staged_tr<K>(ring, lane);
-#pragma unroll
-      for (int i = 0; i < K::NBW; i++) {
-        if (F || i < n) {  // wave-uniform
-          const int blk = l1_blk<K>(wave, i);
-          const v4i a = fr;
-          if (F ? i + 1 < K::NBW : i + 1 < n) fr = staged_tr<K>(ring + 1024 * (i + 1), lane);
-          if ((!F || i == K::NBW - 1) && blk == K::NB1 - 1) {  // a wave's blocks are contiguous
-            l1_block<K, true>(a, blk, smem_y1, R, lane);
-          } else {
-            l1_block<K, false>(a, blk, smem_y1, R, lane);
-          }
-          // slot i's fragment is in registers (its MFMAs read it): refill the slot with the next
-          // trial's block i now, while the TA is idle, instead of all five fills after barrier A,
-          // where the waves' fills queue behind one another (same box: -2.5 %; before barrier B:
-          // +8.0 %)
-          int xo = R.xoff;
-          asm volatile("" : "+v"(xo));
-          dma_b128(rnext, xo, 16 * K::P * i, lds_addr(ring) + 1024 * i);
-        }
-      }
-    };
-    if (n == K::NBW) blocks(BoolC<true>{});
-    else blocks(BoolC<false>{});
-    return;
-  }
-  constexpr int NX = K::NBW - K::PF;  // blocks not prefetched: load now (or from the LDS slots), consumed last
-  v4i xa[NX > 0 ? NX : 1];
-  if constexpr (K::LDMA) {
-    // the slots were filled before this trial's VGPR prefetch was issued: once all but the last PF
-    // vector-memory operations are done, so are the fills (in-order completion)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K::PF) : "memory");
-    const int8_t* ring = smem_y1 - K::OFF_Y1 + K::OFF_STG + wave * K::NLD * 1024;
-#pragma unroll
-    for (int i = 0; i < NX; i++) xa[i] = *(const v4i*)(ring + 1024 * i + 16 * lane);
-  } else {
-#pragma unroll
-    for (int i = 0; i < NX; i++) xa[i] = load_a<K>(rcur, R.xoff, K::PF + i);
-  }
+  };
+  if (n == NMAX) blocks(BoolC<true>{});
+  else blocks(BoolC<false>{});
+}
+
+// Float input: the lane's 16 samples of a block are 64 bytes (4 loads), quantised to the 16 int8
+// bytes the channel-major staging takes.  The first block is requested here, with no trial-ahead
+// request; block i + 1 is loaded while block i is quantised and computed.  The walk is its own:
+// it loads ahead, not reads, and a branch-free copy for waves with all NBW blocks measured +2.7 %.
+template <class K>
+__device__ __forceinline__ void l1_float(Rsrc rcur, int8_t* smem, Regs<K>& R, int wave, int lane) {
   const int n = l1_count<K>(wave);
-  int8_t* stg = smem_y1 - K::OFF_Y1 + K::OFF_STG + wave * K::STG;  // channel-major staging
-  if constexpr (K::RX) {
-    // whole-row exchange: phase 0 of this trial was stored before the previous trial's barrier B
-    // (k_forward); each further phase: barrier (the image consumed), store, barrier (complete).
-    // Waves 0-6 split each phase's blocks; the last wave (layers 4-5) has none.
-    int8_t* img = smem_y1 - K::OFF_Y1 + K::OFF_STG;
-    static_assert(K::NPH >= 1 && K::NPH <= 2, "one or two image phases (T <= 1024)");
-    auto phase = [&](auto PH) {
-      constexpr int ph = decltype(PH)::value;
-      if constexpr (ph > 0) {
-        __syncthreads();
-        rx_store<K>(R, ph, img, lane, wave);
-        __syncthreads();
-      }
-      constexpr int NBP = cmin(32, K::NB1 - 32 * ph), BASE = NBP / (NWAVES - 1), REM = NBP % (NWAVES - 1);
-      constexpr int MAXP = BASE + (REM ? 1 : 0);
-      const int cnt = wave < NWAVES - 1 ? BASE + (wave < REM) : 0;
-      const int lo = wave * BASE + min(wave, REM);
-      auto frag = [&](int j) {
-        int ln = lane;  // read offsets recomputed per block (hoisted, they hold 2 MAXP registers)
-        asm volatile("" : "+v"(ln));
-        return rx_frag(img, ln, lo + j);
-      };
-      // FULL: waves with MAXP blocks in this phase run them without branches
-      auto blocks = [&](auto full) {
-        constexpr bool F = decltype(full)::value;
-        v4i an = frag(0);
-#pragma unroll
-        for (int j = 0; j < MAXP; j++) {
-          if (F || j < cnt) {  // wave-uniform
-            const int blk = 32 * ph + lo + j;
-            const v4i a = an;
-            if (F ? j + 1 < MAXP : j + 1 < cnt) an = frag(j + 1);
-            if ((!F || j == MAXP - 1) && blk == K::NB1 - 1) l1_block<K, true>(a, blk, smem_y1, R, lane);
-            else l1_block<K, false>(a, blk, smem_y1, R, lane);
-          }
-        }
-      };
-      if (cnt > 0) {
-        if (cnt == MAXP) blocks(BoolC<true>{});
-        else blocks(BoolC<false>{});
-      }
-    };
-    phase(IntC<0>{});
-    if constexpr (K::NPH > 1) phase(IntC<1>{});
-    // (issued after barrier A instead: C -0.3 %, 64x480 +1.9 %; the image store before barrier B
-    // then waits on loads with less lead)
-    prefetch_l1<K>(rnext, R, lane, wave);
-    return;
-  }
-  if constexpr (K::CT) {
-    // single-block staging (64 channels, plain BN): block i + 1 is staged (store + transposed
-    // reads) before block i's MFMAs and requant, so the LDS round trip of the staging overlaps the
-    // previous block's work (two staging areas)
-    auto raw = [&](int i) -> v4i {
-      v4i a = (i < K::PF) ? R.pf[i < K::PF ? i : 0] : xa[i >= K::PF ? i - K::PF : 0];
-      if (last_trial && l1_blk<K>(wave, i) == K::NB1 - 1) a = ct_tail<K>(a, rcur, R.xoff + 16 * K::P * i);
-      return a;
-    };
-    // FULL: waves with all NBW blocks run them without wave-uniform branches, as in the DMA path
-    auto blocks = [&](auto full) {
-      constexpr bool F = decltype(full)::value;
-      v4i an = stage_block<K>(raw(0), stg, lane);
-#pragma unroll
-      for (int i = 0; i < K::NBW; i++) {
-        if (F || i < n) {  // wave-uniform
-          const int blk = l1_blk<K>(wave, i);
-          const v4i a = an;
-          if (F ? i + 1 < K::NBW : i + 1 < n) an = stage_block<K>(raw(i + 1), stg + 1024 * ((i + 1) & 1), lane);
-          if ((!F || i == K::NBW - 1) && blk == K::NB1 - 1) {  // a wave's blocks are contiguous
-            l1_block<K, true>(a, blk, smem_y1, R, lane);
-          } else {
-            l1_block<K, false>(a, blk, smem_y1, R, lane);
-          }
-        }
-      }
-    };
-    if (n == K::NBW) blocks(BoolC<true>{});
-    else blocks(BoolC<false>{});
-    prefetch_l1<K>(rnext, R);
-    return;
-  }
+  int8_t* stg = stg_base<K>(smem, wave);
+  request_float<K>(rcur, R);
+  v4i cur[4] = {R.pf[0], R.pf[1], R.pf[2], R.pf[3]};
+  // odd waves walk their blocks backwards (slot n - 1 first), so that both sides of every wave
+  // border are read in the same phase of the trial (float input)
+  const bool back = wave & 1;
 #pragma unroll
   for (int i = 0; i < K::NBW; i++) {
     if (i < n) {  // wave-uniform
-      const int blk = l1_blk<K>(wave, i);
-      const v4i a = (i < K::PF) ? R.pf[i < K::PF ? i : 0] : xa[i >= K::PF ? i - K::PF : 0];
-      if (blk == K::NB1 - 1) {  // the trial's last block: samples >= T are masked
-        l1_block<K, true>(a, blk, smem_y1, R, lane);
-      } else {
-        l1_block<K, false>(a, blk, smem_y1, R, lane);
-      }
+      const int blk = l1_blk<K>(wave, back ? n - 1 - i : i);
+      v4i nxt[4] = {cur[0], cur[1], cur[2], cur[3]};
+      if (i + 1 < n)
+#pragma unroll
+        for (int m = 0; m < 4; m++) nxt[m] = load_f<K>(rcur, R.xoff, back ? n - 2 - i : i + 1, m);
+      v4i raw;
+#pragma unroll
+      for (int m = 0; m < 4; m++) raw[m] = (int)quantize4(cur[m], R.qs, R.qy);
+      l1_block_at<K>(true, stage_block<K>(raw, stg, lane), blk, smem + K::OFF_Y1, R, lane);
+#pragma unroll
+      for (int m = 0; m < 4; m++) cur[m] = nxt[m];
     }
   }
-  prefetch_l1<K>(rnext, R, lane, wave, smem_y1 - K::OFF_Y1);
+}
+
+// Channel-major through the LDS-DMA ring: slots 0 .. RS - 1 hold blocks 0 .. RS - 1, filled a
+// trial ahead (the first trial by request_ring; after that, slot i during the previous trial's
+// layer 1, right after block i's MFMAs).
+template <class K>
+__device__ __forceinline__ void l1_ring(Rsrc rcur, Rsrc rnext, int8_t* smem, const Regs<K>& R, int wave, int lane,
+                                        bool last_trial) {
+  const int n = l1_count<K>(wave);
+  int8_t* ring = ring_base<K>(smem, wave);
+  // this trial's fill has landed.  Issued after it on the last wave: the previous trial's logits
+  // store, which need not complete (a vmcnt(0) there waited for that store's write
+  // acknowledgement on the critical last wave: +1,200 cycles per trial)
+  static_assert(K::PFV == 0, "no VGPR loads behind the ring fill");
+  if (wave == NWAVES - 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (last_trial) {
+    // the batch's last trial: its view ends at its last byte, so the one dword straddling that
+    // end landed as zeros; the lane holding it patches the 1-3 real bytes in (byte loads and
+    // stores, once per launch)
+    constexpr int N = K::C * K::T;
+#pragma unroll
+    for (int i = 0; i < K::RS; i++) {
+      const int o = R.xoff + 16 * K::P * i;
+      if (i < n && l1_blk<K>(wave, i) == K::NB1 - 1 && o < N && N < o + 16 && ((N - o) & 3)) {
+        const int k0 = (N - o) & ~3;
+        for (int m = 0; o + k0 + m < N; m++)
+          ring[1024 * i + 16 * lane + k0 + m] = (int8_t)__builtin_amdgcn_raw_buffer_load_b8(rcur, o + k0 + m, 0, 0);
+      }
+    }
+    wave_sync_lds();
+  }
+  walk_ahead<K::NBW>(
+      n, [=](int i) { return staged_tr<K>(ring + 1024 * i, lane); },
+      [=, &R](int i, v4i a, bool maybe_last) {
+        l1_block_at<K>(maybe_last, a, l1_blk<K>(wave, i), smem + K::OFF_Y1, R, lane);
+        // slot i's fragment is in registers (its MFMAs read it): refill the slot with the next
+        // trial's block i now, while the TA is idle, instead of all five fills after barrier A,
+        // where the waves' fills queue behind one another (same box: -2.5 %; before barrier B:
+        // +8.0 %)
+        dma_b128(rnext, xoff_now(R), 16 * K::P * i, lds_addr(ring) + 1024 * i);
+      });
+}
+
+// Whole-row exchange: phase 0 of this trial was stored before the previous trial's barrier B
+// (k_forward); each further phase: barrier (the image consumed), store, barrier (complete).
+// Waves 0-6 split each phase's blocks; the last wave (layers 4-5) has none.
+template <class K>
+__device__ __forceinline__ void l1_rows(Rsrc rnext, int8_t* smem, Regs<K>& R, int wave, int lane) {
+  int8_t* img = img_base<K>(smem);
+  static_assert(K::NPH >= 1 && K::NPH <= 2, "one or two image phases (T <= 1024)");
+  auto phase = [&](auto PH) {
+    constexpr int ph = decltype(PH)::value;
+    if constexpr (ph > 0) {
+      __syncthreads();
+      rx_store<K>(R, ph, img, lane, wave);
+      __syncthreads();
+    }
+    constexpr int NBP = cmin(32, K::NB1 - 32 * ph), BASE = NBP / (NWAVES - 1), REM = NBP % (NWAVES - 1);
+    const int cnt = wave < NWAVES - 1 ? BASE + (wave < REM) : 0;
+    const int lo = wave * BASE + min(wave, REM);
+    walk_ahead<BASE + (REM ? 1 : 0)>(
+        cnt,
+        [=](int j) {
+          int ln = lane;  // read offsets recomputed per block (hoisted, they hold 2 registers each)
+          asm volatile("" : "+v"(ln));
+          return rx_frag(img, ln, lo + j);
+        },
+        [=, &R](int j, v4i a, bool maybe_last) {
+          l1_block_at<K>(maybe_last, a, 32 * ph + lo + j, smem + K::OFF_Y1, R, lane);
+        });
+  };
+  phase(IntC<0>{});
+  if constexpr (K::NPH > 1) phase(IntC<1>{});
+  // (issued after barrier A instead: C -0.3 %, 64x480 +1.9 %; the image store before barrier B
+  // then waits on loads with less lead)
+  request_rows<K>(rnext, R, lane, wave);
+}
+
+// Layer 1: the trial behind rcur -> y1 rows (LDS, position 32 + t), and the request for the trial
+// behind rnext once the current fragments are consumed.  last_trial: the batch's last trial.
+// The channel-major paths are the functions above.  The time-major path is the rest of this one:
+// as a function of its own it compiled differently for 64 x 480 ("One layer-1 path
+// per input kind").  Its first PF blocks wait in R.pf since the previous trial; the others are
+// loaded now or (K::LDMA) come from the wave's LDS slots, and are consumed last.
+template <class K>
+__device__ __forceinline__ void layer1(Rsrc rcur, Rsrc rnext, int8_t* smem, Regs<K>& R, int wave, int lane,
+                                       bool last_trial) {
+  if constexpr (K::FQ) l1_float<K>(rcur, smem, R, wave, lane);
+  else if constexpr (K::DMA) l1_ring<K>(rcur, rnext, smem, R, wave, lane, last_trial);
+  else if constexpr (K::RX) l1_rows<K>(rnext, smem, R, wave, lane);
+  else {
+    constexpr int NX = K::NBW - K::PF;
+    v4i xa[NX > 0 ? NX : 1];
+    if constexpr (K::LDMA) {
+      // the slots were filled before this trial's VGPR prefetch was issued: once all but the last PF
+      // vector-memory operations are done, so are the fills (in-order completion)
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K::PF) : "memory");
+      const int8_t* slots = ring_base<K>(smem, wave);
+#pragma unroll
+      for (int i = 0; i < NX; i++) xa[i] = *(const v4i*)(slots + 1024 * i + 16 * lane);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NX; i++) xa[i] = load_a<K>(rcur, R.xoff, K::PF + i);
+    }
+    const int n = l1_count<K>(wave);
+#pragma unroll
+    for (int i = 0; i < K::NBW; i++) {
+      if (i < n) {  // wave-uniform
+        const v4i a = (i < K::PF) ? R.pf[i < K::PF ? i : 0] : xa[i >= K::PF ? i - K::PF : 0];
+        l1_block_at<K>(true, a, l1_blk<K>(wave, i), smem + K::OFF_Y1, R, lane);
+      }
+    }
+    request_tm<K>(rnext, R, wave, smem);
+  }
 }
 
 // ---- layer 2 ---------------------------------------------------------------------------------
@@ -1400,7 +1384,7 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(WPE, W
   // The first trial's fragments land before its layer 1 starts, as in k_layer (where loads still
   // in flight at layer 1 gave a rare wrong layer-1 row).  Once per workgroup.
   __builtin_amdgcn_s_waitcnt(0);
-  if constexpr (K::RX) rx_store<K>(R, 0, smem + K::OFF_STG, lane, wave);  // the first trial's phase 0
+  if constexpr (K::RX) rx_store<K>(R, 0, img_base<K>(smem), lane, wave);  // the first trial's phase 0
   __syncthreads();
   MIB_STAMP_INIT
   MIB_CLOCK_INIT
@@ -1419,21 +1403,17 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(WPE, W
     asm volatile("" : "+v"(ln));
     MIB_STAMP(7)
     __builtin_amdgcn_s_setprio(PRIO_L1);
-    layer1<K>(rc, rn, smem + K::OFF_Y1, R, wave, lane, MIB_TRIALS_LEFT(b) == 1);
+    layer1<K>(rc, rn, smem, R, wave, lane, MIB_TRIALS_LEFT(b) == 1);
     __builtin_amdgcn_s_setprio(0);
     MIB_STAMP(0)
     // the lane table is read before barrier A, so its LDS latency hides in the barrier wait
     // instead of delaying layer 2's first loads (same-box A/B -1.8 %)
     const LaneTab T = ((const LaneTab*)(smem + K::OFF_LT))[ln];
     MIB_LOOP_BARRIER();  // A
-    // DMA ring: the next trial's fill, off the layer-1 interval (-0.8 % same box); the ring's
-    // reads all returned before the barrier
     MIB_STAMP(1)
     if constexpr (!DIAG_NOL2) layer2<K>(smem + K::OFF_Y1, smem + K::OFF_Y2, sp, R, T, wave, ln);
     // layer 3 of filter f reads only y2 row f, which this wave wrote
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync_lds();
     MIB_STAMP(2)
     // layer 3 ends the barrier-B interval: at priority 1 a wave's layer 3 wins the arbitration
     // against the other waves' layer 2 (same-box A/B -1.2 ... -1.6 %; 2: -1.0 %; from the layer-2
@@ -1443,7 +1423,7 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(WPE, W
     __builtin_amdgcn_s_setprio(0);
     // whole-row exchange: the next trial's phase 0 into the image (its previous contents were read
     // before barrier A), so that barrier B also completes it
-    if constexpr (K::RX) rx_store<K>(R, 0, smem + K::OFF_STG, lane, wave);
+    if constexpr (K::RX) rx_store<K>(R, 0, img_base<K>(smem), lane, wave);
     MIB_STAMP(3)
     MIB_LOOP_BARRIER();  // B
     MIB_STAMP(4)
@@ -1496,7 +1476,7 @@ __global__ __launch_bounds__(NTHREADS) void k_layer(const DevParams* __restrict_
     // batched kernel, whose fragments are loaded a whole trial ahead, showed none in 39 M trials).
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
-    layer1<K>(rin, rin, y1, R, wave, lane);
+    layer1<K>(rin, rin, smem, R, wave, lane, false);
     __syncthreads();
     for (int i = tid; i < F2 * T_AL; i += NTHREADS) {
       const int f = i / T_AL, t = i - f * T_AL;
