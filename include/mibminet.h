@@ -249,6 +249,47 @@ int net_model_compute_windows(const int8_t* x, int layout, size_t L, size_t hop,
 int net_model_compute_windows_f32(const float* x, size_t L, size_t hop, float scale, int8_t* y, void* ws,
                                   size_t ws_bytes, int device, void* stream);
 
+/* ---- windows at given onsets: dense irregular windows, many recordings in one call -----------
+ * The same two kernels with the window starts read from a device list: window i covers samples
+ * onsets[i] .. onsets[i] + T - 1 of the recording and is valid iff 0 <= onsets[i] <= L - T.
+ * Layer 1 still runs once per sample of the whole recording, so overlapping crops around markers,
+ * irregular hops, and the sliding windows of several recordings laid end to end along time (no
+ * window crossing a boundary: net_windows_multi_onsets) share it exactly as the regular windows
+ * do: ws[f][t] does not depend on which recording sample t belongs to.  Prefer
+ * net_model_compute_epochs for sparse onsets (W*T << L: layer 1 here covers all L samples), channel
+ * subsets and strided sources ("Windows at given onsets").
+ * x, layout, L, ws, ws_bytes, scale, device and stream are those of net_model_compute_windows
+ * [_f32], and ws holds the same after the call.  onsets (W int64, 8-byte aligned, duplicates and
+ * any order allowed), y ([W][N] int8, 4-byte aligned) and n_bad (one int32, 4-byte aligned, or
+ * NULL; the caller zeroes it) are DEVICE pointers.  Logit row i of a valid onset is byte-identical
+ * to what net_model_compute_batch_ct returns for the trial x[:, onsets[i] : onsets[i] + T] (the
+ * float entry quantises first, as net_quantize_input_f32 does).  The kernel checks the onsets:
+ * from an invalid one no address is formed, its row is written as N zeros, and *n_bad (if
+ * non-NULL) is incremented once.  Two kernels are enqueued on `stream`, no host sync, no
+ * allocation: capturable into a HIP graph after one eager call has uploaded the parameters.
+ * Checks, all before any device call: NET_ERR_NO_PARAMS first; then NET_ERR_INVALID for a layout
+ * other than 0 or 1, a null x, y, onsets or ws with W > 0, a misaligned y, n_bad, onsets or float
+ * x, a ws that is misaligned or too small (for any W), W > 0 with L < T, W > INT32_MAX - 65,535,
+ * L * max(16, C * sizeof(element)) >= 2^31 and a bad device; the float scale's domain as in
+ * net_model_compute_windows_f32; NET_ERR_UNSUPPORTED for a network outside the general kernels'
+ * family.  W == 0 returns NET_OK and touches nothing, the workspace included. */
+int net_model_compute_windows_at(const int8_t* x, int layout, size_t L, const int64_t* onsets, size_t W,
+                                 int8_t* y, int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream);
+int net_model_compute_windows_at_f32(const float* x, size_t L, const int64_t* onsets, size_t W, float scale,
+                                     int8_t* y, int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream);
+
+/* Host only: the onset list of the sliding windows of R recordings laid end to end along time.
+ * Recording r has lengths[r] samples and starts at sample s_r = lengths[0] + .. + lengths[r - 1];
+ * it contributes the onsets s_r + k*hop, k < net_windows_count(lengths[r], hop), in order (none
+ * if it is shorter than T).  Both return the total W.  net_windows_multi_onsets fills onsets (a
+ * HOST array) if it is non-NULL and cap >= W, and first (HOST, R + 1 entries) if it is non-NULL:
+ * first[r] = the index of recording r's first window, first[R] = W.  Both return 0 and write
+ * nothing when no set is loaded, hop == 0, or the lengths' sum overflows int64.  The list depends
+ * on the geometry alone: copy it to the device once and reuse it. */
+size_t net_windows_multi_count(const size_t* lengths, size_t R, size_t hop);
+size_t net_windows_multi_onsets(const size_t* lengths, size_t R, size_t hop, int64_t* onsets, size_t cap,
+                                size_t* first);
+
 /* ---- epochs from a wider array: channel map, row stride and onsets --------------------------
  * The source x is a flat DEVICE array of n_elems elements; epoch e, network channel c, sample t is
  * element onsets[e] + channels[c]*row_stride + t.  One formula covers a recording [R][L] with cue

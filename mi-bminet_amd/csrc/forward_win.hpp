@@ -10,7 +10,10 @@
 //   k_forward_y1   gen::k_forward with its layer-1 phase replaced by a copy of the window's
 //                  sixteen workspace rows (T bytes each, from byte w hop) into the LDS y1 rows;
 //                  layers 2-5, the persistent loop and its two barriers are gen::'s own.
-// Both read a gen::GenParams image (every geometry, the compiled ones included) and are built
+//   k_forward_y1_at  the same with each window's first sample read from a device list and
+//                  range-checked (net_model_compute_windows_at): irregular and overlapping
+//                  windows, and the windows of many recordings laid end to end.
+// All read a gen::GenParams image (every geometry, the compiled ones included) and are built
 // from the run-time-dimension family (forward_gen.hpp); the compiled wg:: kernels are untouched.
 #pragma once
 #include "forward_gen.hpp"
@@ -140,6 +143,68 @@ __global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
     __syncthreads();  // B: layer 4 reads every filter's layer-3 rows
     MIB_STAMP(4)
     wprev = w;
+  }
+  MIB_STAMP_FLUSH(lane == 0, wave)
+}
+
+// The same over W windows at caller-given sample onsets (net_model_compute_windows_at): window w
+// covers samples onsets[w] .. onsets[w] + T - 1 of the workspace rows, in any order, duplicates
+// allowed.  last = Lr - T, the largest valid onset.  An onset outside [0, last] forms no address:
+// its rows are not copied (layers 2-3 run on whatever the y1 rows hold and their result is
+// dropped), its logit row is written as zeros and *n_bad (if non-null) counts it, as
+// ep::k_forward_ep does; the previous window and its validity travel in one register.
+template <bool RB, bool XR, bool CB>
+__global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_forward_y1_at(
+    const gen::GenParams* __restrict__ gp, const int8_t* __restrict__ ws, const long long* __restrict__ onsets,
+    int8_t* __restrict__ out, int* __restrict__ n_bad, int W, long long last, int rs) {
+  using namespace gen;
+  extern __shared__ v4i smem_v[];
+  int8_t* smem = (int8_t*)smem_v;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const Lds m = lds_of(gp, smem, 3);
+  const Carve& cv = m.cv;
+  L2C k2;
+  setup(gp, m, k2, tid, wave, lane);
+  const int T = gp->T, N = gp->N, NB1 = gp->NB1;
+  __syncthreads();
+  // (phase stamps as k_forward_y1)
+  MIB_STAMP_INIT
+  // the previous window and whether its onset was valid: w valid, -2 - w invalid, -1 none
+  int wprev = -1;
+  for (int w = blockIdx.x;; w += gridDim.x) {
+    const bool more = w < W;  // uniform over the workgroup
+    MIB_STAMP(7)
+    const long long on = more ? onsets[w] : 0;  // (wave-uniform: one scalar load)
+    const bool valid = (unsigned long long)on <= (unsigned long long)last;  // last >= 0: negative onsets fail too
+    if (wave < NW - 1) {
+      if (more && valid) copy_rows(window_view(ws, on, 1, T, rs), m.y1, cv.y1s, T, NB1, rs, tid, NT - 64);
+    } else if (wprev != -1) {
+      const bool vprev = wprev >= 0;
+      int8_t* o = out + (size_t)(vprev ? wprev : -2 - wprev) * N;
+      if (vprev) {
+        __builtin_amdgcn_s_setprio(wg::PRIO_L45);
+        finish_trial<RB, XR, CB>(gp, m, o, lane);
+        __builtin_amdgcn_s_setprio(0);
+      } else {
+        if (lane < N) o[lane] = 0;
+        if (lane == 0 && n_bad) atomicAdd(n_bad, 1);
+      }
+    }
+    MIB_STAMP(0)
+    if (!more) break;
+    __syncthreads();  // A: layer 2 reads every wave's part of the y1 rows
+    MIB_STAMP(1)
+    layer2<RB, XR, CB>(gp, m.y1, cv.y1s, m.y2, cv.y2s, k2, wave, lane);
+    wg::wave_sync_lds();  // layer 3 of filter f reads only y2 row f, written by this wave
+    MIB_STAMP(2)
+    __builtin_amdgcn_s_setprio(wg::PRIO_L3);
+    layer3<XR, CB>(gp, m.sg, m.y2, cv.y2s, m.y3, wave, lane);
+    __builtin_amdgcn_s_setprio(0);
+    MIB_STAMP(3)
+    __syncthreads();  // B: layer 4 reads every filter's layer-3 rows
+    MIB_STAMP(4)
+    wprev = valid ? w : -2 - w;
   }
   MIB_STAMP_FLUSH(lane == 0, wave)
 }

@@ -241,10 +241,12 @@ size_t windows_count(const Dims& d, size_t L, size_t hop) {
   return hop == 0 || L < (size_t)d.T ? 0 : (L - (size_t)d.T) / hop + 1;
 }
 
-// Layer 1 over the recording (layout as gen::Layout) into ws, then the W windows' layers 2-5.
-// hg: the host copy of the gen::GenParams p points to.
+// Layer 1 over the recording (layout as gen::Layout) into ws, then the W windows' layers 2-5:
+// window w at sample w hop, or, with onsets (a device list, net_model_compute_windows_at), at
+// onsets[w], invalid ones counted in *n_bad.  hg: the host copy of the gen::GenParams p points to.
 int launch_windows(DeviceState& ds, const gen::GenParams& hg, const void* p, int layout, const int8_t* x, size_t Lr,
-                   size_t hop, size_t W, int8_t* y, int8_t* ws, hipStream_t st, float qs) {
+                   size_t hop, size_t W, int8_t* y, int8_t* ws, hipStream_t st, float qs,
+                   const int64_t* onsets = nullptr, int32_t* n_bad = nullptr) {
   const int rs = (int)windows_row_stride(Lr), lds = carve_of(hg, 3).bytes;
   const size_t nb = (Lr + 15) / 16, wgs = (nb + win::NW1 - 1) / win::NW1;
   const gen::GenParams* gp = (const gen::GenParams*)p;
@@ -255,11 +257,18 @@ int launch_windows(DeviceState& ds, const gen::GenParams& hg, const void* p, int
       hipLaunchKernelGGL((win::k_layer1_rec<decltype(lc)::value, XR, CB>), dim3((unsigned)capped_grid(ds, wgs, 8)),
                          dim3(win::NT1), 0, st, gp, x, ws, (int)Lr, rs, qs, recip_scale(qs));
       if (const int rc = hip_err(hipGetLastError())) return rc;
-      auto kern = win::k_forward_y1<RB, XR, CB>;
-      const int grid = capped_grid(ds, W, gen_blocks_per_cu((const void*)kern, lds));
-      // hop > INT32_MAX: a single window (hop <= L - T < 2^27 otherwise), which never multiplies it
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(gen::NT), (size_t)lds, st, gp, (const int8_t*)ws, y, (int)W,
-                         (int)std::min(hop, (size_t)INT32_MAX), rs);
+      if (onsets) {
+        auto kern = win::k_forward_y1_at<RB, XR, CB>;
+        const int grid = capped_grid(ds, W, gen_blocks_per_cu((const void*)kern, lds));
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(gen::NT), (size_t)lds, st, gp, (const int8_t*)ws,
+                           (const long long*)onsets, y, (int*)n_bad, (int)W, (long long)(Lr - (size_t)hg.T), rs);
+      } else {
+        auto kern = win::k_forward_y1<RB, XR, CB>;
+        const int grid = capped_grid(ds, W, gen_blocks_per_cu((const void*)kern, lds));
+        // hop > INT32_MAX: a single window (hop <= L - T < 2^27 otherwise), which never multiplies it
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(gen::NT), (size_t)lds, st, gp, (const int8_t*)ws, y, (int)W,
+                           (int)std::min(hop, (size_t)INT32_MAX), rs);
+      }
       const int rc = hip_err(hipGetLastError());
       note_launch(ds, p, st);  // the layer-1 kernel reads the copy even if the second launch failed
       return rc;
@@ -298,6 +307,67 @@ int windows_async(const void* x, int arg_layout, bool f32, size_t L, size_t hop,
   if (sc.rc) return sc.rc;
   return launch_windows(sc.ds, *(const gen::GenParams*)win.data.get(), sc.image, layout, (const int8_t*)x, L, hop, W, y,
                         (int8_t*)ws, (hipStream_t)stream, qs);
+}
+
+// The windows at the W device-side onsets (win::k_forward_y1_at); the arguments shared with
+// windows_async mean the same, and every check comes before the first device call.
+int windows_at_async(const void* x, int arg_layout, bool f32, size_t L, const int64_t* onsets, size_t W, float qs,
+                     int8_t* y, int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream) {
+  const Snapshot s = snapshot();
+  if (!s.host) return NET_ERR_NO_PARAMS;
+  const Dims& d = s.host->d;
+  if (!f32 && arg_layout != 0 && arg_layout != 1) return NET_ERR_INVALID;
+  const int layout = f32 ? (int)gen::F32 : arg_layout;  // gen::Layout
+  if (W && (!x || !y || !onsets || !ws)) return NET_ERR_INVALID;
+  if (((uintptr_t)y & 3) != 0 || ((uintptr_t)n_bad & 3) != 0 || ((uintptr_t)onsets & 7) != 0) return NET_ERR_INVALID;
+  if (layout == 2 && ((uintptr_t)x & 3) != 0) return NET_ERR_INVALID;
+  if (L > SIZE_MAX / 32) return NET_ERR_INVALID;  // (far past the offset limit below; 16 rs cannot wrap)
+  const size_t rs = windows_row_stride(L);
+  if (((uintptr_t)ws & 15) != 0 || ws_bytes < 16 * rs) return NET_ERR_INVALID;
+  if (W && L < (size_t)d.T) return NET_ERR_INVALID;  // no onset can be valid
+  // window indices are int in the kernel: w + gridDim.x (grid <= 2 per CU) must not wrap
+  if (W > (size_t)INT32_MAX - 65535) return NET_ERR_INVALID;
+  // the recording and the workspace are each one buffer view with 32-bit offsets
+  const size_t per = std::max((size_t)16, (size_t)d.C * (layout == 2 ? sizeof(float) : 1));
+  if (L > (((size_t)1 << 31) - 1) / per) return NET_ERR_INVALID;
+  if (device < 0 || device >= MAX_DEVICES) return NET_ERR_INVALID;
+  if (layout == 2)
+    if (const int rc = check_scale(qs)) return rc;
+  const Image& win = s.img[IMG_WINDOWS];
+  if (!win.data) return NET_ERR_UNSUPPORTED;
+  if (W == 0) return NET_OK;
+  DeviceScope sc(device, s, IMG_WINDOWS);
+  if (sc.rc) return sc.rc;
+  return launch_windows(sc.ds, *(const gen::GenParams*)win.data.get(), sc.image, layout, (const int8_t*)x, L, 0, W, y,
+                        (int8_t*)ws, (hipStream_t)stream, qs, onsets, n_bad);
+}
+
+// The sliding windows of R recordings laid end to end (lengths[r] samples each): recording r, at
+// sample s_r = the sum of the lengths before it, contributes the onsets s_r + k hop, k <
+// windows_count(lengths[r], hop).  Returns their number W (0 on an error, writing nothing); fills
+// onsets if cap >= W and first[0 .. R] (each recording's first index, first[R] = W) if non-null.
+size_t windows_multi(const size_t* lengths, size_t R, size_t hop, int64_t* onsets, size_t cap, size_t* first) {
+  const Snapshot s = snapshot();
+  if (!s.host || hop == 0 || (R && !lengths)) return 0;
+  const Dims& d = s.host->d;
+  size_t sum = 0, W = 0;  // W <= sum
+  for (size_t r = 0; r < R; r++) {
+    if (lengths[r] > (size_t)INT64_MAX - sum) return 0;  // the onsets are int64
+    sum += lengths[r];
+    W += windows_count(d, lengths[r], hop);
+  }
+  const bool fill = onsets && cap >= W;
+  size_t start = 0, i = 0;
+  for (size_t r = 0; r < R; r++) {
+    if (first) first[r] = i;
+    const size_t n = windows_count(d, lengths[r], hop);
+    if (fill)
+      for (size_t k = 0; k < n; k++) onsets[i + k] = (int64_t)(start + k * hop);
+    i += n;
+    start += lengths[r];
+  }
+  if (first) first[R] = W;
+  return W;
 }
 
 // ---- epochs cut out of a wider array (forward_ep.hpp) -----------------------------------------
@@ -708,6 +778,25 @@ int net_model_compute_windows(const int8_t* x, int layout, size_t L, size_t hop,
 int net_model_compute_windows_f32(const float* x, size_t L, size_t hop, float scale, int8_t* y, void* ws,
                                   size_t ws_bytes, int device, void* stream) {
   return windows_async(x, 1, true, L, hop, scale, y, ws, ws_bytes, device, stream);
+}
+
+int net_model_compute_windows_at(const int8_t* x, int layout, size_t L, const int64_t* onsets, size_t W, int8_t* y,
+                                 int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream) {
+  return windows_at_async(x, layout, false, L, onsets, W, 0.0f, y, n_bad, ws, ws_bytes, device, stream);
+}
+
+int net_model_compute_windows_at_f32(const float* x, size_t L, const int64_t* onsets, size_t W, float scale, int8_t* y,
+                                     int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream) {
+  return windows_at_async(x, 1, true, L, onsets, W, scale, y, n_bad, ws, ws_bytes, device, stream);
+}
+
+size_t net_windows_multi_count(const size_t* lengths, size_t R, size_t hop) {
+  return windows_multi(lengths, R, hop, nullptr, 0, nullptr);
+}
+
+size_t net_windows_multi_onsets(const size_t* lengths, size_t R, size_t hop, int64_t* onsets, size_t cap,
+                                size_t* first) {
+  return windows_multi(lengths, R, hop, onsets, cap, first);
 }
 
 int net_model_compute_epochs(const int8_t* x, size_t n_elems, size_t row_stride, const int32_t* channels,

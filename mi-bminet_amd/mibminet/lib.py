@@ -38,6 +38,8 @@ EXPORTED_SYMBOLS = (
     "net_windows_count", "net_windows_row_stride", "net_windows_workspace",
     "net_model_compute_windows", "net_model_compute_windows_f32",
     "net_model_compute_epochs", "net_model_compute_epochs_f32",
+    "net_model_compute_windows_at", "net_model_compute_windows_at_f32",
+    "net_windows_multi_count", "net_windows_multi_onsets",
 )
 NET_PATH_FLOAT, NET_PATH_EXACT, NET_PATH_GENERAL = 0, 1, 2
 
@@ -134,6 +136,14 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     L.net_model_compute_epochs.restype = i
     L.net_model_compute_epochs_f32.argtypes = [vp, sz, sz, vp, vp, sz, ctypes.c_float, vp, vp, i, vp]
     L.net_model_compute_epochs_f32.restype = i
+    L.net_model_compute_windows_at.argtypes = [vp, i, sz, vp, sz, vp, vp, vp, sz, i, vp]
+    L.net_model_compute_windows_at.restype = i
+    L.net_model_compute_windows_at_f32.argtypes = [vp, sz, vp, sz, ctypes.c_float, vp, vp, vp, sz, i, vp]
+    L.net_model_compute_windows_at_f32.restype = i
+    L.net_windows_multi_count.argtypes = [vp, sz, sz]
+    L.net_windows_multi_count.restype = sz
+    L.net_windows_multi_onsets.argtypes = [vp, sz, sz, vp, sz, vp]
+    L.net_windows_multi_onsets.restype = sz
     # test hooks (include/mibminet_testing.h)
     L.mibminet_test_force_general.argtypes = [i]
     L.mibminet_test_folded_filters.argtypes = [vp]
@@ -454,6 +464,160 @@ def forward_windows_f32_torch(x, hop: int, scale: float, stream=None):
     return y
 
 
+def _onsets_tensor(onsets):
+    """``onsets`` (a 1-D int64 tensor or a sequence of ints) as a 1-D int64 tensor."""
+    import torch
+
+    if isinstance(onsets, torch.Tensor):
+        if onsets.dtype != torch.int64 or onsets.dim() != 1:
+            raise ValueError("onsets must be a 1-D int64 tensor or a sequence of ints")
+        return onsets
+    return torch.as_tensor([int(o) for o in onsets], dtype=torch.int64).reshape(-1)
+
+
+def forward_windows_at_torch(x, onsets, layout: str = "ct", scale: Optional[float] = None, stream=None,
+                             check: bool = True, return_y1: bool = False):
+    """net_model_compute_windows_at / _f32: the windows x[:, onsets[i] : onsets[i] + T] of one
+    CUDA/HIP recording, layer 1 run once over the whole of it.  ``x`` is int8 ("ct" = [C][L] or
+    "tc" = [L][C]) or float32 ([C][L]; ``scale`` is required iff it is float32), ``onsets`` an int64
+    tensor or a sequence, in any order, duplicates allowed.  Returns the logits [W][N] int8, row i
+    what forward_ct_torch returns for that window; with ``return_y1`` also the workspace
+    [16][row_stride].  The rows of onsets outside 0 .. L - T are zero; with ``check`` their count
+    is read back (a host sync) and a ValueError names it."""
+    import torch
+
+    if layout not in ("ct", "tc"):
+        raise ValueError('layout must be "ct" ([C][L]) or "tc" ([L][C])')
+    f32 = str(getattr(x, "dtype", "")) == "torch.float32"
+    if f32 and layout != "ct":
+        raise ValueError('a float32 recording is "ct" ([C][L])')
+    L = _check_recording(x, "float32" if f32 else "int8", layout == "ct")
+    if f32 != (scale is not None):
+        raise ValueError("scale is required for a float32 recording and not accepted for an int8 one")
+    onsets = _onsets_tensor(onsets)
+    d = _dims()
+    s = torch.cuda.current_stream(x.device) if stream is None else stream
+    with torch.cuda.stream(s):  # the onsets' copy and the counter's zeroing precede the launch on its stream
+        on = onsets.to(x.device).contiguous()
+        nbad = torch.zeros((1,), dtype=torch.int32, device=x.device) if check else None
+    W = int(on.numel())
+    y = torch.empty((W, d.N), dtype=torch.int8, device=x.device)
+    ws = torch.empty((16, windows_row_stride(L)), dtype=torch.int8, device=x.device)
+    mid = (on.data_ptr() if W else None, W)
+    tail = (y.data_ptr() if W else None, nbad.data_ptr() if nbad is not None else None, ws.data_ptr(), ws.numel(),
+            x.device.index or 0, s.cuda_stream)
+    if f32:
+        _check(load().net_model_compute_windows_at_f32(x.data_ptr(), L, *mid, scale, *tail),
+               "net_model_compute_windows_at_f32")
+    else:
+        _check(load().net_model_compute_windows_at(x.data_ptr(), 1 if layout == "ct" else 0, L, *mid, *tail),
+               "net_model_compute_windows_at")
+    if nbad is not None and W:
+        s.synchronize()
+        bad = int(nbad.item())
+        if bad:
+            raise ValueError(f"{bad} of {W} onsets lie outside the recording (their logit rows are zero)")
+    return (y, ws) if return_y1 else y
+
+
+def windows_multi_onsets(lengths, hop: int):
+    """net_windows_multi_onsets: the sliding-window onsets of recordings of ``lengths`` samples laid
+    end to end along time, no window crossing a boundary.  Returns (onsets as a NumPy int64 array,
+    first as a list of R + 1 ints: first[r] = the index of recording r's first window, first[R] =
+    the number of windows)."""
+    lens = [int(v) for v in lengths]
+    if hop < 1 or any(v < 0 for v in lens) or sum(lens) >= 2**63:
+        raise ValueError("hop must be at least 1, the lengths non-negative and their sum below 2^63")
+    _dims()
+    R = len(lens)
+    arr = (ctypes.c_size_t * max(R, 1))(*lens)
+    first = (ctypes.c_size_t * (R + 1))()
+    W = int(load().net_windows_multi_count(arr, R, hop))
+    onsets = np.empty(W, np.int64)
+    load().net_windows_multi_onsets(arr, R, hop, onsets.ctypes.data if W else None, W, first)
+    return onsets, [int(v) for v in first]
+
+
+def _plan_chunks(lengths, bytes_per_sample: int, max_bytes: int):
+    """Whole recordings, in order, greedily into chunks whose total length times
+    ``bytes_per_sample`` stays below ``max_bytes``.  Returns the chunks as (first recording, one
+    past the last) pairs; a single recording at or over the limit raises ValueError."""
+    lengths = [int(v) for v in lengths]
+    chunks, start, total = [], 0, 0
+    for r, n in enumerate(lengths):
+        if n * bytes_per_sample >= max_bytes:
+            raise ValueError(f"recording {r} ({n} samples of {bytes_per_sample} bytes) reaches the limit of {max_bytes}"
+                             " bytes per call: feed it in chunks that overlap by T - hop samples (INTEGRATION.md,"
+                             ' "Continuous recordings")')
+        if (total + n) * bytes_per_sample >= max_bytes:
+            chunks.append((start, r))
+            start, total = r, 0
+        total += n
+    if start < len(lengths):
+        chunks.append((start, len(lengths)))
+    return chunks
+
+
+def forward_windows_multi_torch(recordings, hop: int, layout: str = "ct", scale: Optional[float] = None, stream=None,
+                                max_bytes: Optional[int] = None):
+    """The sliding windows (hop ``hop``) of many recordings in one call per chunk, no window
+    crossing a recording boundary.  ``recordings`` is a list of CUDA/HIP tensors ([C][L_r] each, or
+    [L_r][C] for "tc"; int8, or float32 with ``scale``), or a pair (x, lengths) of one concatenated
+    tensor and its recordings' lengths.  Returns (logits [W][N] int8, first): rows first[r] ..
+    first[r + 1] - 1 are what forward_windows_torch returns for recording r.  Whole recordings are
+    grouped into chunks whose samples times max(16, C * element size) stay below ``max_bytes``
+    (default: the entries' 2^31 limit), each chunk one forward_windows_at_torch call; no host sync."""
+    import torch
+
+    if layout not in ("ct", "tc"):
+        raise ValueError('layout must be "ct" ([C][L]) or "tc" ([L][C])')
+    if hop < 1:
+        raise ValueError("hop must be at least 1")
+    d = _dims()
+    axis = 1 if layout == "ct" else 0
+    pair = (isinstance(recordings, (tuple, list)) and len(recordings) == 2 and hasattr(recordings[0], "is_cuda")
+            and not hasattr(recordings[1], "is_cuda"))
+    if pair:
+        x, lengths = recordings[0], [int(v) for v in recordings[1]]
+        tensors = [x]
+    else:
+        tensors = list(recordings)
+        if not tensors:
+            raise ValueError("recordings must hold at least one tensor")
+    f32 = str(getattr(tensors[0], "dtype", "")) == "torch.float32"
+    for t in tensors:
+        n = _check_recording(t, "float32" if f32 else "int8", layout == "ct")
+        if t.device != tensors[0].device:
+            raise ValueError("the recordings must be on one device")
+    if pair:
+        if min(lengths, default=0) < 0 or sum(lengths) != n:
+            raise ValueError(f"the lengths must be non-negative and sum to the tensor's {n} samples")
+    else:
+        lengths = [int(t.shape[axis]) for t in tensors]
+    if f32 != (scale is not None):
+        raise ValueError("scale is required for float32 recordings and not accepted for int8 ones")
+    per = max(16, d.C * (4 if f32 else 1))
+    chunks = _plan_chunks(lengths, per, 2**31 if max_bytes is None else int(max_bytes))
+    s = torch.cuda.current_stream(tensors[0].device) if stream is None else stream
+    starts = np.concatenate(([0], np.cumsum(lengths))).tolist()
+    out, first = [], [0]
+    with torch.cuda.stream(s):  # the chunks' copies precede their launches on the stream
+        for a, b in chunks:
+            onsets, f = windows_multi_onsets(lengths[a:b], hop)
+            first += [first[a] + v for v in f[1:]]
+            if pair:
+                xc = x if (a, b) == (0, len(lengths)) else x.narrow(axis, starts[a], starts[b] - starts[a]).contiguous()
+            else:
+                xc = tensors[a] if b == a + 1 else torch.cat(tensors[a:b], dim=axis)
+            # every generated onset is valid: no counter, no host sync
+            out.append(forward_windows_at_torch(xc, torch.from_numpy(onsets), layout=layout, scale=scale, stream=s,
+                                                check=False))
+        if not out:  # no recording
+            out.append(torch.empty((0, d.N), dtype=torch.int8, device=tensors[0].device))
+        y = out[0] if len(out) == 1 else torch.cat(out, dim=0)
+    return y, first
+
+
 def _channel_table(channels, C: int):
     """The ctypes int32[C] host table of ``channels`` (None: NULL, rows 0 .. C-1)."""
     if channels is None:
@@ -490,11 +654,7 @@ def forward_epochs_torch(x, onsets, channels=None, row_stride: Optional[int] = N
     if rs < 1:
         raise ValueError("row_stride must be at least 1")
     tab = _channel_table(channels, d.C)
-    if isinstance(onsets, torch.Tensor):
-        if onsets.dtype != torch.int64 or onsets.dim() != 1:
-            raise ValueError("onsets must be a 1-D int64 tensor or a sequence of ints")
-    else:
-        onsets = torch.as_tensor([int(o) for o in onsets], dtype=torch.int64).reshape(-1)
+    onsets = _onsets_tensor(onsets)
     s = torch.cuda.current_stream(x.device) if stream is None else stream
     with torch.cuda.stream(s):  # the onsets' copy and the counter's zeroing precede the launch on its stream
         on = onsets.to(x.device).contiguous()

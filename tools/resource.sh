@@ -1,6 +1,6 @@
 #!/bin/bash
 # One line per k_forward instantiation: Cfg template args (C, T, RB, CB, CT, FQ, XR), VGPRs, scratch bytes/lane, LDS bytes.
-# The same for each ep::k_forward_ep instantiation (layout, RB, XR, CB).
+# The same for each ep::k_forward_ep instantiation (layout, RB, XR, CB) and each win::k_forward_y1_at (RB, XR, CB).
 # usage: tools/resource.sh [repo root]  (default: this checkout)
 cd "${1:-$(dirname "$0")/..}/mi-bminet_amd"
 make -s resource 2>&1 | python3 -c '
@@ -14,6 +14,10 @@ for line in sys.stdin:
     m = re.search(r"Function Name: _ZN3mib2ep12k_forward_epILi(\d)ELb(\d)ELb(\d)ELb(\d)E", line)
     if m:  # the epoch kernels (forward_ep.hpp): layout 1 = int8, 2 = float32
         cur = "ep L=%s RB=%s XR=%s CB=%s" % m.groups(); vals = {}
+        continue
+    m = re.search(r"Function Name: _ZN3mib3win15k_forward_y1_atILb(\d)ELb(\d)ELb(\d)E", line)
+    if m:  # the windows-at-onsets kernels (forward_win.hpp)
+        cur = "win_at RB=%s XR=%s CB=%s" % m.groups(); vals = {}
         continue
     if cur is None:
         continue
