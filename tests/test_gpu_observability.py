@@ -76,9 +76,9 @@ def _run_entries(case, path):
     want = oracle.COracle(ps).batch(xp, nthreads=NTH)
     junk = np.random.default_rng(B + d.T)
 
-    def check(got, what):
+    def check(got, what, rows=None):
         got = got.cpu().numpy()
-        bad = np.flatnonzero((got != want).any(1))
+        bad = np.flatnonzero((got != (want if rows is None else want[rows])).any(1))
         assert bad.size == 0, f"{name} {what}: {bad.size} of {B} trials differ, first {bad[:5]}"
 
     check(lib.forward_torch(torch.from_numpy(xp).cuda()), "time-major")
@@ -90,7 +90,16 @@ def _run_entries(case, path):
             r = _at_offset(torch, rec if layout == "ct" else rec.T, 1 + gap % 2)
             check(lib.forward_windows_torch(r, d.T + gap, layout=layout), f"windows {layout} gap {gap}")
         if gap == 3:
-            check(lib.forward_windows_f32_torch(torch.from_numpy(_dequant(rec)).cuda(), d.T + gap, SCALE), "windows float32")
+            recf = torch.from_numpy(_dequant(rec)).cuda()
+            check(lib.forward_windows_f32_torch(recf, d.T + gap, SCALE), "windows float32")
+            # the windows at given onsets: the same trials in shuffled order (a generator of its own, so
+            # the inputs of the entries below stay what they were)
+            order = np.random.default_rng(B + d.T + 1).permutation(B)
+            onsets = [int(w) * (d.T + gap) for w in order]
+            for layout in ("ct", "tc"):
+                r = _at_offset(torch, rec if layout == "ct" else rec.T, 2)
+                check(lib.forward_windows_at_torch(r, onsets, layout=layout), f"windows at {layout}", order)
+            check(lib.forward_windows_at_torch(recf, onsets, scale=SCALE), "windows at float32", order)
     src, onsets, channels = _scattered(x, junk)
     check(lib.forward_epochs_torch(_at_offset(torch, src, 3), onsets, channels=channels), "epochs")
     check(lib.forward_epochs_torch(torch.from_numpy(_dequant(src)).cuda(), onsets, channels=channels, scale=SCALE),
@@ -102,7 +111,8 @@ def _run_entries(case, path):
 def test_certified_case(name, gpu):
     """Every forward entry on the certified batch: time-major, channel-major 1-3 bytes into its
     allocation, float32, sliding windows in both layouts (the trials end to end at hop T, and with
-    three junk samples between them at hop T + 3) and from float32, epochs out of a wider source
+    three junk samples between them at hop T + 3) and from float32, the windows at given onsets of
+    the latter recording in shuffled order (both layouts and float32), epochs out of a wider source
     with a permuted channel map and unsorted onsets (int8 and float32), and the single-trial entry.
     The compiled geometries run their compiled kernels here."""
     case = ob.CASES[NAMES.index(name)]
