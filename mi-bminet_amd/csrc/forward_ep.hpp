@@ -11,8 +11,9 @@
 //   per lane   (once per kernel) rowoff = elem_size channels[min(lane, C - 1)] row_stride;
 //   per block  one unaligned 16-byte fetch at delta + rowoff + 16 blk (gen::load16u; float32: four
 //              16-byte loads and the input quantiser, gen::load16f).
-// Layers 2-5, the persistent loop and its two barriers are gen::'s own, on a gen::GenParams image
-// (every geometry, the compiled ones included: the image the window kernels use).
+// Layers 2-5, the persistent loop and its two barriers are gen::'s own (gen::item_loop, which the
+// window kernels run too), on a gen::GenParams image (every geometry, the compiled ones included:
+// the image the window kernels use).
 #pragma once
 #include "forward_gen.hpp"
 
@@ -68,11 +69,49 @@ __device__ __forceinline__ void layer1_ep(const gen::GenParams* __restrict__ gp,
   }
 }
 
-// Fused forward over E epochs of the source x (layout L: CT int8, F32 float32), logits [E][N].
-// last = n_elems - span, the largest valid onset; span_bytes = elem_size span.  An onset outside
-// [0, last] forms no address: its epoch is read at onset 0 and discarded, its logit row is written
-// as zeros and *n_bad (if non-null) counts it.  gen::k_forward's loop in win::k_forward_y1's form
-// (one pass more than the workgroup has epochs; the last pass only finishes the last epoch).
+// Where gen::item_loop finds epoch e: the view at onsets[e], range-checked.  last = n_elems -
+// span, the largest valid onset; span_bytes = elem_size span.  An onset outside [0, last] forms no
+// address: its epoch is read at onset 0 and discarded.  Waves 0 .. NW-2 run layer 1 of all but the
+// epoch's last K7 blocks, which the last wave runs after finishing the previous epoch
+// (host-balanced against layers 4-5), in groups of two blocks when two workgroups share the CU,
+// else of four (gen::k_forward).
+template <int L, bool XR, bool CB>
+struct Epochs {
+  static constexpr bool ONSETS = true;
+  const gen::GenParams* gp;
+  const int8_t* x;
+  const long long* onsets;
+  long long last;
+  unsigned span_bytes, rowoff;
+  int8_t *y1, *stg;
+  int y1s, NB1, K7, wave, lane;
+  bool two_wg;
+  gen::L1C k1;
+  float qs, qy;
+  struct Item {
+    gen::View v;
+    bool valid;
+  };
+  __device__ __forceinline__ Item open(int e, bool more) const {
+    const long long on = more ? onsets[e] : 0;  // (wave-uniform: one scalar load)
+    const bool valid = (unsigned long long)on <= (unsigned long long)last;  // last >= 0: negative onsets fail too
+    return Item{epoch_view<L>(x, valid ? on : 0, span_bytes), valid};
+  }
+  // (layer 1 ahead of the other workgroup's layers 2-3, as gen::k_forward; the priority it raises it resets)
+  __device__ __forceinline__ void l1(const gen::View& v, int first, int nw, int end) const {
+    __builtin_amdgcn_s_setprio(wg::PRIO_L1);
+    if (two_wg) layer1_ep<L, XR, CB, false>(gp, v, rowoff, y1, y1s, stg, k1, first, nw, end, lane, qs, qy);
+    else layer1_ep<L, XR, CB, true>(gp, v, rowoff, y1, y1s, stg, k1, first, nw, end, lane, qs, qy);
+    __builtin_amdgcn_s_setprio(0);
+  }
+  __device__ __forceinline__ void rows(const Item& it) const { l1(it.v, wave, gen::NW - 1, NB1 - K7); }
+  __device__ __forceinline__ void rows_last(const Item& it) const {
+    if (K7 > 0) l1(it.v, NB1 - K7, 1, NB1);
+  }
+};
+
+// Fused forward over E epochs of the source x (layout L: CT int8, F32 float32), logits [E][N]:
+// gen::item_loop over Epochs<L>.
 template <int L, bool RB, bool XR, bool CB>
 __global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_forward_ep(
     const gen::GenParams* __restrict__ gp, const int8_t* __restrict__ x, const long long* __restrict__ onsets,
@@ -86,73 +125,15 @@ __global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // the float32 carve for both layouts: the transpose staging, no staged trial
   const Lds m = lds_of(gp, smem, F32);
-  const Carve& cv = m.cv;
-  const L1C k1 = l1_consts<L>(gp, lane);
   L2C k2;
   setup(gp, m, k2, tid, wave, lane);
-  int8_t* stg = smem + cv.stg + 1024 * wave;
-  const bool two_wg = cv.bytes <= LDS_2WG;  // layer-1 groups of two blocks (gen::k_forward)
-  const int N = gp->N, NB1 = gp->NB1, K7 = gp->K7;
   // rows past C re-read row C - 1 (their K-slots meet zero weights); below 2^31 by the host's limit
   const unsigned rowoff =
       (unsigned)((L == F32 ? 4ull : 1ull) * (unsigned long long)tab.c[min(lane, gp->C - 1)] * row_stride);
+  const Epochs<L, XR, CB> src{gp, x, onsets, last, span_bytes, rowoff, m.y1, smem + m.cv.stg + 1024 * wave, m.cv.y1s,
+                              gp->NB1, gp->K7, wave, lane, m.cv.bytes <= LDS_2WG, l1_consts<L>(gp, lane), qs, qy};
   __syncthreads();
-  // (phase stamps as gen::k_forward: 0 layer 1 / the last wave's layers 4-5, 1 barrier A,
-  // 2 layer 2, 3 layer 3, 4 barrier B, 7 loop top)
-  MIB_STAMP_INIT
-  // the previous epoch and whether its onset was valid, in one register: e valid, -2 - e invalid, -1 none
-  int eprev = -1;
-  for (int e = blockIdx.x;; e += gridDim.x) {
-    const bool more = e < E;  // uniform over the workgroup
-    MIB_STAMP(7)
-    const long long on = more ? onsets[e] : 0;
-    const bool valid = (unsigned long long)on <= (unsigned long long)last;  // last >= 0: negative onsets fail too
-    const View v = epoch_view<L>(x, valid ? on : 0, span_bytes);  // (the pass past the last epoch loads nothing)
-    // layer-1 groups of two or of four blocks (captures by value, as gen::k_forward's)
-    const auto l1 = [=](int first, int nw, int end) __attribute__((always_inline)) {
-      if (two_wg) layer1_ep<L, XR, CB, false>(gp, v, rowoff, m.y1, cv.y1s, stg, k1, first, nw, end, lane, qs, qy);
-      else layer1_ep<L, XR, CB, true>(gp, v, rowoff, m.y1, cv.y1s, stg, k1, first, nw, end, lane, qs, qy);
-    };
-    if (wave < NW - 1) {
-      if (more) {
-        __builtin_amdgcn_s_setprio(wg::PRIO_L1);
-        l1(wave, NW - 1, NB1 - K7);
-      }
-    } else {
-      if (eprev != -1) {
-        const bool vprev = eprev >= 0;
-        int8_t* o = out + (size_t)(vprev ? eprev : -2 - eprev) * N;
-        if (vprev) {
-          __builtin_amdgcn_s_setprio(wg::PRIO_L45);
-          finish_trial<RB, XR, CB>(gp, m, o, lane);
-        } else {
-          if (lane < N) o[lane] = 0;
-          if (lane == 0 && n_bad) atomicAdd(n_bad, 1);
-        }
-      }
-      // then the epoch's last K7 layer-1 blocks (host-balanced against layers 4-5)
-      if (more && K7 > 0) {
-        __builtin_amdgcn_s_setprio(wg::PRIO_L1);
-        l1(NB1 - K7, 1, NB1);
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
-    MIB_STAMP(0)
-    if (!more) break;
-    __syncthreads();  // A: layer 2 reads every wave's layer-1 rows
-    MIB_STAMP(1)
-    layer2<RB, XR, CB>(gp, m.y1, cv.y1s, m.y2, cv.y2s, k2, wave, lane);
-    wg::wave_sync_lds();  // layer 3 of filter f reads only y2 row f, written by this wave
-    MIB_STAMP(2)
-    __builtin_amdgcn_s_setprio(wg::PRIO_L3);
-    layer3<XR, CB>(gp, m.sg, m.y2, cv.y2s, m.y3, wave, lane);
-    __builtin_amdgcn_s_setprio(0);
-    MIB_STAMP(3)
-    __syncthreads();  // B: layer 4 reads every filter's layer-3 rows
-    MIB_STAMP(4)
-    eprev = valid ? e : -2 - e;
-  }
-  MIB_STAMP_FLUSH(lane == 0, wave)
+  item_loop<RB, XR, CB>(gp, m, k2, src, out, n_bad, E, wave, lane);
 }
 
 }  // namespace ep

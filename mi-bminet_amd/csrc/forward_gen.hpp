@@ -651,6 +651,72 @@ __device__ __forceinline__ void finish_trial(const GenParams* __restrict__ gp, c
   layer5<CB>(gp, m.y4, m.w5, out, 0, 1, lane);
 }
 
+// The persistent loop of the kernels that read their items where they lie (win::k_forward_y1,
+// win::k_forward_y1_at, ep::k_forward_ep): items blockIdx.x, + gridDim.x, ... < n, logits [n][N].
+// Two barriers per item, as k_forward: waves 0 .. NW-2 bring in item i's y1 rows while the last
+// wave finishes the previous item (layers 4-5; its y3t and y4 are untouched until this item's
+// layer 3); A: layer 2 reads every wave's part of the y1 rows; B: layer 4 reads every filter's
+// layer-3 rows.  One pass more than the workgroup has items: the last pass only finishes the last
+// item (one copy of that code in the kernel).  The source src says where an item's data comes from:
+//   src.open(i, more)   (wave-uniform) item i's descriptor, with .valid; on the pass past the last
+//                       item (more false) it loads nothing;
+//   src.rows(it)        what waves 0 .. NW-2 do with the item;
+//   src.rows_last(it)   what the last wave does with it after finishing the previous item (both
+//                       leave the wave at priority 0: a reset at the join of the two branches
+//                       cost the window kernels up to 2 %);
+//   S::ONSETS           items may be invalid (a caller-given onset out of range): such an item's
+//                       layers 2-3 run on whatever the y1 rows hold and their result is dropped, its
+//                       logit row is written as zeros and *n_bad (if non-null) counts it.  The
+//                       previous item and its validity travel in one register: i valid, -2 - i
+//                       invalid, -1 none.
+// (phase stamps in tools/ builds with -DMIB_STAMPS, as k_forward: 0 the rows / the last wave's
+// layers 4-5, 1 barrier A, 2 layer 2, 3 layer 3, 4 barrier B, 7 loop top)
+template <bool RB, bool XR, bool CB, class S>
+__device__ __forceinline__ void item_loop(const GenParams* __restrict__ gp, const Lds& m, const L2C& k2, const S& src,
+                                          int8_t* __restrict__ out, int* __restrict__ n_bad, int n, int wave,
+                                          int lane) {
+  const int N = gp->N;
+  MIB_STAMP_INIT
+  int prev = -1;
+  for (int i = blockIdx.x;; i += gridDim.x) {
+    const bool more = i < n;  // uniform over the workgroup
+    MIB_STAMP(7)
+    const auto it = src.open(i, more);
+    if (wave < NW - 1) {
+      if (more) src.rows(it);
+    } else {
+      if (prev != -1) {
+        const bool vprev = !S::ONSETS || prev >= 0;
+        int8_t* o = out + (size_t)(vprev ? prev : -2 - prev) * N;
+        if (vprev) {
+          __builtin_amdgcn_s_setprio(wg::PRIO_L45);
+          finish_trial<RB, XR, CB>(gp, m, o, lane);
+          __builtin_amdgcn_s_setprio(0);
+        } else {
+          if (lane < N) o[lane] = 0;
+          if (lane == 0 && n_bad) atomicAdd(n_bad, 1);
+        }
+      }
+      if (more) src.rows_last(it);
+    }
+    MIB_STAMP(0)
+    if (!more) break;
+    __syncthreads();  // A
+    MIB_STAMP(1)
+    layer2<RB, XR, CB>(gp, m.y1, m.cv.y1s, m.y2, m.cv.y2s, k2, wave, lane);
+    wg::wave_sync_lds();  // layer 3 of filter f reads only y2 row f, written by this wave
+    MIB_STAMP(2)
+    __builtin_amdgcn_s_setprio(wg::PRIO_L3);
+    layer3<XR, CB>(gp, m.sg, m.y2, m.cv.y2s, m.y3, wave, lane);
+    __builtin_amdgcn_s_setprio(0);
+    MIB_STAMP(3)
+    __syncthreads();  // B
+    MIB_STAMP(4)
+    prev = !S::ONSETS || it.valid ? i : -2 - i;
+  }
+  MIB_STAMP_FLUSH(lane == 0, wave)
+}
+
 // Fused forward over a batch of B trials (layout L), logits [B][N].
 // ST: int8 trials staged in LDS (the carve's raw area fits; the host picks the instantiation)
 template <int L, bool ST, bool RB, bool XR, bool CB>

@@ -7,10 +7,10 @@
 // and the pool-8 phase).  So layer 1 runs once per sample of the recording, not once per window:
 //   k_layer1_rec   layer 1 over the recording in 16-sample blocks -> workspace [16][row_stride]
 //                  int8 (row f = filter f, byte t = sample t; bytes L .. 16 ceil(L / 16) - 1 zero)
-//   k_forward_y1   gen::k_forward with its layer-1 phase replaced by a copy of the window's
-//                  sixteen workspace rows (T bytes each, from byte w hop) into the LDS y1 rows;
-//                  layers 2-5, the persistent loop and its two barriers are gen::'s own.
-//   k_forward_y1_at  the same with each window's first sample read from a device list and
+//   k_forward_y1   gen::item_loop (layers 2-5, the persistent loop and its two barriers) over the
+//                  windows at samples w hop: in place of layer 1, a copy of the window's sixteen
+//                  workspace rows (T bytes each) into the LDS y1 rows;
+//   k_forward_y1_at  the same body with each window's first sample read from a device list and
 //                  range-checked (net_model_compute_windows_at): irregular and overlapping
 //                  windows, and the windows of many recordings laid end to end.
 // All read a gen::GenParams image (every geometry, the compiled ones included) and are built
@@ -48,13 +48,13 @@ __global__ __launch_bounds__(NT1) void k_layer1_rec(const gen::GenParams* __rest
     gen::l1_block<L, XR, CB>(gen::l1_fetch<L>(v, blk, C, Lr, lane, qs, qy), stg, k, blk, blk == NB - 1, Lr, row, lane >> 4, lane);
 }
 
-// The view of window w's sixteen workspace rows: base = ws + w hop rounded down to a dword, delta
-// = the rest (the same for every row: ws is 16-byte aligned and rs a multiple of 16), row f at
-// byte f rs.  num_records ends with the dword holding row 15's last window byte, which lies inside
-// the workspace (w hop + T <= L <= rs): (delta + 15 rs + T + 3) & ~3 = 15 rs + ((delta + T + 3) & ~3),
-// rs being a multiple of 16.  Offsets stay below 2^31 (16 rs <= 2^31, the host's limit).
-__device__ __forceinline__ gen::View window_view(const int8_t* ws, long long w, int hop, int T, int rs) {
-  return gen::make_view(ws + w * hop, 15u * (unsigned)rs + (unsigned)T);
+// The view of the sixteen workspace rows of the window at sample on: base = ws + on rounded down
+// to a dword, delta = the rest (the same for every row: ws is 16-byte aligned and rs a multiple of
+// 16), row f at byte f rs.  num_records ends with the dword holding row 15's last window byte,
+// which lies inside the workspace (on + T <= L <= rs): (delta + 15 rs + T + 3) & ~3 =
+// 15 rs + ((delta + T + 3) & ~3), rs being a multiple of 16.  Offsets stay below 2^31 (16 rs <= 2^31, the host's limit).
+__device__ __forceinline__ gen::View window_view(const int8_t* ws, long long on, int T, int rs) {
+  return gen::make_view(ws + on, 15u * (unsigned)rs + (unsigned)T);
 }
 
 // Copies window rows into the LDS y1 rows (position 32 + t), as layer 1 leaves them: row f's T
@@ -95,118 +95,70 @@ __device__ __forceinline__ void copy_rows(const gen::View& v, int8_t* y1, int y1
   }
 }
 
-// Fused forward over the W windows of a recording whose layer-1 output is in ws ([F1][rs]),
-// logits [W][N].  gen::k_forward's loop: waves 0 .. NW-2 copy window w's rows while the last wave
-// runs layers 4-5 of the previous window; barrier A; layers 2-3; barrier B.
+// Where gen::item_loop finds window w: the workspace rows ([F1][rs]) from sample w hop, or, AT,
+// from the caller-given sample onsets[w] (net_model_compute_windows_at; any order, duplicates
+// allowed).  last = Lr - T, the largest valid onset.  A regular window is always valid; an onset
+// outside [0, last] forms no address and its rows are not copied.  Waves 0 .. NW-2 copy the rows;
+// the last wave only finishes the previous window.  HT: T is held across the loop; else it is one
+// scalar load per window.  The plain-BN float builds read it (held, they spilled 13 more scalar
+// registers and ran 1-2 % slower), the others hold it (reading cost them 0.7 %).
+template <bool AT, bool HT>
+struct Rows {
+  static constexpr bool ONSETS = AT;
+  const int8_t* ws;
+  const long long* onsets;
+  long long last;
+  const gen::GenParams* gp;
+  int hop, rs, T, NB1, y1s, tid;
+  int8_t* y1;
+  struct Item {
+    long long on;  // the window's first sample
+    bool valid;
+  };
+  __device__ __forceinline__ Item open(int w, bool more) const {
+    if constexpr (!AT) return Item{(long long)w * hop, true};
+    const long long on = more ? onsets[w] : 0;  // (wave-uniform: one scalar load)
+    return Item{on, (unsigned long long)on <= (unsigned long long)last};  // last >= 0: negative onsets fail too
+  }
+  __device__ __forceinline__ void rows(const Item& it) const {
+    const int t = HT ? T : gp->T;
+    if (it.valid) copy_rows(window_view(ws, it.on, t, rs), y1, y1s, t, NB1, rs, tid, gen::NT - 64);
+  }
+  __device__ __forceinline__ void rows_last(const Item&) const {}
+};
+
+// Fused forward over W windows of a recording whose layer-1 output is in ws, logits [W][N]:
+// gen::item_loop over Rows<AT, HT>.
+template <bool RB, bool XR, bool CB, bool AT>
+__device__ __forceinline__ void forward_y1(const gen::GenParams* __restrict__ gp, const int8_t* __restrict__ ws,
+                                           const long long* __restrict__ onsets, int8_t* __restrict__ out,
+                                           int* __restrict__ n_bad, int W, long long last, int hop, int rs) {
+  using namespace gen;
+  extern __shared__ v4i smem_v[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const Lds m = lds_of(gp, (int8_t*)smem_v, 3);
+  L2C k2;
+  setup(gp, m, k2, tid, wave, lane);
+  const Rows<AT, RB || XR> src{ws, onsets, last, gp, hop, rs, gp->T, gp->NB1, m.cv.y1s, tid, m.y1};
+  __syncthreads();
+  item_loop<RB, XR, CB>(gp, m, k2, src, out, n_bad, W, wave, lane);
+}
+
+// The windows at samples w hop (net_model_compute_windows).
 template <bool RB, bool XR, bool CB>
 __global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_forward_y1(
     const gen::GenParams* __restrict__ gp, const int8_t* __restrict__ ws, int8_t* __restrict__ out, int W, int hop,
     int rs) {
-  using namespace gen;
-  extern __shared__ v4i smem_v[];
-  int8_t* smem = (int8_t*)smem_v;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const Lds m = lds_of(gp, smem, 3);
-  const Carve& cv = m.cv;
-  L2C k2;
-  setup(gp, m, k2, tid, wave, lane);
-  const int T = gp->T, N = gp->N, NB1 = gp->NB1;
-  __syncthreads();
-  // (phase stamps as gen::k_forward: 0 the copy / the last wave's layers 4-5, 1 barrier A,
-  // 2 layer 2, 3 layer 3, 4 barrier B, 7 loop top)
-  MIB_STAMP_INIT
-  // one pass more than the workgroup has windows: the last pass only runs the last window's
-  // layers 4-5 (one copy of that code in the kernel)
-  int wprev = -1;
-  for (int w = blockIdx.x;; w += gridDim.x) {
-    const bool more = w < W;  // uniform over the workgroup
-    MIB_STAMP(7)
-    if (wave < NW - 1) {
-      if (more) copy_rows(window_view(ws, w, hop, T, rs), m.y1, cv.y1s, T, NB1, rs, tid, NT - 64);
-    } else if (wprev >= 0) {
-      __builtin_amdgcn_s_setprio(wg::PRIO_L45);
-      finish_trial<RB, XR, CB>(gp, m, out + (size_t)wprev * N, lane);
-      __builtin_amdgcn_s_setprio(0);
-    }
-    MIB_STAMP(0)
-    if (!more) break;
-    __syncthreads();  // A: layer 2 reads every wave's part of the y1 rows
-    MIB_STAMP(1)
-    layer2<RB, XR, CB>(gp, m.y1, cv.y1s, m.y2, cv.y2s, k2, wave, lane);
-    wg::wave_sync_lds();  // layer 3 of filter f reads only y2 row f, written by this wave
-    MIB_STAMP(2)
-    __builtin_amdgcn_s_setprio(wg::PRIO_L3);
-    layer3<XR, CB>(gp, m.sg, m.y2, cv.y2s, m.y3, wave, lane);
-    __builtin_amdgcn_s_setprio(0);
-    MIB_STAMP(3)
-    __syncthreads();  // B: layer 4 reads every filter's layer-3 rows
-    MIB_STAMP(4)
-    wprev = w;
-  }
-  MIB_STAMP_FLUSH(lane == 0, wave)
+  forward_y1<RB, XR, CB, false>(gp, ws, nullptr, out, nullptr, W, 0, hop, rs);
 }
 
-// The same over W windows at caller-given sample onsets (net_model_compute_windows_at): window w
-// covers samples onsets[w] .. onsets[w] + T - 1 of the workspace rows, in any order, duplicates
-// allowed.  last = Lr - T, the largest valid onset.  An onset outside [0, last] forms no address:
-// its rows are not copied (layers 2-3 run on whatever the y1 rows hold and their result is
-// dropped), its logit row is written as zeros and *n_bad (if non-null) counts it, as
-// ep::k_forward_ep does; the previous window and its validity travel in one register.
+// The windows at the onsets of a device list (net_model_compute_windows_at).
 template <bool RB, bool XR, bool CB>
 __global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_forward_y1_at(
     const gen::GenParams* __restrict__ gp, const int8_t* __restrict__ ws, const long long* __restrict__ onsets,
     int8_t* __restrict__ out, int* __restrict__ n_bad, int W, long long last, int rs) {
-  using namespace gen;
-  extern __shared__ v4i smem_v[];
-  int8_t* smem = (int8_t*)smem_v;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const Lds m = lds_of(gp, smem, 3);
-  const Carve& cv = m.cv;
-  L2C k2;
-  setup(gp, m, k2, tid, wave, lane);
-  const int T = gp->T, N = gp->N, NB1 = gp->NB1;
-  __syncthreads();
-  // (phase stamps as k_forward_y1)
-  MIB_STAMP_INIT
-  // the previous window and whether its onset was valid: w valid, -2 - w invalid, -1 none
-  int wprev = -1;
-  for (int w = blockIdx.x;; w += gridDim.x) {
-    const bool more = w < W;  // uniform over the workgroup
-    MIB_STAMP(7)
-    const long long on = more ? onsets[w] : 0;  // (wave-uniform: one scalar load)
-    const bool valid = (unsigned long long)on <= (unsigned long long)last;  // last >= 0: negative onsets fail too
-    if (wave < NW - 1) {
-      if (more && valid) copy_rows(window_view(ws, on, 1, T, rs), m.y1, cv.y1s, T, NB1, rs, tid, NT - 64);
-    } else if (wprev != -1) {
-      const bool vprev = wprev >= 0;
-      int8_t* o = out + (size_t)(vprev ? wprev : -2 - wprev) * N;
-      if (vprev) {
-        __builtin_amdgcn_s_setprio(wg::PRIO_L45);
-        finish_trial<RB, XR, CB>(gp, m, o, lane);
-        __builtin_amdgcn_s_setprio(0);
-      } else {
-        if (lane < N) o[lane] = 0;
-        if (lane == 0 && n_bad) atomicAdd(n_bad, 1);
-      }
-    }
-    MIB_STAMP(0)
-    if (!more) break;
-    __syncthreads();  // A: layer 2 reads every wave's part of the y1 rows
-    MIB_STAMP(1)
-    layer2<RB, XR, CB>(gp, m.y1, cv.y1s, m.y2, cv.y2s, k2, wave, lane);
-    wg::wave_sync_lds();  // layer 3 of filter f reads only y2 row f, written by this wave
-    MIB_STAMP(2)
-    __builtin_amdgcn_s_setprio(wg::PRIO_L3);
-    layer3<XR, CB>(gp, m.sg, m.y2, cv.y2s, m.y3, wave, lane);
-    __builtin_amdgcn_s_setprio(0);
-    MIB_STAMP(3)
-    __syncthreads();  // B: layer 4 reads every filter's layer-3 rows
-    MIB_STAMP(4)
-    wprev = valid ? w : -2 - w;
-  }
-  MIB_STAMP_FLUSH(lane == 0, wave)
+  forward_y1<RB, XR, CB, true>(gp, ws, onsets, out, n_bad, W, last, 1, rs);
 }
 
 }  // namespace win

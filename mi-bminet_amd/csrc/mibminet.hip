@@ -180,6 +180,17 @@ int gen_blocks_per_cu(const void* k, int lds) {
   return n;
 }
 
+// The grid of a general-family kernel with `lds` bytes of dynamic LDS over `items` (gen_blocks_per_cu
+// also lets the kernel take that much), and its launch.
+int gen_grid(const DeviceState& ds, const void* kern, int lds, size_t items) {
+  return capped_grid(ds, items, gen_blocks_per_cu(kern, lds));
+}
+template <class K, class... A>
+int launch_items(const DeviceState& ds, K kern, int lds, size_t items, hipStream_t st, A... args) {
+  hipLaunchKernelGGL(kern, dim3(gen_grid(ds, (const void*)kern, lds, items)), dim3(gen::NT), (size_t)lds, st, args...);
+  return hip_err(hipGetLastError());
+}
+
 // hg: the host copy of the gen::GenParams p points to (the general path reads its dimensions and
 // flags).  Int8 trials that fit in LDS run the staged instantiation (gen::carve_of).
 int launch_gen(DeviceState& ds, const gen::GenParams& hg, const void* p, const int8_t* x, int8_t* y, size_t B,
@@ -190,12 +201,12 @@ int launch_gen(DeviceState& ds, const gen::GenParams& hg, const void* p, const i
     return with_flags(hg, [&](auto rb, auto xr, auto cb) {
       auto go = [&](auto staged) {
         auto kern = gen::k_forward<L, decltype(staged)::value, decltype(rb)::value, decltype(xr)::value, decltype(cb)::value>;
-        const int grid = capped_grid(ds, B, gen_blocks_per_cu((const void*)kern, cv.bytes));
-        if (info) { info[0] = grid; info[1] = gen::NT; info[2] = cv.bytes; return NET_OK; }
+        if (info) {
+          info[0] = gen_grid(ds, (const void*)kern, cv.bytes, B); info[1] = gen::NT; info[2] = cv.bytes;
+          return NET_OK;
+        }
         if (B == 0) return NET_OK;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(gen::NT), (size_t)cv.bytes, st, (const gen::GenParams*)p, x, y,
-                           (int)B, qs, recip_scale(qs));
-        return hip_err(hipGetLastError());
+        return launch_items(ds, kern, cv.bytes, B, st, (const gen::GenParams*)p, x, y, (int)B, qs, recip_scale(qs));
       };
       if constexpr (L != gen::F32) {
         if (cv.raw >= 0) return go(std::true_type{});
@@ -257,41 +268,41 @@ int launch_windows(DeviceState& ds, const gen::GenParams& hg, const void* p, int
       hipLaunchKernelGGL((win::k_layer1_rec<decltype(lc)::value, XR, CB>), dim3((unsigned)capped_grid(ds, wgs, 8)),
                          dim3(win::NT1), 0, st, gp, x, ws, (int)Lr, rs, qs, recip_scale(qs));
       if (const int rc = hip_err(hipGetLastError())) return rc;
-      if (onsets) {
-        auto kern = win::k_forward_y1_at<RB, XR, CB>;
-        const int grid = capped_grid(ds, W, gen_blocks_per_cu((const void*)kern, lds));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(gen::NT), (size_t)lds, st, gp, (const int8_t*)ws,
-                           (const long long*)onsets, y, (int*)n_bad, (int)W, (long long)(Lr - (size_t)hg.T), rs);
-      } else {
-        auto kern = win::k_forward_y1<RB, XR, CB>;
-        const int grid = capped_grid(ds, W, gen_blocks_per_cu((const void*)kern, lds));
-        // hop > INT32_MAX: a single window (hop <= L - T < 2^27 otherwise), which never multiplies it
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(gen::NT), (size_t)lds, st, gp, (const int8_t*)ws, y, (int)W,
-                           (int)std::min(hop, (size_t)INT32_MAX), rs);
-      }
-      const int rc = hip_err(hipGetLastError());
+      // hop > INT32_MAX: a single window (hop <= L - T < 2^27 otherwise), at sample 0 whatever hop is
+      const int rc = onsets ? launch_items(ds, win::k_forward_y1_at<RB, XR, CB>, lds, W, st, gp, (const int8_t*)ws,
+                                           (const long long*)onsets, y, (int*)n_bad, (int)W,
+                                           (long long)(Lr - (size_t)hg.T), rs)
+                            : launch_items(ds, win::k_forward_y1<RB, XR, CB>, lds, W, st, gp, (const int8_t*)ws, y, (int)W,
+                                           (int)std::min(hop, (size_t)INT32_MAX), rs);
       note_launch(ds, p, st);  // the layer-1 kernel reads the copy even if the second launch failed
       return rc;
     });
   });
 }
 
-// arg_layout: the int8 entry's layout argument (0 time-major, 1 channel-major); f32: the float32
-// entry (channel-major, scale qs).  Every argument and parameter check comes before the first
-// device call.
-int windows_async(const void* x, int arg_layout, bool f32, size_t L, size_t hop, float qs, int8_t* y, void* ws,
-                  size_t ws_bytes, int device, void* stream) {
+// Both windows entries.  arg_layout: the int8 entry's layout argument (0 time-major, 1
+// channel-major); f32: the float32 entry (channel-major, scale qs).  at selects the entry: false,
+// the windows at every hop-th sample (onsets, W_at and n_bad unused); true, the W_at windows at the
+// device list onsets (win::k_forward_y1_at; hop unused), invalid ones counted in *n_bad.  The list
+// may be null only with W_at == 0, which returns before any launch, so launch_windows, reached
+// with W > 0 only, tells the two by the list.  Every argument and parameter check comes before the
+// first device call.
+int windows_async(const void* x, int arg_layout, bool f32, size_t L, bool at, size_t hop, const int64_t* onsets,
+                  size_t W_at, float qs, int8_t* y, int32_t* n_bad, void* ws, size_t ws_bytes, int device,
+                  void* stream) {
   const Snapshot s = snapshot();
   if (!s.host) return NET_ERR_NO_PARAMS;
   const Dims& d = s.host->d;
-  if (hop == 0 || (!f32 && arg_layout != 0 && arg_layout != 1)) return NET_ERR_INVALID;
+  if ((!at && hop == 0) || (!f32 && arg_layout != 0 && arg_layout != 1)) return NET_ERR_INVALID;
   const int layout = f32 ? (int)gen::F32 : arg_layout;  // gen::Layout
-  const size_t W = windows_count(d, L, hop);
-  if (W && (!x || !y || !ws)) return NET_ERR_INVALID;
+  const size_t W = at ? W_at : windows_count(d, L, hop);
+  if (W && (!x || !y || !ws || (at && !onsets))) return NET_ERR_INVALID;
+  if (((uintptr_t)y & 3) != 0 || (layout == 2 && ((uintptr_t)x & 3) != 0)) return NET_ERR_INVALID;
+  if (at && (((uintptr_t)n_bad & 3) != 0 || ((uintptr_t)onsets & 7) != 0)) return NET_ERR_INVALID;
   if (L > SIZE_MAX / 32) return NET_ERR_INVALID;  // (far past the offset limit below; 16 rs cannot wrap)
   const size_t rs = windows_row_stride(L);
   if (((uintptr_t)ws & 15) != 0 || ws_bytes < 16 * rs) return NET_ERR_INVALID;
-  if (((uintptr_t)y & 3) != 0 || (layout == 2 && ((uintptr_t)x & 3) != 0)) return NET_ERR_INVALID;
+  if (at && W && L < (size_t)d.T) return NET_ERR_INVALID;  // no onset can be valid
   if (device < 0 || device >= MAX_DEVICES) return NET_ERR_INVALID;
   // window indices are int in the kernel: w + gridDim.x (grid <= 2 per CU) must not wrap
   if (W > (size_t)INT32_MAX - 65535) return NET_ERR_INVALID;
@@ -306,39 +317,6 @@ int windows_async(const void* x, int arg_layout, bool f32, size_t L, size_t hop,
   DeviceScope sc(device, s, IMG_WINDOWS);
   if (sc.rc) return sc.rc;
   return launch_windows(sc.ds, *(const gen::GenParams*)win.data.get(), sc.image, layout, (const int8_t*)x, L, hop, W, y,
-                        (int8_t*)ws, (hipStream_t)stream, qs);
-}
-
-// The windows at the W device-side onsets (win::k_forward_y1_at); the arguments shared with
-// windows_async mean the same, and every check comes before the first device call.
-int windows_at_async(const void* x, int arg_layout, bool f32, size_t L, const int64_t* onsets, size_t W, float qs,
-                     int8_t* y, int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream) {
-  const Snapshot s = snapshot();
-  if (!s.host) return NET_ERR_NO_PARAMS;
-  const Dims& d = s.host->d;
-  if (!f32 && arg_layout != 0 && arg_layout != 1) return NET_ERR_INVALID;
-  const int layout = f32 ? (int)gen::F32 : arg_layout;  // gen::Layout
-  if (W && (!x || !y || !onsets || !ws)) return NET_ERR_INVALID;
-  if (((uintptr_t)y & 3) != 0 || ((uintptr_t)n_bad & 3) != 0 || ((uintptr_t)onsets & 7) != 0) return NET_ERR_INVALID;
-  if (layout == 2 && ((uintptr_t)x & 3) != 0) return NET_ERR_INVALID;
-  if (L > SIZE_MAX / 32) return NET_ERR_INVALID;  // (far past the offset limit below; 16 rs cannot wrap)
-  const size_t rs = windows_row_stride(L);
-  if (((uintptr_t)ws & 15) != 0 || ws_bytes < 16 * rs) return NET_ERR_INVALID;
-  if (W && L < (size_t)d.T) return NET_ERR_INVALID;  // no onset can be valid
-  // window indices are int in the kernel: w + gridDim.x (grid <= 2 per CU) must not wrap
-  if (W > (size_t)INT32_MAX - 65535) return NET_ERR_INVALID;
-  // the recording and the workspace are each one buffer view with 32-bit offsets
-  const size_t per = std::max((size_t)16, (size_t)d.C * (layout == 2 ? sizeof(float) : 1));
-  if (L > (((size_t)1 << 31) - 1) / per) return NET_ERR_INVALID;
-  if (device < 0 || device >= MAX_DEVICES) return NET_ERR_INVALID;
-  if (layout == 2)
-    if (const int rc = check_scale(qs)) return rc;
-  const Image& win = s.img[IMG_WINDOWS];
-  if (!win.data) return NET_ERR_UNSUPPORTED;
-  if (W == 0) return NET_OK;
-  DeviceScope sc(device, s, IMG_WINDOWS);
-  if (sc.rc) return sc.rc;
-  return launch_windows(sc.ds, *(const gen::GenParams*)win.data.get(), sc.image, layout, (const int8_t*)x, L, 0, W, y,
                         (int8_t*)ws, (hipStream_t)stream, qs, onsets, n_bad);
 }
 
@@ -415,11 +393,9 @@ int epochs_async(const void* x, bool f32, size_t n_elems, size_t row_stride, con
   const int lds = carve_of(hg, gen::F32).bytes;
   return with_flags(hg, [&](auto rb, auto xr, auto cb) {
     auto go = [&](auto kern) {
-      const int grid = capped_grid(sc.ds, E, gen_blocks_per_cu((const void*)kern, lds));
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(gen::NT), (size_t)lds, st, (const gen::GenParams*)sc.image,
-                         (const int8_t*)x, (const long long*)onsets, y, (int*)n_bad, (int)E, last, (unsigned)(esz * span),
-                         (unsigned long long)row_stride, tab, qs, recip_scale(qs));
-      const int rc = hip_err(hipGetLastError());
+      const int rc = launch_items(sc.ds, kern, lds, E, st, (const gen::GenParams*)sc.image, (const int8_t*)x,
+                                  (const long long*)onsets, y, (int*)n_bad, (int)E, last, (unsigned)(esz * span),
+                                  (unsigned long long)row_stride, tab, qs, recip_scale(qs));
       if (rc == NET_OK) note_launch(sc.ds, sc.image, st);
       return rc;
     };
@@ -772,22 +748,22 @@ size_t net_windows_workspace(size_t L) {
 
 int net_model_compute_windows(const int8_t* x, int layout, size_t L, size_t hop, int8_t* y, void* ws, size_t ws_bytes,
                               int device, void* stream) {
-  return windows_async(x, layout, false, L, hop, 0.0f, y, ws, ws_bytes, device, stream);
+  return windows_async(x, layout, false, L, false, hop, nullptr, 0, 0.0f, y, nullptr, ws, ws_bytes, device, stream);
 }
 
 int net_model_compute_windows_f32(const float* x, size_t L, size_t hop, float scale, int8_t* y, void* ws,
                                   size_t ws_bytes, int device, void* stream) {
-  return windows_async(x, 1, true, L, hop, scale, y, ws, ws_bytes, device, stream);
+  return windows_async(x, 1, true, L, false, hop, nullptr, 0, scale, y, nullptr, ws, ws_bytes, device, stream);
 }
 
 int net_model_compute_windows_at(const int8_t* x, int layout, size_t L, const int64_t* onsets, size_t W, int8_t* y,
                                  int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream) {
-  return windows_at_async(x, layout, false, L, onsets, W, 0.0f, y, n_bad, ws, ws_bytes, device, stream);
+  return windows_async(x, layout, false, L, true, 0, onsets, W, 0.0f, y, n_bad, ws, ws_bytes, device, stream);
 }
 
 int net_model_compute_windows_at_f32(const float* x, size_t L, const int64_t* onsets, size_t W, float scale, int8_t* y,
                                      int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream) {
-  return windows_at_async(x, 1, true, L, onsets, W, scale, y, n_bad, ws, ws_bytes, device, stream);
+  return windows_async(x, 1, true, L, true, 0, onsets, W, scale, y, n_bad, ws, ws_bytes, device, stream);
 }
 
 size_t net_windows_multi_count(const size_t* lengths, size_t R, size_t hop) {

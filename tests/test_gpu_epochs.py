@@ -18,6 +18,7 @@ from mibminet import lib
 from mibminet.params import ParamSet, pack_trials
 from test_gpu_general import _tile_sweep
 from test_gpu_windows import _at_offset
+from test_gpu_windows_at import _BAD
 
 pytestmark = pytest.mark.gpu
 NTH = min(16, os.cpu_count() or 1)
@@ -262,6 +263,63 @@ def test_persistent_loop(gpu):
     src = _source((6, 64 + E), 41)
     onsets = [int(v) for v in np.random.default_rng(41).permutation(E)]
     _check_epochs(ps, src, onsets, [5, 0, 3, 3], offset=3, witness=False)
+
+
+def test_persistent_loop_with_invalid_onsets(gpu):
+    """test_persistent_loop's epochs with every seventh onset invalid (test_gpu_windows_at's values,
+    among them ones whose low 32 bits would be valid), so that a workgroup meets invalid epochs on
+    its first pass, on its last and in between: their rows are zero, n_bad counts them exactly,
+    every other row matches the oracle and nothing is written past y.  Then the same source as
+    float32 through the in-kernel quantiser, against the oracle on the two-pass quantiser's
+    samples."""
+    import torch
+
+    ps = ParamSet.synthetic(seed=41, C=4, T=64, N=4)
+    lib.params_load(ps)
+    T, N, ch = 64, 4, [5, 0, 3, 3]
+    grid = 2 * torch.cuda.get_device_properties(0).multi_processor_count  # two workgroups per CU
+    E = 3 * grid + 1
+    L = 64 + E
+    src = _source((6, L), 41)
+    last = 6 * L - (5 * L + T)  # n_elems - span
+    assert last == E
+    onsets = [int(v) for v in np.random.default_rng(41).permutation(E)]
+    bad = list(range(0, E, 7))
+    for j, i in enumerate(bad):
+        v = _BAD[j % 7]
+        onsets[i] = last + 1 if v is None else v
+    # the low 32 bits of 2^32, 2^32 + 5 and INT64_MIN are valid onsets: the check must see 64 bits
+    assert all(0 <= (v & 0xFFFFFFFF) <= last for v in (2**32, 2**32 + 5, -(2**63)))
+    # invalid entries on a workgroup's first pass, on its last (the pass before the one that only
+    # finishes) and on one in between
+    assert bad[0] < grid and bad[-1] + grid >= E and any(grid <= i < E - grid for i in bad)
+    ok = [i for i in range(E) if i % 7]
+    want = _want(ps, _materialise(src, [onsets[i] for i in ok], ch, L, T))
+    assert want.any(axis=1).all()  # no valid row is zero itself
+    on = torch.tensor(onsets, dtype=torch.int64, device="cuda")
+    tab = (ctypes.c_int32 * 4)(*ch)
+
+    def run(x, *scale):
+        y = torch.full((E * N + 64,), 0x5A, dtype=torch.int8, device="cuda")
+        nb = torch.zeros((3,), dtype=torch.int32, device="cuda")
+        entry = lib.load().net_model_compute_epochs_f32 if scale else lib.load().net_model_compute_epochs
+        rc = entry(x.data_ptr(), x.numel(), L, tab, on.data_ptr(), E, *scale, y.data_ptr(), nb.data_ptr() + 4, 0, None)
+        assert rc == lib.NET_OK
+        torch.cuda.synchronize()
+        assert nb.cpu().tolist() == [0, len(bad), 0]
+        assert bool((y[E * N:] == 0x5A).all())
+        rows = y[: E * N].view(E, N).cpu().numpy()
+        assert not rows[bad].any()
+        return rows[ok]
+
+    np.testing.assert_array_equal(run(_at_offset(torch, src, 3)), want)
+    # float32, scale 3: the samples the two-pass quantiser makes of it (-128 becomes -127)
+    xf = _at_offset(torch, src.astype(np.float32) * np.float32(3.0 / 127.0), 4)
+    q = lib.quantize_input_torch(xf[None].contiguous(), 3.0)  # [1][stride], the trial [L][6]
+    q_rl = np.ascontiguousarray(q.cpu().numpy()[0, : L * 6].reshape(L, 6).T)
+    assert (np.abs(q_rl.astype(int) - src) <= 1).all()
+    want_f = _want(ps, _materialise(q_rl, [onsets[i] for i in ok], ch, L, T))
+    np.testing.assert_array_equal(run(xf, 3.0), want_f)
 
 
 def test_invalid_onsets(gpu):

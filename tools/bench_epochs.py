@@ -10,7 +10,8 @@ All logits of (a) are compared with (c).  One JSON line per case goes to
 <out-dir>/epochs_<name>.json and to stdout.  There is no CPU path: without a GPU this fails.
 
   python tools/bench_epochs.py [--cases b22_rec,p19_crop_i8,p19_crop_f32] [--epochs 65536]
-                               [--reps 7] [--warmup 2] [--out-dir profiles]
+                               [--reps 7] [--warmup 2] [--variant canonical|plain_bn]
+                               [--out-dir profiles]
 """
 import argparse
 import json
@@ -30,14 +31,14 @@ CASES = {  # name: (kind, C, T, N, rows of the source, float32)
 SCALE = 3.0
 
 
-def run_case(name, E, reps, warmup, seed=2026):
+def run_case(name, E, reps, warmup, variant, seed=2026):
     import torch
 
     from mibminet import lib
     from mibminet.params import ParamSet
 
     kind, C, T, N, R, f32 = CASES[name]
-    ps = ParamSet.synthetic(seed=seed, C=C, T=T, N=N)
+    ps = ParamSet.synthetic(seed=seed, C=C, T=T, N=N, reorder_bn=variant != "plain_bn")
     lib.params_load(ps)
     g = torch.Generator(device="cuda").manual_seed(seed)
     fwd = (lambda t: lib.forward_f32_torch(t, SCALE)) if f32 else lib.forward_ct_torch
@@ -97,7 +98,7 @@ def run_case(name, E, reps, warmup, seed=2026):
     esz = 4 if f32 else 1
     return {
         "name": name, "kind": kind, "C": C, "T": T, "N": N, "source_rows": R, "float32": f32, "epochs": E,
-        "path": lib.params_info()["path"], "reps": reps, "warmup": warmup,
+        "variant": variant, "path": lib.params_info()["path"], "reps": reps, "warmup": warmup,
         "ms_epochs": round(med["a"], 4), "ms_gather_forward": round(med["b"], 4), "ms_forward": round(med["c"], 4),
         "ms_epochs_min_max": [round(min(ms["a"]), 4), round(max(ms["a"]), 4)],
         "ms_gather_forward_min_max": [round(min(ms["b"]), 4), round(max(ms["b"]), 4)],
@@ -115,6 +116,8 @@ def main():
     ap.add_argument("--epochs", type=int, default=65536)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--variant", default="canonical", choices=("canonical", "plain_bn"),
+                    help="plain_bn: a set without REORDER_BN (the plain-BN kernels); the file name then carries it")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
     names = [n for n in args.cases.split(",") if n]
@@ -126,12 +129,13 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_epochs.py needs a GPU (there is no CPU path)")
     os.makedirs(args.out_dir, exist_ok=True)
+    suffix = "" if args.variant == "canonical" else "_" + args.variant
     bad = 0
     for n in names:
-        res = run_case(n, args.epochs, args.reps, args.warmup)
+        res = run_case(n, args.epochs, args.reps, args.warmup, args.variant)
         line = json.dumps(res)
         print(line, flush=True)
-        with open(os.path.join(args.out_dir, f"epochs_{n}.json"), "w") as f:
+        with open(os.path.join(args.out_dir, f"epochs_{n}{suffix}.json"), "w") as f:
             f.write(line + "\n")
         bad += res["mismatched_epochs"]
         torch.cuda.empty_cache()

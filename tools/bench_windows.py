@@ -10,7 +10,8 @@ All logits of (a) are compared with (b).  One JSON line per case goes to
 <out-dir>/windows_<name>.json and to stdout.  There is no CPU path: without a GPU this fails.
 
   python tools/bench_windows.py [--cases b22_h1,b22_h8,b22_h125,p64_h8] [--windows 65536]
-                                [--reps 7] [--warmup 2] [--out-dir profiles]
+                                [--reps 7] [--warmup 2] [--variant canonical|plain_bn]
+                                [--out-dir profiles]
 """
 import argparse
 import json
@@ -29,14 +30,14 @@ CASES = {  # name: (C, T, N, hop)
 }
 
 
-def run_case(name, W, reps, warmup, seed=2026):
+def run_case(name, W, reps, warmup, variant, seed=2026):
     import torch
 
     from mibminet import lib
     from mibminet.params import ParamSet
 
     C, T, N, hop = CASES[name]
-    ps = ParamSet.synthetic(seed=seed, C=C, T=T, N=N)
+    ps = ParamSet.synthetic(seed=seed, C=C, T=T, N=N, reorder_bn=variant != "plain_bn")
     lib.params_load(ps)
     L = T + (W - 1) * hop
     assert lib.windows_count(L, hop) == W
@@ -76,7 +77,7 @@ def run_case(name, W, reps, warmup, seed=2026):
     med = {k: statistics.median(v) for k, v in ms.items()}
     return {
         "name": name, "C": C, "T": T, "N": N, "hop": hop, "windows": W, "samples": L,
-        "path": lib.params_info()["path"], "reps": reps, "warmup": warmup,
+        "variant": variant, "path": lib.params_info()["path"], "reps": reps, "warmup": warmup,
         "ms_windows": round(med["a"], 4), "ms_batch_ct": round(med["b"], 4),
         "ms_materialise_batch_ct": round(med["c"], 4),
         "ms_windows_min_max": [round(min(ms["a"]), 4), round(max(ms["a"]), 4)],
@@ -93,6 +94,8 @@ def main():
     ap.add_argument("--windows", type=int, default=65536)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--variant", default="canonical", choices=("canonical", "plain_bn"),
+                    help="plain_bn: a set without REORDER_BN (the plain-BN kernels); the file name then carries it")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
     names = [n for n in args.cases.split(",") if n]
@@ -104,12 +107,13 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_windows.py needs a GPU (there is no CPU path)")
     os.makedirs(args.out_dir, exist_ok=True)
+    suffix = "" if args.variant == "canonical" else "_" + args.variant
     bad = 0
     for n in names:
-        res = run_case(n, args.windows, args.reps, args.warmup)
+        res = run_case(n, args.windows, args.reps, args.warmup, args.variant)
         line = json.dumps(res)
         print(line, flush=True)
-        with open(os.path.join(args.out_dir, f"windows_{n}.json"), "w") as f:
+        with open(os.path.join(args.out_dir, f"windows_{n}{suffix}.json"), "w") as f:
             f.write(line + "\n")
         bad += res["mismatched_windows"]
     sys.exit(1 if bad else 0)

@@ -15,7 +15,8 @@ case goes to <out-dir>/windows_at_<name>.json and to stdout.  There is no CPU pa
 this fails.
 
   python tools/bench_windows_at.py [--cases multi_p64,multi_b22,random_b22,regular_b22]
-                                   [--windows 65536] [--reps 7] [--warmup 2] [--out-dir profiles]
+                                   [--windows 65536] [--reps 7] [--warmup 2]
+                                   [--variant canonical|plain_bn] [--out-dir profiles]
 """
 import argparse
 import json
@@ -35,7 +36,7 @@ CASES = {  # name: (kind, C, T, N, hop, recordings, samples per recording)
 GATE = 0.03  # the same-box A/B noise
 
 
-def run_case(name, W, reps, warmup, seed=2026):
+def run_case(name, W, reps, warmup, variant, seed=2026):
     import numpy as np
     import torch
 
@@ -43,7 +44,7 @@ def run_case(name, W, reps, warmup, seed=2026):
     from mibminet.params import ParamSet
 
     kind, C, T, N, hop, R, Lr = CASES[name]
-    ps = ParamSet.synthetic(seed=seed, C=C, T=T, N=N)
+    ps = ParamSet.synthetic(seed=seed, C=C, T=T, N=N, reorder_bn=variant != "plain_bn")
     lib.params_load(ps)
     g = torch.Generator(device="cuda").manual_seed(seed)
     rng = np.random.default_rng(seed)
@@ -87,7 +88,7 @@ def run_case(name, W, reps, warmup, seed=2026):
     med = {k: statistics.median(v) for k, v in ms.items()}
     res = {
         "name": name, "kind": kind, "C": C, "T": T, "N": N, "hop": hop, "recordings": R, "samples": L,
-        "windows": int(onsets.numel()), "path": lib.params_info()["path"], "reps": reps, "warmup": warmup,
+        "windows": int(onsets.numel()), "variant": variant, "path": lib.params_info()["path"], "reps": reps, "warmup": warmup,
         "ms": {k: round(v, 4) for k, v in med.items()},
         "ms_min_max": {k: [round(min(v), 4), round(max(v), 4)] for k, v in ms.items()},
         "over_a": {k: round(v / med["a"], 4) for k, v in med.items() if k != "a"},
@@ -110,6 +111,8 @@ def main():
     ap.add_argument("--windows", type=int, default=65536)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--variant", default="canonical", choices=("canonical", "plain_bn"),
+                    help="plain_bn: a set without REORDER_BN (the plain-BN kernels); the file name then carries it")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
     args = ap.parse_args()
     names = [n for n in args.cases.split(",") if n]
@@ -121,12 +124,13 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_windows_at.py needs a GPU (there is no CPU path)")
     os.makedirs(args.out_dir, exist_ok=True)
+    suffix = "" if args.variant == "canonical" else "_" + args.variant
     bad = 0
     for n in names:
-        res = run_case(n, args.windows, args.reps, args.warmup)
+        res = run_case(n, args.windows, args.reps, args.warmup, args.variant)
         line = json.dumps(res)
         print(line, flush=True)
-        with open(os.path.join(args.out_dir, f"windows_at_{n}.json"), "w") as f:
+        with open(os.path.join(args.out_dir, f"windows_at_{n}{suffix}.json"), "w") as f:
             f.write(line + "\n")
         bad += sum(res["mismatched_rows"].values()) + (0 if res.get("gate_ok", True) else 1)
         torch.cuda.empty_cache()

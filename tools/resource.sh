@@ -1,6 +1,7 @@
 #!/bin/bash
 # One line per k_forward instantiation: Cfg template args (C, T, RB, CB, CT, FQ, XR), VGPRs, scratch bytes/lane, LDS bytes.
-# The same for each ep::k_forward_ep instantiation (layout, RB, XR, CB) and each win::k_forward_y1_at (RB, XR, CB).
+# The same for each ep::k_forward_ep instantiation (layout, RB, XR, CB) and each win::k_forward_y1 and
+# win::k_forward_y1_at (RB, XR, CB).
 # usage: tools/resource.sh [repo root]  (default: this checkout)
 cd "${1:-$(dirname "$0")/..}/mi-bminet_amd"
 make -s resource 2>&1 | python3 -c '
@@ -15,9 +16,9 @@ for line in sys.stdin:
     if m:  # the epoch kernels (forward_ep.hpp): layout 1 = int8, 2 = float32
         cur = "ep L=%s RB=%s XR=%s CB=%s" % m.groups(); vals = {}
         continue
-    m = re.search(r"Function Name: _ZN3mib3win15k_forward_y1_atILb(\d)ELb(\d)ELb(\d)E", line)
-    if m:  # the windows-at-onsets kernels (forward_win.hpp)
-        cur = "win_at RB=%s XR=%s CB=%s" % m.groups(); vals = {}
+    m = re.search(r"Function Name: _ZN3mib3win1[25]k_forward_y1(_at)?ILb(\d)ELb(\d)ELb(\d)E", line)
+    if m:  # the window kernels (forward_win.hpp): regular onsets, and onsets from a device list
+        cur = "win%s RB=%s XR=%s CB=%s" % (m.group(1) or "", *m.groups()[1:]); vals = {}
         continue
     if cur is None:
         continue
