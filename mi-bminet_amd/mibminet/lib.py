@@ -26,21 +26,63 @@ NET_ERR_BLOB = -4
 NET_ERR_RANGE = -5
 NET_ERR_HIP = -100
 
-EXPORTED_SYMBOLS = (
-    "net_model_compute", "net_forward", "net_layer1", "net_layer2", "net_layer3",
-    "net_layer3_flip_inplace", "net_layer4", "net_layer5", "net_last_error", "net_params_load",
-    "net_params_dims", "net_params_unload", "net_trial_stride", "net_model_compute_batch",
-    "net_model_compute_batch_async", "net_set_device", "net_launch_info", "net_error_string",
-    "net_version", "net_quantize_input_f32", "net_quantize_input_f64", "net_argmax_batch",
-    "net_pack_trials_i8", "net_model_compute_batch_multi", "net_model_compute_batch_ct",
-    "net_model_compute_batch_multi_ct", "net_launch_info_ct", "net_model_compute_batch_f32",
-    "net_model_compute_batch_ct_sync", "net_params_info", "net_params_load_arrays",
-    "net_windows_count", "net_windows_row_stride", "net_windows_workspace",
-    "net_model_compute_windows", "net_model_compute_windows_f32",
-    "net_model_compute_epochs", "net_model_compute_epochs_f32",
-    "net_model_compute_windows_at", "net_model_compute_windows_at_f32",
-    "net_windows_multi_count", "net_windows_multi_onsets",
-)
+# Every C function the binding calls, as "return (arguments)" in the words of _CTYPES: the net_*
+# entries in the order of include/mibminet.h (tests/test_lib_cpu.py holds each to its declaration
+# there), then the hooks of include/mibminet_testing.h that this module calls.
+_CTYPES = {"void": None, "int": ctypes.c_int, "size_t": ctypes.c_size_t, "int32_t": ctypes.c_int32,
+           "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
+           "ptr": ctypes.c_void_p, "str": ctypes.c_char_p}
+PROTOTYPES = {
+    "net_model_compute": "void (ptr, ptr)",
+    "net_forward": "int (ptr, ptr)",
+    "net_layer1": "void (ptr, ptr)",
+    "net_layer2": "void (ptr, ptr)",
+    "net_layer3": "void (ptr, ptr)",
+    "net_layer3_flip_inplace": "void (ptr)",
+    "net_layer4": "void (ptr, ptr)",
+    "net_layer5": "void (ptr, ptr)",
+    "net_last_error": "int ()",
+    "net_params_load": "int (ptr, size_t)",
+    "net_params_info": "int (ptr)",
+    "net_params_load_arrays": "int (ptr)",
+    "net_params_dims": "int (ptr)",
+    "net_params_unload": "void ()",
+    "net_trial_stride": "size_t ()",
+    "net_model_compute_batch": "int (ptr, ptr, size_t, int)",
+    "net_model_compute_batch_ct_sync": "int (ptr, ptr, size_t, int)",
+    "net_model_compute_batch_async": "int (ptr, ptr, size_t, int, ptr)",
+    "net_model_compute_batch_ct": "int (ptr, ptr, size_t, int, ptr)",
+    "net_model_compute_batch_f32": "int (ptr, ptr, size_t, float, int, ptr)",
+    "net_windows_count": "size_t (size_t, size_t)",
+    "net_windows_row_stride": "size_t (size_t)",
+    "net_windows_workspace": "size_t (size_t)",
+    "net_model_compute_windows": "int (ptr, int, size_t, size_t, ptr, ptr, size_t, int, ptr)",
+    "net_model_compute_windows_f32": "int (ptr, size_t, size_t, float, ptr, ptr, size_t, int, ptr)",
+    "net_model_compute_windows_at": "int (ptr, int, size_t, ptr, size_t, ptr, ptr, ptr, size_t, int, ptr)",
+    "net_model_compute_windows_at_f32": "int (ptr, size_t, ptr, size_t, float, ptr, ptr, ptr, size_t, int, ptr)",
+    "net_windows_multi_count": "size_t (ptr, size_t, size_t)",
+    "net_windows_multi_onsets": "size_t (ptr, size_t, size_t, ptr, size_t, ptr)",
+    "net_model_compute_epochs": "int (ptr, size_t, size_t, ptr, ptr, size_t, ptr, ptr, int, ptr)",
+    "net_model_compute_epochs_f32": "int (ptr, size_t, size_t, ptr, ptr, size_t, float, ptr, ptr, int, ptr)",
+    "net_model_compute_batch_multi": "int (int, ptr, ptr, ptr, ptr, ptr)",
+    "net_model_compute_batch_multi_ct": "int (int, ptr, ptr, ptr, ptr, ptr)",
+    "net_quantize_input_f32": "int (ptr, ptr, size_t, int, int, float, int, ptr)",
+    "net_quantize_input_f64": "int (ptr, ptr, size_t, int, int, double, int, ptr)",
+    "net_argmax_batch": "int (ptr, ptr, size_t, int, int, ptr)",
+    "net_pack_trials_i8": "int (ptr, ptr, size_t, int, int, int, ptr)",
+    "net_set_device": "int (int)",
+    "net_launch_info": "int (size_t, int, ptr)",
+    "net_launch_info_ct": "int (size_t, int, ptr)",
+    "net_error_string": "str (int)",
+    "net_version": "int ()",
+    "mibminet_test_xdiv_host": "int (ptr, size_t, int32_t, ptr)",
+    "mibminet_test_xdiv_gpu": "int (int32_t, int64_t, int64_t, ptr, int)",
+    "mibminet_test_pool_consts": "int (int32_t, int32_t, ptr, ptr)",
+    "mibminet_test_params_xr": "int ()",
+    "mibminet_test_force_general": "int (int)",
+    "mibminet_test_folded_filters": "int (ptr)",
+}
+EXPORTED_SYMBOLS = tuple(n for n in PROTOTYPES if n.startswith("net_"))
 NET_PATH_FLOAT, NET_PATH_EXACT, NET_PATH_GENERAL = 0, 1, 2
 
 
@@ -61,6 +103,12 @@ def _lib_error_string(code: int) -> str:
         return "error"
 
 
+def prototype(name: str):
+    """(restype, argtypes) of PROTOTYPES[name] as ctypes types."""
+    ret, _, args = PROTOTYPES[name].rstrip(")").partition("(")
+    return _CTYPES[ret.strip()], [_CTYPES[a.strip()] for a in args.split(",") if a.strip()]
+
+
 def load(path: str = LIB_PATH) -> ctypes.CDLL:
     """Load libmibminet.so (raises OSError — loudly — if it is missing or fails to load)."""
     global _lib
@@ -70,93 +118,9 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         raise OSError(f"libmibminet.so not found at {path}: build it with `make -C mi-bminet_amd`"
                       " (there is no CPU fallback)")
     L = ctypes.CDLL(path)
-    vp, sz, i, i8p = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p
-    for name in ("net_model_compute", "net_layer1", "net_layer2", "net_layer3", "net_layer4", "net_layer5"):
-        getattr(L, name).argtypes = [i8p, i8p]
-        getattr(L, name).restype = None
-    L.net_forward.argtypes = [i8p, i8p]
-    L.net_forward.restype = i
-    L.net_layer3_flip_inplace.argtypes = [i8p]
-    L.net_layer3_flip_inplace.restype = None
-    L.net_last_error.argtypes = []
-    L.net_last_error.restype = i
-    L.net_params_load.argtypes = [vp, sz]
-    L.net_params_load.restype = i
-    L.net_params_dims.argtypes = [vp]
-    L.net_params_dims.restype = i
-    L.net_params_unload.argtypes = []
-    L.net_params_unload.restype = None
-    L.net_trial_stride.argtypes = []
-    L.net_trial_stride.restype = sz
-    L.net_model_compute_batch.argtypes = [vp, vp, sz, i]
-    L.net_model_compute_batch.restype = i
-    L.net_model_compute_batch_async.argtypes = [vp, vp, sz, i, vp]
-    L.net_model_compute_batch_async.restype = i
-    L.net_set_device.argtypes = [i]
-    L.net_set_device.restype = i
-    L.net_launch_info.argtypes = [sz, i, vp]
-    L.net_launch_info.restype = i
-    L.net_launch_info_ct.argtypes = [sz, i, vp]
-    L.net_launch_info_ct.restype = i
-    L.net_model_compute_batch_f32.argtypes = [vp, vp, sz, ctypes.c_float, i, vp]
-    L.net_model_compute_batch_f32.restype = i
-    L.net_error_string.argtypes = [i]
-    L.net_error_string.restype = ctypes.c_char_p
-    L.net_version.argtypes = []
-    L.net_version.restype = i
-    L.net_quantize_input_f32.argtypes = [vp, vp, sz, i, i, ctypes.c_float, i, vp]
-    L.net_quantize_input_f32.restype = i
-    L.net_quantize_input_f64.argtypes = [vp, vp, sz, i, i, ctypes.c_double, i, vp]
-    L.net_quantize_input_f64.restype = i
-    L.net_model_compute_batch_multi.argtypes = [i, vp, vp, vp, vp, vp]
-    L.net_model_compute_batch_multi.restype = i
-    L.net_pack_trials_i8.argtypes = [vp, vp, sz, i, i, i, vp]
-    L.net_pack_trials_i8.restype = i
-    L.net_argmax_batch.argtypes = [vp, vp, sz, i, i, vp]
-    L.net_argmax_batch.restype = i
-    L.net_model_compute_batch_ct.argtypes = [vp, vp, sz, i, vp]
-    L.net_model_compute_batch_ct.restype = i
-    L.net_model_compute_batch_multi_ct.argtypes = [i, vp, vp, vp, vp, vp]
-    L.net_model_compute_batch_multi_ct.restype = i
-    L.net_model_compute_batch_ct_sync.argtypes = [vp, vp, sz, i]
-    L.net_model_compute_batch_ct_sync.restype = i
-    L.net_params_info.argtypes = [vp]
-    L.net_params_info.restype = i
-    L.net_windows_count.argtypes = [sz, sz]
-    L.net_windows_count.restype = sz
-    L.net_windows_row_stride.argtypes = [sz]
-    L.net_windows_row_stride.restype = sz
-    L.net_windows_workspace.argtypes = [sz]
-    L.net_windows_workspace.restype = sz
-    L.net_model_compute_windows.argtypes = [vp, i, sz, sz, vp, vp, sz, i, vp]
-    L.net_model_compute_windows.restype = i
-    L.net_model_compute_windows_f32.argtypes = [vp, sz, sz, ctypes.c_float, vp, vp, sz, i, vp]
-    L.net_model_compute_windows_f32.restype = i
-    L.net_model_compute_epochs.argtypes = [vp, sz, sz, vp, vp, sz, vp, vp, i, vp]
-    L.net_model_compute_epochs.restype = i
-    L.net_model_compute_epochs_f32.argtypes = [vp, sz, sz, vp, vp, sz, ctypes.c_float, vp, vp, i, vp]
-    L.net_model_compute_epochs_f32.restype = i
-    L.net_model_compute_windows_at.argtypes = [vp, i, sz, vp, sz, vp, vp, vp, sz, i, vp]
-    L.net_model_compute_windows_at.restype = i
-    L.net_model_compute_windows_at_f32.argtypes = [vp, sz, vp, sz, ctypes.c_float, vp, vp, vp, sz, i, vp]
-    L.net_model_compute_windows_at_f32.restype = i
-    L.net_windows_multi_count.argtypes = [vp, sz, sz]
-    L.net_windows_multi_count.restype = sz
-    L.net_windows_multi_onsets.argtypes = [vp, sz, sz, vp, sz, vp]
-    L.net_windows_multi_onsets.restype = sz
-    # test hooks (include/mibminet_testing.h)
-    L.mibminet_test_force_general.argtypes = [i]
-    L.mibminet_test_folded_filters.argtypes = [vp]
-    L.mibminet_test_folded_filters.restype = i
-    L.mibminet_test_force_general.restype = i
-    L.mibminet_test_xdiv_host.argtypes = [vp, sz, ctypes.c_int32, vp]
-    L.mibminet_test_xdiv_host.restype = i
-    L.mibminet_test_xdiv_gpu.argtypes = [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, vp, i]
-    L.mibminet_test_xdiv_gpu.restype = i
-    L.mibminet_test_pool_consts.argtypes = [ctypes.c_int32, ctypes.c_int32, vp, vp]
-    L.mibminet_test_pool_consts.restype = i
-    L.mibminet_test_params_xr.argtypes = []
-    L.mibminet_test_params_xr.restype = i
+    for name in PROTOTYPES:
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = prototype(name)
     _lib = L
     return L
 
@@ -170,20 +134,20 @@ def _check(rc: int, what: str) -> None:
 _loaded: Optional[ParamSet] = None
 
 
-def params_load(ps: ParamSet) -> None:
-    """net_params_load(blob) — replaces the generated net.h globals of the reference."""
+def _load_blob(blob: bytes, ps: Optional[ParamSet]) -> None:
     global _loaded
-    blob = ps.to_blob()
     buf = ctypes.create_string_buffer(blob, len(blob))
     _check(load().net_params_load(buf, len(blob)), "net_params_load")
-    _loaded = ps
+    _loaded = ParamSet.from_blob(blob) if ps is None else ps
+
+
+def params_load(ps: ParamSet) -> None:
+    """net_params_load(blob) — replaces the generated net.h globals of the reference."""
+    _load_blob(ps.to_blob(), ps)
 
 
 def params_load_blob(blob: bytes) -> None:
-    global _loaded
-    buf = ctypes.create_string_buffer(blob, len(blob))
-    _check(load().net_params_load(buf, len(blob)), "net_params_load")
-    _loaded = ParamSet.from_blob(blob)
+    _load_blob(blob, None)
 
 
 def params_dims() -> dict:
@@ -212,11 +176,12 @@ def _dims():
 
 
 # ---- reference single-trial API (host arrays, reference layouts) --------------------------------
-def _call_void(name: str, x: np.ndarray, out: np.ndarray) -> np.ndarray:
+def _call_void(name: str, *arrays: np.ndarray) -> np.ndarray:
+    """A void entry on host arrays, its status read from net_last_error; returns the last array."""
     L = load()
-    getattr(L, name)(x.ctypes.data, out.ctypes.data)
+    getattr(L, name)(*(a.ctypes.data for a in arrays))
     _check(L.net_last_error(), name)
-    return out
+    return arrays[-1]
 
 
 def net_model_compute(x_tc_align: np.ndarray) -> np.ndarray:
@@ -248,10 +213,7 @@ def net_layer3_flip_inplace(y3: np.ndarray) -> np.ndarray:
     """layers.h:107 — [F2][T8_ALIGN] -> [T8][F2] (in place on a copy; returned)."""
     d = _dims()
     buf = np.ascontiguousarray(y3, np.int8).reshape(d.F2 * d.T8_ALIGN).copy()
-    L = load()
-    L.net_layer3_flip_inplace(buf.ctypes.data)
-    _check(L.net_last_error(), "net_layer3_flip_inplace")
-    return buf
+    return _call_void("net_layer3_flip_inplace", buf)
 
 
 def net_layer4(y3t: np.ndarray) -> np.ndarray:
@@ -342,21 +304,76 @@ def launch_info(B: int, device: int = 0, channel_major: bool = False) -> dict:
     return {"grid": arr[0], "threads": arr[1], "lds_bytes": arr[2]}
 
 
-def forward_torch(x, params: Optional[ParamSet] = None, stream=None):
-    """Convenience: x is a CUDA/HIP int8 torch tensor [B][trial_stride] -> logits [B][N] tensor."""
+# ---- the torch entries' shared steps ----------------------------------------------------------
+def _torch():
+    """torch, imported on first use: importing this module must work where torch is never imported."""
     import torch
 
+    return torch
+
+
+def _launch(x, stream):
+    """(launch stream, device index) for the device tensor ``x`` and an optional ``stream``."""
+    s = _torch().cuda.current_stream(x.device) if stream is None else stream
+    return s, x.device.index or 0
+
+
+def _logits(x, rows: int):
+    """An uninitialised [rows][N] int8 logits tensor on ``x``'s device."""
+    return _torch().empty((rows, _dims().N), dtype=_torch().int8, device=x.device)
+
+
+def _check_tensor(x, noun: str, dtypes, dims=None, device: bool = True, contiguous: bool = True) -> str:
+    """Raises ValueError unless ``x`` is a tensor of one of ``dtypes`` (names such as "int8"), on
+    the device (``device=False``: anywhere, and a NumPy array passes too), contiguous unless
+    ``contiguous`` is false and, given ``dims``, of that rank with every int entry matched (a str
+    entry names a free dimension: ("B", 22, 1125)).  ``noun`` opens the message.  Returns the
+    dtype's name.  The C ABI sees only pointers and counts, so another element type, orientation
+    or stride would otherwise run and its bytes be read as something else."""
+    dt = str(getattr(x, "dtype", "")).rpartition(".")[2]
+    ok = dt in dtypes and (not device or getattr(x, "is_cuda", False))
+    if ok and contiguous:
+        ok = x.is_contiguous() if hasattr(x, "is_contiguous") else bool(x.flags["C_CONTIGUOUS"])
+    if ok and dims is not None:
+        shape = tuple(x.shape)
+        ok = len(shape) == len(dims) and all(isinstance(d, str) or d == n for d, n in zip(dims, shape))
+    if not ok:
+        want = " ".join(w for w in ("contiguous" if contiguous else "", "/".join(dtypes), "device" if device else "",
+                                    "tensor", "".join(f"[{d}]" for d in dims or ())) if w)
+        got = f"{dt} {tuple(x.shape)}" if dt and hasattr(x, "shape") else type(x).__name__
+        raise ValueError(f"{noun} must be a {want}, got {got}")
+    return dt
+
+
+def _layout_code(layout: str) -> int:
+    """The C ABI's integer of a recording layout: "ct" ([C][L], channel-major) = 1, "tc" = 0."""
+    if layout not in ("ct", "tc"):
+        raise ValueError('layout must be "ct" ([C][L]) or "tc" ([L][C])')
+    return 1 if layout == "ct" else 0
+
+
+def _check_scale(f32: bool, scale, noun: str) -> None:
+    if f32 != (scale is not None):
+        raise ValueError(f"scale is required for a float32 {noun} and not accepted for an int8 one")
+
+
+def _packed_stride(C: int, T: int) -> int:
+    """Bytes per trial of the batched time-major layout: C*T rounded up to 16."""
+    return (C * T + 15) // 16 * 16
+
+
+def forward_torch(x, params: Optional[ParamSet] = None, stream=None):
+    """Convenience: x is a CUDA/HIP int8 torch tensor [B][trial_stride] -> logits [B][N] tensor."""
     if params is not None:
         params_load(params)
-    d = _dims()
-    if x.dtype != torch.int8 or not x.is_cuda or not x.is_contiguous():
-        raise ValueError("x must be a contiguous int8 device tensor [B][trial_stride]")
+    _dims()
+    _check_tensor(x, "x", ("int8",))
     B = x.shape[0]
     if x.numel() != B * trial_stride():
         raise ValueError(f"x must be [B][{trial_stride()}]")
-    y = torch.empty((B, d.N), dtype=torch.int8, device=x.device)
-    s = torch.cuda.current_stream(x.device) if stream is None else stream
-    model_compute_batch(x.data_ptr(), y.data_ptr(), B, x.device.index or 0, s.cuda_stream)
+    y = _logits(x, B)
+    s, dev = _launch(x, stream)
+    model_compute_batch(x.data_ptr(), y.data_ptr(), B, dev, s.cuda_stream)
     return y
 
 
@@ -364,15 +381,11 @@ def forward_ct_torch(x, stream=None):
     """net_model_compute_batch_ct: x is a CUDA/HIP int8 tensor [B][C][T] (channel-major, the
     reference's input.npz layout; any byte alignment) -> logits [B][N] tensor, with no separate
     transpose pass."""
-    import torch
-
     d = _dims()
-    if x.dtype != torch.int8 or not x.is_cuda or not x.is_contiguous() or tuple(x.shape[1:]) != (d.C, d.T):
-        raise ValueError(f"x must be a contiguous int8 device tensor [B][{d.C}][{d.T}]")
-    B = x.shape[0]
-    y = torch.empty((B, d.N), dtype=torch.int8, device=x.device)
-    s = torch.cuda.current_stream(x.device) if stream is None else stream
-    _check(load().net_model_compute_batch_ct(x.data_ptr(), y.data_ptr(), B, x.device.index or 0, s.cuda_stream),
+    _check_tensor(x, "x", ("int8",), ("B", d.C, d.T))
+    y = _logits(x, x.shape[0])
+    s, dev = _launch(x, stream)
+    _check(load().net_model_compute_batch_ct(x.data_ptr(), y.data_ptr(), x.shape[0], dev, s.cuda_stream),
            "net_model_compute_batch_ct")
     return y
 
@@ -380,16 +393,12 @@ def forward_ct_torch(x, stream=None):
 def forward_f32_torch(x, scale: float, stream=None):
     """net_model_compute_batch_f32: x is a CUDA/HIP float32 tensor [B][C][T] (float EEG, the
     reference's input.npz layout) -> logits [B][N], quantised inside the fused kernel."""
-    import torch
-
     d = _dims()
-    if x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous() or tuple(x.shape[1:]) != (d.C, d.T):
-        raise ValueError(f"x must be a contiguous float32 device tensor [B][{d.C}][{d.T}]")
-    B = x.shape[0]
-    y = torch.empty((B, d.N), dtype=torch.int8, device=x.device)
-    s = torch.cuda.current_stream(x.device) if stream is None else stream
-    _check(load().net_model_compute_batch_f32(x.data_ptr(), y.data_ptr(), B, scale, x.device.index or 0,
-                                              s.cuda_stream), "net_model_compute_batch_f32")
+    _check_tensor(x, "x", ("float32",), ("B", d.C, d.T))
+    y = _logits(x, x.shape[0])
+    s, dev = _launch(x, stream)
+    _check(load().net_model_compute_batch_f32(x.data_ptr(), y.data_ptr(), x.shape[0], scale, dev, s.cuda_stream),
+           "net_model_compute_batch_f32")
     return y
 
 
@@ -408,28 +417,23 @@ def windows_workspace(L: int) -> int:
     return int(load().net_windows_workspace(L))
 
 
-def _check_recording(x, dtype: str, channels_first: bool):
-    """Raises ValueError unless ``x`` is a contiguous 2-D device tensor of ``dtype`` holding a
-    recording of the loaded network's C channels ([C][L] or [L][C]); returns L.  The C ABI sees
-    only a pointer and a length, so another element type or orientation would otherwise run."""
-    d = _dims()
-    want = f"[{d.C}][L]" if channels_first else f"[L][{d.C}]"
-    if str(getattr(x, "dtype", "")) != f"torch.{dtype}" or not x.is_cuda or not x.is_contiguous():
-        raise ValueError(f"the recording must be a contiguous {dtype} device tensor {want}")
-    if x.dim() != 2 or x.shape[0 if channels_first else 1] != d.C:
-        raise ValueError(f"the recording must be {want}, got {tuple(x.shape)}")
-    return int(x.shape[1 if channels_first else 0])
+def _check_recording(x, dtypes, channels_first: bool):
+    """_check_tensor for a recording of the loaded network's C channels ([C][L] or [L][C]) of one
+    of ``dtypes``; returns (L, whether it is float32)."""
+    C = _dims().C
+    dt = _check_tensor(x, "the recording", dtypes, (C, "L") if channels_first else ("L", C))
+    return int(x.shape[1 if channels_first else 0]), dt == "float32"
+
+
+def _workspace(x, L: int):
+    """An uninitialised layer-1 workspace [16][row_stride] of L samples on ``x``'s device."""
+    return _torch().empty((16, windows_row_stride(L)), dtype=_torch().int8, device=x.device)
 
 
 def _windows_buffers(x, L: int, hop: int):
-    import torch
-
     if hop < 1:
         raise ValueError("hop must be at least 1")
-    W = windows_count(L, hop)
-    y = torch.empty((W, _dims().N), dtype=torch.int8, device=x.device)
-    ws = torch.empty((16, windows_row_stride(L)), dtype=torch.int8, device=x.device)
-    return y, ws
+    return _logits(x, windows_count(L, hop)), _workspace(x, L)
 
 
 def forward_windows_torch(x, hop: int, layout: str = "ct", stream=None, return_y1: bool = False):
@@ -438,41 +442,56 @@ def forward_windows_torch(x, hop: int, layout: str = "ct", stream=None, return_y
     of the windows x[:, w*hop : w*hop + T], W = windows_count(L, hop), each row what
     forward_ct_torch returns for that window; with ``return_y1`` also the workspace
     [16][row_stride] int8, whose row f holds layer 1's filter f over the whole recording."""
-    if layout not in ("ct", "tc"):
-        raise ValueError('layout must be "ct" ([C][L]) or "tc" ([L][C])')
-    L = _check_recording(x, "int8", layout == "ct")
+    code = _layout_code(layout)
+    L, _ = _check_recording(x, ("int8",), layout == "ct")
     y, ws = _windows_buffers(x, L, hop)
-    import torch
-
-    s = torch.cuda.current_stream(x.device) if stream is None else stream
-    _check(load().net_model_compute_windows(x.data_ptr(), 1 if layout == "ct" else 0, L, hop, y.data_ptr(),
-                                            ws.data_ptr(), ws.numel(), x.device.index or 0, s.cuda_stream),
-           "net_model_compute_windows")
+    s, dev = _launch(x, stream)
+    _check(load().net_model_compute_windows(x.data_ptr(), code, L, hop, y.data_ptr(), ws.data_ptr(), ws.numel(), dev,
+                                            s.cuda_stream), "net_model_compute_windows")
     return (y, ws) if return_y1 else y
 
 
 def forward_windows_f32_torch(x, hop: int, scale: float, stream=None):
     """net_model_compute_windows_f32: x is a CUDA/HIP float32 recording [C][L], quantised per
     sample as forward_f32_torch does; returns the logits [W][N] of its sliding windows."""
-    L = _check_recording(x, "float32", True)
+    L, _ = _check_recording(x, ("float32",), True)
     y, ws = _windows_buffers(x, L, hop)
-    import torch
-
-    s = torch.cuda.current_stream(x.device) if stream is None else stream
+    s, dev = _launch(x, stream)
     _check(load().net_model_compute_windows_f32(x.data_ptr(), L, hop, scale, y.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                x.device.index or 0, s.cuda_stream), "net_model_compute_windows_f32")
+                                                dev, s.cuda_stream), "net_model_compute_windows_f32")
     return y
 
 
-def _onsets_tensor(onsets):
-    """``onsets`` (a 1-D int64 tensor or a sequence of ints) as a 1-D int64 tensor."""
-    import torch
-
-    if isinstance(onsets, torch.Tensor):
-        if onsets.dtype != torch.int64 or onsets.dim() != 1:
-            raise ValueError("onsets must be a 1-D int64 tensor or a sequence of ints")
-        return onsets
-    return torch.as_tensor([int(o) for o in onsets], dtype=torch.int64).reshape(-1)
+def _forward_onsets(name: str, x, head, onsets, scale, mid, stream, check: bool, noun: str):
+    """The call of an entry that takes an onset list, ``name`` or, with a ``scale``, ``name``_f32:
+    entry(x, *head, onsets, n, [scale,] y, n_bad, *mid, device, stream).  ``onsets`` is a 1-D int64
+    tensor or a sequence of ints; its device copy and, with ``check``, the zeroed counter are made
+    on the launch stream.  An empty list passes NULL for the onsets and the logits, ``check=False``
+    NULL for the counter.  With ``check`` and a non-empty list the stream is synchronised, the
+    count of onsets outside the ``noun`` read back and a ValueError raised if it is not zero.
+    Returns the logits [n][N]."""
+    torch = _torch()
+    if not isinstance(onsets, torch.Tensor):
+        onsets = torch.as_tensor([int(o) for o in onsets], dtype=torch.int64).reshape(-1)
+    elif onsets.dtype != torch.int64 or onsets.dim() != 1:
+        raise ValueError("onsets must be a 1-D int64 tensor or a sequence of ints")
+    s, dev = _launch(x, stream)
+    with torch.cuda.stream(s):  # the onsets' copy and the counter's zeroing precede the launch on its stream
+        on = onsets.to(x.device).contiguous()
+        nbad = torch.zeros((1,), dtype=torch.int32, device=x.device) if check else None
+    n = int(on.numel())
+    y = _logits(x, n)
+    if scale is not None:
+        name += "_f32"
+    _check(getattr(load(), name)(x.data_ptr(), *head, on.data_ptr() if n else None, n,
+                                 *(() if scale is None else (scale,)), y.data_ptr() if n else None,
+                                 nbad.data_ptr() if check else None, *mid, dev, s.cuda_stream), name)
+    if check and n:
+        s.synchronize()
+        bad = int(nbad.item())
+        if bad:
+            raise ValueError(f"{bad} of {n} onsets lie outside the {noun} (their logit rows are zero)")
+    return y
 
 
 def forward_windows_at_torch(x, onsets, layout: str = "ct", scale: Optional[float] = None, stream=None,
@@ -484,39 +503,14 @@ def forward_windows_at_torch(x, onsets, layout: str = "ct", scale: Optional[floa
     what forward_ct_torch returns for that window; with ``return_y1`` also the workspace
     [16][row_stride].  The rows of onsets outside 0 .. L - T are zero; with ``check`` their count
     is read back (a host sync) and a ValueError names it."""
-    import torch
-
-    if layout not in ("ct", "tc"):
-        raise ValueError('layout must be "ct" ([C][L]) or "tc" ([L][C])')
-    f32 = str(getattr(x, "dtype", "")) == "torch.float32"
+    code = _layout_code(layout)
+    L, f32 = _check_recording(x, ("int8", "float32"), layout == "ct")
     if f32 and layout != "ct":
         raise ValueError('a float32 recording is "ct" ([C][L])')
-    L = _check_recording(x, "float32" if f32 else "int8", layout == "ct")
-    if f32 != (scale is not None):
-        raise ValueError("scale is required for a float32 recording and not accepted for an int8 one")
-    onsets = _onsets_tensor(onsets)
-    d = _dims()
-    s = torch.cuda.current_stream(x.device) if stream is None else stream
-    with torch.cuda.stream(s):  # the onsets' copy and the counter's zeroing precede the launch on its stream
-        on = onsets.to(x.device).contiguous()
-        nbad = torch.zeros((1,), dtype=torch.int32, device=x.device) if check else None
-    W = int(on.numel())
-    y = torch.empty((W, d.N), dtype=torch.int8, device=x.device)
-    ws = torch.empty((16, windows_row_stride(L)), dtype=torch.int8, device=x.device)
-    mid = (on.data_ptr() if W else None, W)
-    tail = (y.data_ptr() if W else None, nbad.data_ptr() if nbad is not None else None, ws.data_ptr(), ws.numel(),
-            x.device.index or 0, s.cuda_stream)
-    if f32:
-        _check(load().net_model_compute_windows_at_f32(x.data_ptr(), L, *mid, scale, *tail),
-               "net_model_compute_windows_at_f32")
-    else:
-        _check(load().net_model_compute_windows_at(x.data_ptr(), 1 if layout == "ct" else 0, L, *mid, *tail),
-               "net_model_compute_windows_at")
-    if nbad is not None and W:
-        s.synchronize()
-        bad = int(nbad.item())
-        if bad:
-            raise ValueError(f"{bad} of {W} onsets lie outside the recording (their logit rows are zero)")
+    _check_scale(f32, scale, "recording")
+    ws = _workspace(x, L)
+    y = _forward_onsets("net_model_compute_windows_at", x, (L,) if f32 else (code, L), onsets, scale,
+                        (ws.data_ptr(), ws.numel()), stream, check, "recording")
     return (y, ws) if return_y1 else y
 
 
@@ -567,14 +561,12 @@ def forward_windows_multi_torch(recordings, hop: int, layout: str = "ct", scale:
     first[r + 1] - 1 are what forward_windows_torch returns for recording r.  Whole recordings are
     grouped into chunks whose samples times max(16, C * element size) stay below ``max_bytes``
     (default: the entries' 2^31 limit), each chunk one forward_windows_at_torch call; no host sync."""
-    import torch
-
-    if layout not in ("ct", "tc"):
-        raise ValueError('layout must be "ct" ([C][L]) or "tc" ([L][C])')
+    torch = _torch()
+    _layout_code(layout)
+    axis = 1 if layout == "ct" else 0  # the time axis
     if hop < 1:
         raise ValueError("hop must be at least 1")
     d = _dims()
-    axis = 1 if layout == "ct" else 0
     pair = (isinstance(recordings, (tuple, list)) and len(recordings) == 2 and hasattr(recordings[0], "is_cuda")
             and not hasattr(recordings[1], "is_cuda"))
     if pair:
@@ -584,21 +576,19 @@ def forward_windows_multi_torch(recordings, hop: int, layout: str = "ct", scale:
         tensors = list(recordings)
         if not tensors:
             raise ValueError("recordings must hold at least one tensor")
-    f32 = str(getattr(tensors[0], "dtype", "")) == "torch.float32"
     for t in tensors:
-        n = _check_recording(t, "float32" if f32 else "int8", layout == "ct")
-        if t.device != tensors[0].device:
-            raise ValueError("the recordings must be on one device")
+        n, f32 = _check_recording(t, ("int8", "float32"), layout == "ct")
+        if t.device != tensors[0].device or t.dtype != tensors[0].dtype:
+            raise ValueError("the recordings must be on one device and of one element type")
     if pair:
         if min(lengths, default=0) < 0 or sum(lengths) != n:
             raise ValueError(f"the lengths must be non-negative and sum to the tensor's {n} samples")
     else:
         lengths = [int(t.shape[axis]) for t in tensors]
-    if f32 != (scale is not None):
-        raise ValueError("scale is required for float32 recordings and not accepted for int8 ones")
+    _check_scale(f32, scale, "recording")
     per = max(16, d.C * (4 if f32 else 1))
     chunks = _plan_chunks(lengths, per, 2**31 if max_bytes is None else int(max_bytes))
-    s = torch.cuda.current_stream(tensors[0].device) if stream is None else stream
+    s, _ = _launch(tensors[0], stream)
     starts = np.concatenate(([0], np.cumsum(lengths))).tolist()
     out, first = [], [0]
     with torch.cuda.stream(s):  # the chunks' copies precede their launches on the stream
@@ -613,7 +603,7 @@ def forward_windows_multi_torch(recordings, hop: int, layout: str = "ct", scale:
             out.append(forward_windows_at_torch(xc, torch.from_numpy(onsets), layout=layout, scale=scale, stream=s,
                                                 check=False))
         if not out:  # no recording
-            out.append(torch.empty((0, d.N), dtype=torch.int8, device=tensors[0].device))
+            out.append(_logits(tensors[0], 0))
         y = out[0] if len(out) == 1 else torch.cat(out, dim=0)
     return y, first
 
@@ -640,39 +630,16 @@ def forward_epochs_torch(x, onsets, channels=None, row_stride: Optional[int] = N
     int64 tensor or a sequence.  Returns the logits [E][N] int8, row e what forward_ct_torch
     returns for the materialised epoch.  The rows of onsets outside the source are zero; with
     ``check`` their count is read back (a host sync) and a ValueError names it."""
-    import torch
-
     d = _dims()
-    if not hasattr(x, "is_cuda") or x.dtype not in (torch.int8, torch.float32) or not x.is_cuda or not x.is_contiguous():
-        raise ValueError("x must be a contiguous int8 or float32 device tensor")
-    f32 = x.dtype == torch.float32
-    if f32 != (scale is not None):
-        raise ValueError("scale is required for a float32 source and not accepted for an int8 one")
+    f32 = _check_tensor(x, "x", ("int8", "float32")) == "float32"
+    _check_scale(f32, scale, "source")
     if x.dim() < 1:
         raise ValueError("x must have at least one dimension")
     rs = int(x.shape[-1]) if row_stride is None else int(row_stride)
     if rs < 1:
         raise ValueError("row_stride must be at least 1")
-    tab = _channel_table(channels, d.C)
-    onsets = _onsets_tensor(onsets)
-    s = torch.cuda.current_stream(x.device) if stream is None else stream
-    with torch.cuda.stream(s):  # the onsets' copy and the counter's zeroing precede the launch on its stream
-        on = onsets.to(x.device).contiguous()
-        nbad = torch.zeros((1,), dtype=torch.int32, device=x.device) if check else None
-    E = int(on.numel())
-    y = torch.empty((E, d.N), dtype=torch.int8, device=x.device)
-    head = (x.data_ptr(), x.numel(), rs, tab, on.data_ptr() if E else None, E)
-    tail = (y.data_ptr() if E else None, nbad.data_ptr() if nbad is not None else None, x.device.index or 0, s.cuda_stream)
-    if f32:
-        _check(load().net_model_compute_epochs_f32(*head, scale, *tail), "net_model_compute_epochs_f32")
-    else:
-        _check(load().net_model_compute_epochs(*head, *tail), "net_model_compute_epochs")
-    if nbad is not None and E:
-        s.synchronize()
-        bad = int(nbad.item())
-        if bad:
-            raise ValueError(f"{bad} of {E} onsets lie outside the source (their logit rows are zero)")
-    return y
+    return _forward_onsets("net_model_compute_epochs", x, (x.numel(), rs, _channel_table(channels, d.C)), onsets,
+                           scale, (), stream, check, "source")
 
 
 def forward_crop_torch(x, t0: int, channels=None, scale: Optional[float] = None, stream=None):
@@ -680,8 +647,7 @@ def forward_crop_torch(x, t0: int, channels=None, scale: Optional[float] = None,
     t0 .. t0 + T - 1 of the rows ``channels`` (C row indices < R; default 0 .. C-1), through
     forward_epochs_torch: row_stride = Tf, onsets[b] = b R Tf + t0, built on the device.  Returns
     the logits [B][N]."""
-    import torch
-
+    torch = _torch()
     d = _dims()
     if not hasattr(x, "dim") or x.dim() != 3:
         raise ValueError("x must be a batch [B][R][Tf]")
@@ -693,7 +659,7 @@ def forward_crop_torch(x, t0: int, channels=None, scale: Optional[float] = None,
         raise ValueError(f"channels must be {d.C} row indices below R = {R}")
     if not x.is_cuda:
         raise ValueError("x must be a device tensor")
-    s = torch.cuda.current_stream(x.device) if stream is None else stream
+    s, _ = _launch(x, stream)
     with torch.cuda.stream(s):
         onsets = torch.arange(B, dtype=torch.int64, device=x.device) * (R * Tf) + t0
     # every onset is in range by the checks above: no counter, no host sync
@@ -705,47 +671,34 @@ def quantize_input_torch(x, scale: float, stream=None):
     [B][C][T] (the reference's input.npz layout); returns the batched int8 layout [B][stride]
     (stride = C*T rounded up to 16, each trial [T][C]) that forward_torch consumes.  Semantics of
     the reference's quantize_to_int (functional.py:308-334) in the input's precision."""
-    import torch
-
-    if not x.is_cuda or not x.is_contiguous() or x.dim() != 3 or x.dtype not in (torch.float32, torch.float64):
-        raise ValueError("x must be a contiguous float32/float64 device tensor [B][C][T]")
+    dt = _check_tensor(x, "x", ("float32", "float64"), ("B", "C", "T"))
     B, C, T = x.shape
-    stride = (C * T + 15) // 16 * 16
-    y = torch.empty((B, stride), dtype=torch.int8, device=x.device)
-    s = torch.cuda.current_stream(x.device) if stream is None else stream
-    fn = load().net_quantize_input_f32 if x.dtype == torch.float32 else load().net_quantize_input_f64
-    _check(fn(x.data_ptr(), y.data_ptr(), B, C, T, scale, x.device.index or 0, s.cuda_stream), "net_quantize_input")
+    y = _torch().empty((B, _packed_stride(C, T)), dtype=_torch().int8, device=x.device)
+    s, dev = _launch(x, stream)
+    fn = load().net_quantize_input_f32 if dt == "float32" else load().net_quantize_input_f64
+    _check(fn(x.data_ptr(), y.data_ptr(), B, C, T, scale, dev, s.cuda_stream), "net_quantize_input")
     return y
 
 
 def argmax_torch(logits, stream=None):
     """Class per trial (net_argmax_batch): logits is a CUDA/HIP int8 tensor [B][N]; returns an int32
     tensor [B] holding the first maximal index of each row (torch.max(dim=1)'s rule)."""
-    import torch
-
-    if logits.dtype != torch.int8 or not logits.is_cuda or not logits.is_contiguous() or logits.dim() != 2:
-        raise ValueError("logits must be a contiguous int8 device tensor [B][N]")
+    _check_tensor(logits, "logits", ("int8",), ("B", "N"))
     B, N = logits.shape
-    out = torch.empty((B,), dtype=torch.int32, device=logits.device)
-    s = torch.cuda.current_stream(logits.device) if stream is None else stream
-    _check(load().net_argmax_batch(logits.data_ptr(), out.data_ptr(), B, N, logits.device.index or 0, s.cuda_stream),
-           "net_argmax_batch")
+    out = _torch().empty((B,), dtype=_torch().int32, device=logits.device)
+    s, dev = _launch(logits, stream)
+    _check(load().net_argmax_batch(logits.data_ptr(), out.data_ptr(), B, N, dev, s.cuda_stream), "net_argmax_batch")
     return out
 
 
 def pack_trials_torch(x, stream=None):
     """net_pack_trials_i8: x is a CUDA/HIP int8 tensor [B][C][T] (channel-major); returns the
     batched layout [B][stride] (each trial [T][C], pad zero) that forward_torch consumes."""
-    import torch
-
-    if x.dtype != torch.int8 or not x.is_cuda or not x.is_contiguous() or x.dim() != 3:
-        raise ValueError("x must be a contiguous int8 device tensor [B][C][T]")
+    _check_tensor(x, "x", ("int8",), ("B", "C", "T"))
     B, C, T = x.shape
-    stride = (C * T + 15) // 16 * 16
-    y = torch.empty((B, stride), dtype=torch.int8, device=x.device)
-    s = torch.cuda.current_stream(x.device) if stream is None else stream
-    _check(load().net_pack_trials_i8(x.data_ptr(), y.data_ptr(), B, C, T, x.device.index or 0, s.cuda_stream),
-           "net_pack_trials_i8")
+    y = _torch().empty((B, _packed_stride(C, T)), dtype=_torch().int8, device=x.device)
+    s, dev = _launch(x, stream)
+    _check(load().net_pack_trials_i8(x.data_ptr(), y.data_ptr(), B, C, T, dev, s.cuda_stream), "net_pack_trials_i8")
     return y
 
 
@@ -755,12 +708,7 @@ def check_trials(x, channel_major: bool, require_contiguous: bool = True) -> Non
     batch of another element type (e.g. int64 from rng.integers) or with strides would otherwise
     run and its bytes be read as int8 trials.  ``require_contiguous=False``: callers that copy the
     batch contiguously themselves before it reaches a pointer (shard.forward_devices)."""
-    dt = str(getattr(x, "dtype", ""))
-    if dt not in ("int8", "torch.int8"):
-        raise ValueError(f"trials must be int8, got {dt or type(x).__name__}")
-    contiguous = x.is_contiguous() if hasattr(x, "is_contiguous") else bool(x.flags["C_CONTIGUOUS"])
-    if require_contiguous and not contiguous:
-        raise ValueError("trials must be C-contiguous")
+    _check_tensor(x, "trials", ("int8",), device=False, contiguous=require_contiguous)
     check_trial_shape(tuple(x.shape), channel_major)
 
 

@@ -28,6 +28,72 @@ def test_header_symbols_exported():
     assert set(names) == set(lib.EXPORTED_SYMBOLS)
 
 
+_C_IMAGE = {"size_t": ctypes.c_size_t, "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
+            "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def header_prototypes():
+    """{name: (restype, argtypes)} of every function include/mibminet.h declares, each C type as
+    its ctypes image: any pointer c_void_p (a returned ``const char*`` c_char_p), the scalars as
+    _C_IMAGE, a void return None and ``(void)`` no arguments."""
+    text = open(os.path.join(ROOT, "include", "mibminet.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    text = re.sub(r"typedef\s+struct\s*\{.*?\}\s*\w+\s*;", "", text, flags=re.S)  # net_arrays_t's fields are no functions
+
+    def image(ctype, returned=False):
+        ctype = re.sub(r"\bconst\b", "", ctype).replace(" ", "")
+        if ctype.endswith("*"):
+            return ctypes.c_char_p if returned and ctype == "char*" else ctypes.c_void_p
+        return None if returned and ctype == "void" else _C_IMAGE[ctype]
+
+    protos = {}
+    for ret, name, args in re.findall(r"^([\w \t\*]+?)\b(\w+)\s*\(([^()]*)\)\s*;", text, flags=re.M):
+        assert name not in protos, name
+        args = [] if args.strip() == "void" else [a.strip() for a in args.split(",")]
+        # an argument is "type name": drop the name, keep the stars that belong to the type
+        protos[name] = (image(ret, True), [image(re.sub(r"\w+$", "", a)) for a in args])
+    return protos
+
+
+def test_prototype_table_matches_header():
+    """lib.PROTOTYPES gives every function the header declares, and no other net_* function, the
+    ctypes image of its declaration, in the header's order, and load() has bound exactly that."""
+    protos = header_prototypes()
+    assert sorted(protos) == declared_functions() and len(protos) >= 42
+    assert list(lib.EXPORTED_SYMBOLS) == list(protos)
+    L = lib.load()
+    for name, (ret, args) in protos.items():
+        assert lib.prototype(name) == (ret, args), name
+        fn = getattr(L, name)
+        assert fn.restype is ret and list(fn.argtypes) == args, name
+    hooks = set(lib.PROTOTYPES) - set(protos)
+    assert hooks and all(n.startswith("mibminet_test_") for n in hooks)
+    for name in hooks:
+        fn = getattr(L, name)
+        assert (fn.restype, list(fn.argtypes)) == lib.prototype(name), name
+
+
+def test_torch_entries_refuse_what_is_no_tensor():
+    """Every torch entry answers an argument that is no tensor at all (None, a list, a NumPy array
+    where a device tensor is due) with ValueError, before it takes a pointer."""
+    lib.params_load(ParamSet.synthetic(seed=5))
+    rec = np.zeros((22, 2000), np.int8)
+    for bad in (None, [[0] * 1125] * 22, "x", 3, rec):
+        for call in (lib.forward_torch, lib.forward_ct_torch, lambda x: lib.forward_f32_torch(x, 1.0),
+                     lambda x: lib.quantize_input_torch(x, 1.0), lib.argmax_torch, lib.pack_trials_torch,
+                     lambda x: lib.forward_windows_torch(x, 8), lambda x: lib.forward_windows_f32_torch(x, 8, 1.0),
+                     lambda x: lib.forward_windows_at_torch(x, [0]), lambda x: lib.forward_windows_multi_torch([x], 8),
+                     lambda x: lib.forward_epochs_torch(x, [0]), lambda x: lib.forward_crop_torch(x, 0)):
+            with pytest.raises(ValueError):
+                call(bad)
+        if bad is not rec:
+            with pytest.raises(ValueError):
+                lib.check_trials(bad, True)
+    lib.check_trials(np.zeros((3, 22, 1125), np.int8), True)  # NumPy batches stay welcome here
+    lib.params_unload()
+
+
 def test_section_8b_signature():
     """SURVEY §8(b)'s batched entry, int f(const int8_t* x /*[B][C][T]*/, int8_t* y /*[B][N]*/,
     size_t B, int device), exists with exactly those argument types (channel-major trials), and

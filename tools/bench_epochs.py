@@ -13,14 +13,7 @@ All logits of (a) are compared with (c).  One JSON line per case goes to
                                [--reps 7] [--warmup 2] [--variant canonical|plain_bn]
                                [--out-dir profiles]
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mi-bminet_amd"))
+from bench_common import main, medians, min_max, time_alternating
 
 P19 = [0, 2, 4, 8, 10, 12, 14, 21, 23, 29, 31, 33, 35, 37, 40, 41, 47, 54, 61]  # 19 of 64 rows
 CASES = {  # name: (kind, C, T, N, rows of the source, float32)
@@ -81,28 +74,16 @@ def run_case(name, E, reps, warmup, variant, seed=2026):
     ya, yc = a(), c()
     mismatches = int((ya != yc).any(dim=1).sum().item())
     fns = {"a": a, "b": b, "c": c}
-    for _ in range(warmup):
-        for f in fns.values():
-            f()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in fns}
-    for _ in range(reps):
-        for k, f in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            f()
-            e1.record()
-            e1.synchronize()
-            ms[k].append(e0.elapsed_time(e1))
-    med = {k: statistics.median(v) for k, v in ms.items()}
+    ms = time_alternating(fns, reps, warmup)
+    med = medians(ms)
     esz = 4 if f32 else 1
     return {
         "name": name, "kind": kind, "C": C, "T": T, "N": N, "source_rows": R, "float32": f32, "epochs": E,
         "variant": variant, "path": lib.params_info()["path"], "reps": reps, "warmup": warmup,
         "ms_epochs": round(med["a"], 4), "ms_gather_forward": round(med["b"], 4), "ms_forward": round(med["c"], 4),
-        "ms_epochs_min_max": [round(min(ms["a"]), 4), round(max(ms["a"]), 4)],
-        "ms_gather_forward_min_max": [round(min(ms["b"]), 4), round(max(ms["b"]), 4)],
-        "ms_forward_min_max": [round(min(ms["c"]), 4), round(max(ms["c"]), 4)],
+        "ms_epochs_min_max": min_max(ms["a"]),
+        "ms_gather_forward_min_max": min_max(ms["b"]),
+        "ms_forward_min_max": min_max(ms["c"]),
         "epochs_over_gather_forward": round(med["a"] / med["b"], 4), "epochs_over_forward": round(med["a"] / med["c"], 4),
         "epochs_per_s": round(E / med["a"] * 1e3),
         "source_bytes": x.numel() * esz, "materialised_bytes": E * C * T * esz,
@@ -110,37 +91,5 @@ def run_case(name, E, reps, warmup, variant, seed=2026):
     }
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--cases", default=",".join(CASES))
-    ap.add_argument("--epochs", type=int, default=65536)
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--variant", default="canonical", choices=("canonical", "plain_bn"),
-                    help="plain_bn: a set without REORDER_BN (the plain-BN kernels); the file name then carries it")
-    ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
-    args = ap.parse_args()
-    names = [n for n in args.cases.split(",") if n]
-    for n in names:
-        if n not in CASES:
-            ap.error(f"unknown case {n} (known: {', '.join(CASES)})")
-    import torch
-
-    if not torch.cuda.is_available():
-        sys.exit("bench_epochs.py needs a GPU (there is no CPU path)")
-    os.makedirs(args.out_dir, exist_ok=True)
-    suffix = "" if args.variant == "canonical" else "_" + args.variant
-    bad = 0
-    for n in names:
-        res = run_case(n, args.epochs, args.reps, args.warmup, args.variant)
-        line = json.dumps(res)
-        print(line, flush=True)
-        with open(os.path.join(args.out_dir, f"epochs_{n}{suffix}.json"), "w") as f:
-            f.write(line + "\n")
-        bad += res["mismatched_epochs"]
-        torch.cuda.empty_cache()
-    sys.exit(1 if bad else 0)
-
-
 if __name__ == "__main__":
-    main()
+    main(__doc__, CASES, run_case, "epochs", "epochs", lambda res: res["mismatched_epochs"])

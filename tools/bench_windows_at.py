@@ -18,14 +18,7 @@ this fails.
                                    [--windows 65536] [--reps 7] [--warmup 2]
                                    [--variant canonical|plain_bn] [--out-dir profiles]
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "mi-bminet_amd"))
+from bench_common import main, medians, min_max, time_alternating
 
 CASES = {  # name: (kind, C, T, N, hop, recordings, samples per recording)
     "multi_p64": ("multi", 64, 480, 2, 8, 64, 20000),
@@ -72,25 +65,13 @@ def run_case(name, W, reps, warmup, variant, seed=2026):
         fns["d"] = lambda: lib.forward_windows_torch(x, hop)
     ya = fns["a"]()
     mismatches = {k: int((f() != ya).any(dim=1).sum().item()) for k, f in fns.items() if k != "a"}
-    for _ in range(warmup):
-        for f in fns.values():
-            f()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in fns}
-    for _ in range(reps):
-        for k, f in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            f()
-            e1.record()
-            e1.synchronize()
-            ms[k].append(e0.elapsed_time(e1))
-    med = {k: statistics.median(v) for k, v in ms.items()}
+    ms = time_alternating(fns, reps, warmup)
+    med = medians(ms)
     res = {
         "name": name, "kind": kind, "C": C, "T": T, "N": N, "hop": hop, "recordings": R, "samples": L,
         "windows": int(onsets.numel()), "variant": variant, "path": lib.params_info()["path"], "reps": reps, "warmup": warmup,
         "ms": {k: round(v, 4) for k, v in med.items()},
-        "ms_min_max": {k: [round(min(v), 4), round(max(v), 4)] for k, v in ms.items()},
+        "ms_min_max": {k: min_max(v) for k, v in ms.items()},
         "over_a": {k: round(v / med["a"], 4) for k, v in med.items() if k != "a"},
         "windows_per_s": round(int(onsets.numel()) / med["a"] * 1e3),
         "recording_bytes": C * L, "workspace_bytes": lib.windows_workspace(L),
@@ -105,37 +86,9 @@ def run_case(name, W, reps, warmup, variant, seed=2026):
     return res
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--cases", default=",".join(CASES))
-    ap.add_argument("--windows", type=int, default=65536)
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--variant", default="canonical", choices=("canonical", "plain_bn"),
-                    help="plain_bn: a set without REORDER_BN (the plain-BN kernels); the file name then carries it")
-    ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
-    args = ap.parse_args()
-    names = [n for n in args.cases.split(",") if n]
-    for n in names:
-        if n not in CASES:
-            ap.error(f"unknown case {n} (known: {', '.join(CASES)})")
-    import torch
-
-    if not torch.cuda.is_available():
-        sys.exit("bench_windows_at.py needs a GPU (there is no CPU path)")
-    os.makedirs(args.out_dir, exist_ok=True)
-    suffix = "" if args.variant == "canonical" else "_" + args.variant
-    bad = 0
-    for n in names:
-        res = run_case(n, args.windows, args.reps, args.warmup, args.variant)
-        line = json.dumps(res)
-        print(line, flush=True)
-        with open(os.path.join(args.out_dir, f"windows_at_{n}{suffix}.json"), "w") as f:
-            f.write(line + "\n")
-        bad += sum(res["mismatched_rows"].values()) + (0 if res.get("gate_ok", True) else 1)
-        torch.cuda.empty_cache()
-    sys.exit(1 if bad else 0)
+def failures(res):
+    return sum(res["mismatched_rows"].values()) + (0 if res.get("gate_ok", True) else 1)
 
 
 if __name__ == "__main__":
-    main()
+    main(__doc__, CASES, run_case, "windows", "windows_at", failures)
