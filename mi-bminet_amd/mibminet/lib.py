@@ -26,9 +26,10 @@ NET_ERR_BLOB = -4
 NET_ERR_RANGE = -5
 NET_ERR_HIP = -100
 
-# Every C function the binding calls, as "return (arguments)" in the words of _CTYPES: the net_*
-# entries in the order of include/mibminet.h (tests/test_lib_cpu.py holds each to its declaration
-# there), then the hooks of include/mibminet_testing.h that this module calls.
+# Every C function the library declares, as "return (arguments)" in the words of _CTYPES: the net_*
+# entries in the order of include/mibminet.h, then every hook of include/mibminet_testing.h in that
+# header's order.  tests/test_lib_cpu.py holds each to its declaration in its header, so tests and
+# tools call the hooks through load() or the wrappers below and bind nothing themselves.
 _CTYPES = {"void": None, "int": ctypes.c_int, "size_t": ctypes.c_size_t, "int32_t": ctypes.c_int32,
            "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
            "ptr": ctypes.c_void_p, "str": ctypes.c_char_p}
@@ -75,11 +76,19 @@ PROTOTYPES = {
     "net_launch_info_ct": "int (size_t, int, ptr)",
     "net_error_string": "str (int)",
     "net_version": "int ()",
+    "mibminet_test_reciprocal": "int (int32_t, int64_t, int32_t, int32_t, ptr, ptr)",
+    "mibminet_test_floor_form": "int (int32_t, int64_t, int64_t, ptr, ptr, ptr)",
+    "mibminet_test_quantize_f32": "int (ptr, ptr, size_t, float, int, ptr)",
+    "mibminet_test_multi_order": "int (int, ptr, int, ptr, size_t)",
+    "mibminet_test_upload_stats": "int (ptr, ptr)",
+    "mibminet_test_device_images": "int (int)",
     "mibminet_test_xdiv_host": "int (ptr, size_t, int32_t, ptr)",
     "mibminet_test_xdiv_gpu": "int (int32_t, int64_t, int64_t, ptr, int)",
     "mibminet_test_pool_consts": "int (int32_t, int32_t, ptr, ptr)",
     "mibminet_test_params_xr": "int ()",
     "mibminet_test_force_general": "int (int)",
+    "mibminet_test_image_digest": "int (ptr)",
+    "mibminet_test_image_copy": "int (int, ptr, size_t, ptr)",
     "mibminet_test_folded_filters": "int (ptr)",
 }
 EXPORTED_SYMBOLS = tuple(n for n in PROTOTYPES if n.startswith("net_"))
@@ -109,6 +118,16 @@ def prototype(name: str):
     return _CTYPES[ret.strip()], [_CTYPES[a.strip()] for a in args.split(",") if a.strip()]
 
 
+def bind(L: ctypes.CDLL, names=None) -> ctypes.CDLL:
+    """Gives the functions ``names`` (default: all of PROTOTYPES) their restype and argtypes on
+    ``L``, a loaded build of the library.  load() binds everything on the one the package uses; the
+    tools that time other builds side by side, some of an older revision, name what they call."""
+    for name in PROTOTYPES if names is None else names:
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = prototype(name)
+    return L
+
+
 def load(path: str = LIB_PATH) -> ctypes.CDLL:
     """Load libmibminet.so (raises OSError — loudly — if it is missing or fails to load)."""
     global _lib
@@ -117,12 +136,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise OSError(f"libmibminet.so not found at {path}: build it with `make -C mi-bminet_amd`"
                       " (there is no CPU fallback)")
-    L = ctypes.CDLL(path)
-    for name in PROTOTYPES:
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = prototype(name)
-    _lib = L
-    return L
+    _lib = bind(ctypes.CDLL(path))
+    return _lib
 
 
 def _check(rc: int, what: str) -> None:
@@ -295,6 +310,43 @@ def xdiv_gpu_mismatches(d: int, e0: int, count: int, device: int = 0) -> int:
     n = ctypes.c_int64(0)
     _check(load().mibminet_test_xdiv_gpu(int(d), int(e0), int(count), ctypes.byref(n), device), "mibminet_test_xdiv_gpu")
     return int(n.value)
+
+
+def image_digest() -> int:
+    """Test hook (mibminet_test_image_digest): FNV-1a digest of the loaded set's device parameter image."""
+    v = ctypes.c_uint64(0)
+    _check(load().mibminet_test_image_digest(ctypes.byref(v)), "mibminet_test_image_digest")
+    return v.value
+
+
+def upload_stats() -> tuple:
+    """Test hook (mibminet_test_upload_stats): (parameter-image uploads so far, how many of them
+    happened while the multi-device entries were enqueueing shards)."""
+    a, b = ctypes.c_int64(0), ctypes.c_int64(0)
+    _check(load().mibminet_test_upload_stats(ctypes.byref(a), ctypes.byref(b)), "mibminet_test_upload_stats")
+    return a.value, b.value
+
+
+def device_images(device: int = 0) -> int:
+    """Test hook (mibminet_test_device_images): parameter-image copies resident on ``device``."""
+    n = load().mibminet_test_device_images(device)
+    if n < 0:
+        raise NetError(n, "mibminet_test_device_images")
+    return n
+
+
+def quantize_f32_flat(x_ptr: int, q_ptr: int, n: int, scale: float, device: int = 0, stream: Optional[int] = None) -> None:
+    """Test hook (mibminet_test_quantize_f32): the fused float entries' in-kernel quantiser on a flat
+    device array, q[i] = quantize(x[i]) for i < n (x_ptr float32, q_ptr int8), enqueued on ``stream``."""
+    _check(load().mibminet_test_quantize_f32(x_ptr, q_ptr, n, scale, device, stream), "mibminet_test_quantize_f32")
+
+
+def pool_consts(off: int, layer: int) -> tuple:
+    """Test hook (mibminet_test_pool_consts): (threshold, offset term) of the REORDER_BN pooling of
+    ``layer`` (2 or 4) for offset ``off``, as the kernels use them."""
+    thr, offm = ctypes.c_int32(0), ctypes.c_int32(0)
+    _check(load().mibminet_test_pool_consts(off, layer, ctypes.byref(thr), ctypes.byref(offm)), "mibminet_test_pool_consts")
+    return thr.value, offm.value
 
 
 def launch_info(B: int, device: int = 0, channel_major: bool = False) -> dict:

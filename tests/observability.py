@@ -22,6 +22,7 @@ from numpy.lib.stride_tricks import sliding_window_view
 
 from mibminet.params import L2_TAPS, L3_TAPS, ParamSet, dot_ranges
 from oracle import golden_np as G
+from support import tile_sweep
 
 DELTAS = (+1, -1)
 
@@ -394,7 +395,7 @@ class Case:
         return self.name
 
 
-SWEEP_RESIDUES = (0, 1, 16, 17)  # of test_gpu_general._tile_sweep(): layer 2's tail tiles
+SWEEP_RESIDUES = (0, 1, 16, 17)  # of support.tile_sweep(): layer 2's tail tiles
 COMPILED = ((22, 1125, 4), (64, 1000, 4), (64, 480, 4))
 VARIANT_GEOMETRIES = ((5, 77, 16), (22, 1125, 4), (64, 480, 4))
 VARIANTS = {"plain": dict(reorder_bn=False), "balanced": dict(clip_balanced=True), "int4": dict(weight_bits=4),
@@ -415,14 +416,12 @@ _SEED = {"5x77": 4, "5x77-plain": 4, "5x77-balanced": 4, "5x77-exact": 4, "5x77-
 
 
 def _cases():
-    from test_gpu_general import _tile_sweep
-
     def case(name, C, T, N, **kw):
         return Case(name, C, T, N, _B.get(name, 2048), seed=_SEED.get(name, 0), **kw)
 
     out = [case(f"{C}x{T}", C, T, N)
            for C, T, N in ((1, 64, 1), (5, 77, 16), (17, 130, 3), (33, 200, 2), (64, 136, 16)) + COMPILED]
-    sweep = _tile_sweep()
+    sweep = tile_sweep()
     for r in SWEEP_RESIDUES:
         C, T, N, kw = sweep[r]
         out.append(case(f"sweep{r}-{C}x{T}", C, T, N, **kw))

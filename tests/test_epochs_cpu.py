@@ -9,18 +9,11 @@ import pytest
 
 from mibminet import lib
 from mibminet.params import ParamSet
+from support import loaded  # noqa: F401 (a fixture)
 
 INV, NOP, RNG, UNS, OK = (lib.NET_ERR_INVALID, lib.NET_ERR_NO_PARAMS, lib.NET_ERR_RANGE, lib.NET_ERR_UNSUPPORTED,
                           lib.NET_OK)
 C, T = 22, 1125
-
-
-@pytest.fixture
-def loaded():
-    ps = ParamSet.synthetic(seed=5)  # 22 x 1125, N = 4
-    lib.params_load(ps)
-    yield ps
-    lib.params_unload()
 
 
 @pytest.fixture

@@ -21,9 +21,7 @@ A = 128 * 128
 
 
 def _floor_form(fac, emax, vmax):
-    L = lib.load()
-    fn = L.mibminet_test_floor_form
-    fn.argtypes = [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    fn = lib.load().mibminet_test_floor_form
     m, r, c = ctypes.c_int32(), ctypes.c_float(), ctypes.c_float()
     rc = fn(fac, emax, vmax, ctypes.addressof(m), ctypes.addressof(r), ctypes.addressof(c))
     return rc, m.value, np.float32(r.value), np.float32(c.value)

@@ -8,7 +8,6 @@ batched entry (forward_ct_torch) on the same materialised epochs is a second wit
 uniform int8 from seeded generators.
 """
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -16,24 +15,10 @@ import pytest
 import oracle
 from mibminet import lib
 from mibminet.params import ParamSet, pack_trials
-from test_gpu_general import _tile_sweep
-from test_gpu_windows import _at_offset
-from test_gpu_windows_at import _BAD
+from support import _BAD, NTH, at_offset, epochs_of, source, tile_sweep
+from support import want as _want
 
 pytestmark = pytest.mark.gpu
-NTH = min(16, os.cpu_count() or 1)
-
-
-def _materialise(src, onsets, channels, row_stride, T):
-    """The epochs [E][C][T] of the flat view of `src`."""
-    on = np.asarray(onsets, np.int64)
-    ch = np.asarray(channels, np.int64)
-    idx = on[:, None, None] + ch[None, :, None] * row_stride + np.arange(T, dtype=np.int64)[None, None, :]
-    return np.ascontiguousarray(src.reshape(-1)[idx])
-
-
-def _want(ps, epochs):
-    return oracle.COracle(ps).batch(pack_trials(epochs), nthreads=NTH)
 
 
 def _check_epochs(ps, src, onsets, channels, offset=0, witness=True, row_stride=None):
@@ -45,9 +30,9 @@ def _check_epochs(ps, src, onsets, channels, offset=0, witness=True, row_stride=
     d = ps.dims
     rs = src.shape[-1] if row_stride is None else row_stride
     ch = list(range(d.C)) if channels is None else channels
-    epochs = _materialise(src, onsets, ch, rs, d.T)
+    epochs = epochs_of(src, onsets, ch, rs, d.T)
     want = _want(ps, epochs)
-    x = _at_offset(torch, src, offset)
+    x = at_offset(torch, src, offset)
     got = lib.forward_epochs_torch(x, onsets, channels=channels, row_stride=row_stride).cpu().numpy()
     assert got.shape == (len(onsets), d.N)
     np.testing.assert_array_equal(got, want, err_msg=f"epochs vs oracle, offset {offset}")
@@ -55,10 +40,6 @@ def _check_epochs(ps, src, onsets, channels, offset=0, witness=True, row_stride=
         full = lib.forward_ct_torch(torch.from_numpy(epochs).cuda()).cpu().numpy()
         np.testing.assert_array_equal(full, want, err_msg="forward_ct_torch vs oracle")
     return want
-
-
-def _source(shape, seed):
-    return np.random.default_rng(seed).integers(-128, 128, size=shape).astype(np.int8)
 
 
 _CH19 = [23, 0, 7, 22, 3, 3, 15, 1, 19, 11, 5, 21, 2, 9, 14, 8, 0, 17, 12]  # non-monotonic, duplicates, rows 0 and 23
@@ -73,7 +54,7 @@ def test_alignment(L, gpu):
     lib.params_load(ps)
     assert lib.params_info()["path"] == "general"
     assert len(_CH19) == 19 and L % 4 in (0, 1, 3)
-    src = _source((24, L), L)
+    src = source((24, L), L)
     last = L - 480  # n_elems - span = 24 L - (23 L + 480)
     rng = np.random.default_rng(L + 1)
     onsets = [0, last, last, 0] + [int(v) for v in rng.permutation(np.arange(1, 45))]  # 44 consecutive: every residue
@@ -97,21 +78,21 @@ def test_partial_last_block(C, T, gpu):
     L = 3 * (T + gap) + T
     onsets = [2 * (T + gap), 0, L - T, T + gap]
     channels = [R - 1] + list(range(C - 1))  # the last row: epoch L - T ends at the last element
-    src = _source((R, L), T)
+    src = source((R, L), T)
     for o in onsets[:2] + onsets[3:]:
         src[:, o + T: o + T + gap] = np.where(np.arange(gap) % 2 == 0, -128, 127).astype(np.int8)
     for offset in (0, 3):
         _check_epochs(ps, src, onsets, channels, offset=offset, witness=offset == 0)
     # float32: the same layout with non-finite values after the epochs
     g = torch.Generator(device="cuda").manual_seed(T)
-    xf = _at_offset(torch, np.zeros((R, L), np.float32), 4)
+    xf = at_offset(torch, np.zeros((R, L), np.float32), 4)
     xf.copy_(torch.randn((R, L), dtype=torch.float32, device="cuda", generator=g) * 1.3)
     junk = torch.tensor([float("nan"), float("inf"), -float("inf"), float("nan")] * (gap // 4), device="cuda")
     for o in onsets[:2] + onsets[3:]:
         xf[:, o + T: o + T + gap] = junk
     q = lib.quantize_input_torch(xf[None].contiguous(), 3.0)  # [1][stride], the trial [L][R]
     q_rl = np.ascontiguousarray(q.cpu().numpy()[0, : L * R].reshape(L, R).T)
-    want = _want(ps, _materialise(q_rl, onsets, channels, L, T))
+    want = _want(ps, epochs_of(q_rl, onsets, channels, L, T))
     got = lib.forward_epochs_torch(xf, onsets, channels=channels, scale=3.0).cpu().numpy()
     np.testing.assert_array_equal(got, want)
 
@@ -126,7 +107,7 @@ def test_float32(offset, gpu):
     lib.params_load(ps)
     L = 611
     g = torch.Generator(device="cuda").manual_seed(offset + 7)
-    xf = _at_offset(torch, np.zeros((24, L), np.float32), offset)
+    xf = at_offset(torch, np.zeros((24, L), np.float32), offset)
     assert xf.data_ptr() % 8 == offset
     xf.copy_(torch.randn((24, L), dtype=torch.float32, device="cuda", generator=g) * 1.3)
     plant = torch.tensor([float("nan"), float("inf"), -float("inf"), 9.0, -9.0, 0.0, -0.0, 3.0, -3.0], device="cuda")
@@ -136,15 +117,15 @@ def test_float32(offset, gpu):
     q = lib.quantize_input_torch(xf[None].contiguous(), 3.0)
     q_rl = np.ascontiguousarray(q.cpu().numpy()[0, : L * 24].reshape(L, 24).T)
     onsets = [0, L - 480, 5, 77, 5, 130, 16, 1]
-    want = _want(ps, _materialise(q_rl, onsets, _CH19, L, 480))
+    want = _want(ps, epochs_of(q_rl, onsets, _CH19, L, 480))
     got = lib.forward_epochs_torch(xf, onsets, channels=_CH19, scale=3.0).cpu().numpy()
     np.testing.assert_array_equal(got, want)
-    full = lib.forward_ct_torch(torch.from_numpy(_materialise(q_rl, onsets, _CH19, L, 480)).cuda()).cpu().numpy()
+    full = lib.forward_ct_torch(torch.from_numpy(epochs_of(q_rl, onsets, _CH19, L, 480)).cuda()).cpu().numpy()
     np.testing.assert_array_equal(full, want)
 
 
 def _geometries():
-    sweep = _tile_sweep()
+    sweep = tile_sweep()
     Ts = [64, 65] + [sweep[r][1] for r in (0, 1, 16, 17, 5, 9, 20, 31)] + [64, 65]
     Cs = [1, 16, 17, 33, 64, 1, 16, 17, 33, 64, 64, 33]
     kws = [{}, {}] + [sweep[r][3] for r in (0, 1, 16, 17, 5, 9, 20, 31)] + [{}, {}]
@@ -169,14 +150,14 @@ def test_geometries(C, T, N, kw, gpu):
     ps = ParamSet.synthetic(seed=C * T + N, C=C, T=T, N=N, **kw)
     lib.params_load(ps)
     R, L = C + 3, T + 37
-    _check_epochs(ps, _source((R, L), C + T), [37, 0, 13, 13, 7], _channels(C, R, T), offset=1)
+    _check_epochs(ps, source((R, L), C + T), [37, 0, 13, 13, 7], _channels(C, R, T), offset=1)
 
 
 def test_longest_trial(gpu):
     ps = ParamSet.synthetic(seed=4096, C=64, T=4096, N=5)
     lib.params_load(ps)
     R, L = 66, 4096 + 50
-    _check_epochs(ps, _source((R, L), 4096), [50, 0, 3, 17, 17, 32, 49, 1], _channels(64, R, 1), offset=3)
+    _check_epochs(ps, source((R, L), 4096), [50, 0, 3, 17, 17, 32, 49, 1], _channels(64, R, 1), offset=3)
 
 
 _VARIANTS = [dict(reorder_bn=False), dict(clip_balanced=True), dict(weight_bits=4), dict(extreme=3)]
@@ -195,7 +176,7 @@ def test_variants(kw, gpu):
         assert lib.params_info()["exact_division"]
     R, L = 64, 640
     onsets = [160, 0, 1, 159, 80, 80, 33, 15, 16, 17, 31]
-    _check_epochs(ps, _source((R, L), C + len(kw)), onsets, _channels(C, R, 5), offset=2)
+    _check_epochs(ps, source((R, L), C + len(kw)), onsets, _channels(C, R, 5), offset=2)
 
 
 @pytest.mark.parametrize("C,T", [(22, 1125), (64, 1000), (64, 480)])
@@ -209,7 +190,7 @@ def test_compiled_geometries(C, T, gpu):
     info = lib.params_info()
     assert info["path"] == "float"
     R, L = C + 2, T + 99
-    _check_epochs(ps, _source((R, L), C * T), [99, 0, 50, 7, 7, 98], _channels(C, R, 3), offset=1)
+    _check_epochs(ps, source((R, L), C * T), [99, 0, 50, 7, 7, 98], _channels(C, R, 3), offset=1)
     assert lib.params_info() == info
     xp = pack_trials(np.random.default_rng(T).integers(-128, 128, size=(41, C, T)))
     got = lib.forward_torch(torch.from_numpy(xp).cuda()).cpu().numpy()
@@ -223,8 +204,8 @@ def test_identity(gpu):
     ps = ParamSet.synthetic(seed=31, C=19, T=480, N=3)
     lib.params_load(ps)
     B = 41
-    xb = _source((B, 19, 480), 31)
-    x = _at_offset(torch, xb, 1)
+    xb = source((B, 19, 480), 31)
+    x = at_offset(torch, xb, 1)
     want = lib.forward_ct_torch(x)
     got = lib.forward_epochs_torch(x, torch.arange(B, dtype=torch.int64) * (19 * 480), row_stride=480)
     assert bool((got == want).all())
@@ -238,7 +219,7 @@ def test_forward_crop(t0, gpu):
     ps = ParamSet.synthetic(seed=33, C=19, T=480, N=3)
     lib.params_load(ps)
     ch = [63, 0, 31, 8, 9, 10, 40, 41, 42, 20, 21, 22, 50, 51, 52, 60, 61, 62, 5]
-    xb = _source((37, 64, 640), 33)
+    xb = source((37, 64, 640), 33)
     want = _want(ps, np.ascontiguousarray(xb[:, ch, t0: t0 + 480]))
     got = lib.forward_crop_torch(torch.from_numpy(xb).cuda(), t0, channels=ch).cpu().numpy()
     np.testing.assert_array_equal(got, want)
@@ -260,7 +241,7 @@ def test_persistent_loop(gpu):
     lib.params_load(ps)
     grid = 2 * torch.cuda.get_device_properties(0).multi_processor_count  # two workgroups per CU
     E = 3 * grid + 1
-    src = _source((6, 64 + E), 41)
+    src = source((6, 64 + E), 41)
     onsets = [int(v) for v in np.random.default_rng(41).permutation(E)]
     _check_epochs(ps, src, onsets, [5, 0, 3, 3], offset=3, witness=False)
 
@@ -280,7 +261,7 @@ def test_persistent_loop_with_invalid_onsets(gpu):
     grid = 2 * torch.cuda.get_device_properties(0).multi_processor_count  # two workgroups per CU
     E = 3 * grid + 1
     L = 64 + E
-    src = _source((6, L), 41)
+    src = source((6, L), 41)
     last = 6 * L - (5 * L + T)  # n_elems - span
     assert last == E
     onsets = [int(v) for v in np.random.default_rng(41).permutation(E)]
@@ -294,7 +275,7 @@ def test_persistent_loop_with_invalid_onsets(gpu):
     # finishes) and on one in between
     assert bad[0] < grid and bad[-1] + grid >= E and any(grid <= i < E - grid for i in bad)
     ok = [i for i in range(E) if i % 7]
-    want = _want(ps, _materialise(src, [onsets[i] for i in ok], ch, L, T))
+    want = _want(ps, epochs_of(src, [onsets[i] for i in ok], ch, L, T))
     assert want.any(axis=1).all()  # no valid row is zero itself
     on = torch.tensor(onsets, dtype=torch.int64, device="cuda")
     tab = (ctypes.c_int32 * 4)(*ch)
@@ -312,13 +293,13 @@ def test_persistent_loop_with_invalid_onsets(gpu):
         assert not rows[bad].any()
         return rows[ok]
 
-    np.testing.assert_array_equal(run(_at_offset(torch, src, 3)), want)
+    np.testing.assert_array_equal(run(at_offset(torch, src, 3)), want)
     # float32, scale 3: the samples the two-pass quantiser makes of it (-128 becomes -127)
-    xf = _at_offset(torch, src.astype(np.float32) * np.float32(3.0 / 127.0), 4)
+    xf = at_offset(torch, src.astype(np.float32) * np.float32(3.0 / 127.0), 4)
     q = lib.quantize_input_torch(xf[None].contiguous(), 3.0)  # [1][stride], the trial [L][6]
     q_rl = np.ascontiguousarray(q.cpu().numpy()[0, : L * 6].reshape(L, 6).T)
     assert (np.abs(q_rl.astype(int) - src) <= 1).all()
-    want_f = _want(ps, _materialise(q_rl, [onsets[i] for i in ok], ch, L, T))
+    want_f = _want(ps, epochs_of(q_rl, [onsets[i] for i in ok], ch, L, T))
     np.testing.assert_array_equal(run(xf, 3.0), want_f)
 
 
@@ -330,7 +311,7 @@ def test_invalid_onsets(gpu):
     ps = ParamSet.synthetic(seed=19, C=19, T=480, N=3)
     lib.params_load(ps)
     L = 583
-    src = _source((24, L), 77)
+    src = source((24, L), 77)
     last = L - 480
     bad = {1: -1, 4: last + 1, 5: 2**40, 9: -(2**40), 10: -(2**63), 14: 2**63 - 1, 15: 24 * L}
     onsets = [int(v) for v in np.random.default_rng(5).integers(0, last + 1, size=17)]
@@ -338,8 +319,8 @@ def test_invalid_onsets(gpu):
     for i, o in bad.items():
         onsets[i] = o
     ok = [i for i in range(17) if i not in bad]
-    want = _want(ps, _materialise(src, [onsets[i] for i in ok], _CH19, L, 480))
-    x = _at_offset(torch, src, 2)
+    want = _want(ps, epochs_of(src, [onsets[i] for i in ok], _CH19, L, 480))
+    x = at_offset(torch, src, 2)
     on = torch.tensor(onsets, dtype=torch.int64, device="cuda")
     y = torch.full((17 * 3 + 64,), 0x5A, dtype=torch.int8, device="cuda")
     nb = torch.zeros((3,), dtype=torch.int32, device="cuda")
@@ -371,9 +352,9 @@ def test_graph_capture_and_replay(gpu):
     lib.params_load(ps)
     L = 700
     rng = np.random.default_rng(3)
-    srcs = [_source((24, L), 100 + i) for i in range(3)]
+    srcs = [source((24, L), 100 + i) for i in range(3)]
     onsets = [int(v) for v in rng.integers(0, L - 480 + 1, size=300)]
-    x = _at_offset(torch, srcs[0], 1)
+    x = at_offset(torch, srcs[0], 1)
     on = torch.tensor(onsets, dtype=torch.int64, device="cuda")
     lib.forward_epochs_torch(x, on, channels=_CH19)  # eager: uploads the parameters
     y = torch.zeros((300, 3), dtype=torch.int8, device="cuda")
@@ -392,6 +373,6 @@ def test_graph_capture_and_replay(gpu):
         y.zero_()
         g.replay()
         torch.cuda.synchronize()
-        np.testing.assert_array_equal(y.cpu().numpy(), _want(ps, _materialise(src, onsets, _CH19, L, 480)))
+        np.testing.assert_array_equal(y.cpu().numpy(), _want(ps, epochs_of(src, onsets, _CH19, L, 480)))
     assert int(nb.item()) == 0
     del g

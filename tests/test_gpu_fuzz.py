@@ -2,14 +2,13 @@
 and offsets, both BN branches, both clip modes, int8 and int4 weights), each run on a batch of
 trials with the reference tests' input range (randint(-60, 60), model/testcase.py:53) and the
 full int8 range, compared bit for bit with the C oracle."""
-import os
-
 import numpy as np
 import pytest
 
 import oracle
 from mibminet import lib
 from mibminet.params import ParamSet, pack_trials
+from support import NTH
 
 pytestmark = pytest.mark.gpu
 
@@ -35,7 +34,7 @@ def test_fuzz_vs_oracle(gpu, case):
     lo, hi = (-60, 60) if case["seed"] % 2 else (-128, 128)
     x = pack_trials(rng.integers(lo, hi, size=(B, case["C"], case["T"])))
     got = lib.forward_torch(torch.from_numpy(x).cuda()).cpu().numpy()
-    want = oracle.COracle(ps).batch(x, nthreads=min(16, os.cpu_count() or 1))
+    want = oracle.COracle(ps).batch(x, nthreads=NTH)
     assert np.array_equal(got, want)
 
 
@@ -66,4 +65,4 @@ def test_envelope_edges_vs_oracle(gpu, seed, C, T):
     rng = np.random.default_rng(seed)
     x = pack_trials(rng.integers(-128, 128, size=(128, C, T)))
     got = lib.forward_torch(torch.from_numpy(x).cuda()).cpu().numpy()
-    assert np.array_equal(got, oracle.COracle(ps).batch(x, nthreads=min(16, os.cpu_count() or 1)))
+    assert np.array_equal(got, oracle.COracle(ps).batch(x, nthreads=NTH))

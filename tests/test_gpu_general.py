@@ -10,25 +10,15 @@ and every per-layer entry point.  The compiled geometries are also forced onto t
 kernels (mibminet_test_force_general) so that both kernel families meet the same oracle on the
 same sets.
 """
-import os
-
 import numpy as np
 import pytest
 
 import oracle
 from mibminet import lib
 from mibminet.params import ParamSet, pack_trials
+from support import NTH, at_offset, tile_sweep
 
 pytestmark = pytest.mark.gpu
-NTH = min(16, os.cpu_count() or 1)
-
-
-def _ct(torch, x_ct, offset=0):
-    """[B][C][T] int8 on the device, starting `offset` bytes into its allocation."""
-    B, C, T = x_ct.shape
-    flat = torch.zeros(offset + B * C * T + 64, dtype=torch.int8, device="cuda")
-    flat[offset: offset + B * C * T] = torch.from_numpy(np.ascontiguousarray(x_ct, np.int8).ravel()).cuda()
-    return flat[offset: offset + B * C * T].view(B, C, T)
 
 
 def _check_all_entries(ps, B, seed, offset=1, layers=True):
@@ -44,7 +34,7 @@ def _check_all_entries(ps, B, seed, offset=1, layers=True):
     want = co.batch(xp, nthreads=NTH)
     got = lib.forward_torch(torch.from_numpy(xp).cuda()).cpu().numpy()
     np.testing.assert_array_equal(got, want, err_msg="time-major")
-    got_ct = lib.forward_ct_torch(_ct(torch, x_ct, offset)).cpu().numpy()
+    got_ct = lib.forward_ct_torch(at_offset(torch, x_ct, offset)).cpu().numpy()
     np.testing.assert_array_equal(got_ct, want, err_msg="channel-major")
     # the reference's single-trial entry and its per-layer entries
     x0 = oracle.to_tc_align(x_ct[0], d.C_ALIGN)
@@ -102,27 +92,7 @@ def test_extreme_requant_sets(C, T, gpu):
         assert lib.params_info()["exact_division"]
 
 
-def _tile_sweep():
-    """32 geometries, one per residue of layer 2's column blocks mod 32 (NB2 = ceil(T8 / 4): rest
-    0 = whole 32x32 tiles, 1-16 = one or two 16x16x64 tail tiles, 17-31 = one more full tile),
-    each with 0-4 full tiles, C over 1..64, N over 1..16, T mod 16 and T mod 64 varied, the
-    largest trials past the LDS staging limit (unstaged fragments), and both build variants on
-    some of them."""
-    out = []
-    for rest in range(32):
-        m = max(rest % 4, 1 if rest < 2 else 0)
-        T8 = 4 * (32 * m + rest) - rest % 4
-        T = 8 * T8 + (3 * rest) % 8
-        kw = {}
-        if rest % 5 == 1:
-            kw["reorder_bn"] = False
-        if rest % 7 == 3:
-            kw["clip_balanced"] = True
-        out.append((1 + (7 * rest) % 64, T, 1 + rest % 16, kw))
-    return out
-
-
-@pytest.mark.parametrize("C,T,N,kw", _tile_sweep())
+@pytest.mark.parametrize("C,T,N,kw", tile_sweep())
 def test_layer2_tile_sweep(C, T, N, kw, gpu):
     """Every layer-2 tile residue (full and tail tiles), against the oracle through the batched
     time-major and channel-major entries and the single-trial net_model_compute."""

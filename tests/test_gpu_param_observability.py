@@ -9,8 +9,6 @@ offset exchanged, or a scalar factor off by one changes some logit of some trial
 computes the forward pass, against the C oracle, byte for byte; and a sample of single faults is
 loaded one after the other, each of which must give the faulted set's logits, not the base set's.
 """
-import os
-
 import numpy as np
 import pytest
 
@@ -18,11 +16,9 @@ import oracle
 import param_faults as pf
 from mibminet import lib
 from mibminet.params import pack_trials
-from test_gpu_general import _ct
-from test_gpu_observability import _run_entries
+from support import NTH, at_offset, run_entries
 
 pytestmark = pytest.mark.gpu
-NTH = min(16, os.cpu_count() or 1)
 NAMES = [c.name for c in pf.PCASES]
 _COMPILED = {(C, T) for C, T, _ in pf.COMPILED}
 _COMPILED_NAMES = [c.name for c in pf.PCASES if c.dims[:2] in _COMPILED]
@@ -36,11 +32,11 @@ def _path(case):
 
 @pytest.mark.parametrize("name", NAMES)
 def test_certified_case(name, gpu):
-    """Every forward entry of test_gpu_observability._run_entries on the certified batch.  The
+    """Every forward entry of support.run_entries on the certified batch.  The
     compiled geometries run their compiled kernels here."""
     case = pf.PCASES[NAMES.index(name)]
     try:
-        _run_entries(case, _path(case))
+        run_entries(case, _path(case))
     finally:
         case.drop()
 
@@ -51,7 +47,7 @@ def test_certified_case_forced_general(name, gpu):
     case = pf.PCASES[NAMES.index(name)]
     try:
         lib.force_general(True)
-        _run_entries(case, "general")
+        run_entries(case, "general")
     finally:
         lib.force_general(False)
         case.drop()
@@ -93,7 +89,7 @@ def _differential(case, path):
     faults = _sample(case, xp, base)
     fam = {f: sum(1 for ft, _, _ in faults if ft[1] == f) for f in pf.FAMILIES}
     assert len(faults) >= 40 and all(n >= 4 for n in fam.values()), (len(faults), fam)
-    xd, xc = torch.from_numpy(xp).cuda(), _ct(torch, x, 1)
+    xd, xc = torch.from_numpy(xp).cuda(), at_offset(torch, x, 1)
 
     def check(want, what):
         for entry, got in (("time-major", lib.forward_torch(xd)), ("channel-major", lib.forward_ct_torch(xc))):

@@ -12,6 +12,7 @@ import pytest
 import oracle
 from mibminet import lib
 from mibminet.params import ParamSet
+from support import NTH
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
@@ -38,7 +39,7 @@ def test_batch_repeated_vs_oracle(stress, gpu):
     g = torch.Generator(device="cuda").manual_seed(5)
     x = torch.randint(-128, 128, (B, stride), dtype=torch.int8, device="cuda", generator=g)
     x[:, 22 * 1125:] = 0
-    want = torch.from_numpy(oracle.COracle(ps).batch(x.cpu().numpy(), nthreads=min(16, os.cpu_count() or 1))).cuda()
+    want = torch.from_numpy(oracle.COracle(ps).batch(x.cpu().numpy(), nthreads=NTH)).cuda()
     y = torch.empty((B, 4), dtype=torch.int8, device="cuda")
     bad = []
     for i in range(40):

@@ -2,14 +2,13 @@
 edgeEEGNet (QuantLab/PhysionetMMMI/config_INQ.json: F1 = F2 = 16, D = 1, C = 64, T = 480, N = 4).
 Its 60 pooled layer-2 samples per filter fill half of one 32x32 tile, which the kernel computes
 as a partial tile (Cfg::MT / TB, forward_wg.hpp).  Per layer and batched against the oracle."""
-import os
-
 import numpy as np
 import pytest
 
 import oracle
 from mibminet import lib
 from mibminet.params import ParamSet, pack_trials
+from support import NTH
 
 pytestmark = pytest.mark.gpu
 C, T = 64, 480
@@ -28,7 +27,7 @@ def test_batch_64x480(gpu, rb, cb, stress, wbits, B):
     rng = np.random.default_rng(B)
     x = pack_trials(rng.integers(-128, 128, size=(B, C, T)))
     got = lib.forward_torch(torch.from_numpy(x).cuda()).cpu().numpy()
-    assert np.array_equal(got, oracle.COracle(ps).batch(x, nthreads=min(16, os.cpu_count() or 1)))
+    assert np.array_equal(got, oracle.COracle(ps).batch(x, nthreads=NTH))
 
 
 @pytest.mark.parametrize("stress", [False, True])

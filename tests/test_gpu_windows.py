@@ -6,40 +6,15 @@ The reference is always the C oracle on materialised windows (sliding_window_vie
 pack_trials -> COracle.batch); the existing channel-major batched entry (forward_ct_torch) on the
 same windows is a second witness.  Inputs are uniform int8 from seeded generators.
 """
-import ctypes
-import os
-
 import numpy as np
 import pytest
-from numpy.lib.stride_tricks import sliding_window_view
 
 import oracle
 from mibminet import lib
 from mibminet.params import ParamSet, pack_trials
-from test_gpu_general import _tile_sweep
+from support import NTH, at_offset, float_recording, length, recording, sliding_windows, tile_sweep
 
 pytestmark = pytest.mark.gpu
-NTH = min(16, os.cpu_count() or 1)
-
-
-def _materialise(x_ct, T, hop):
-    """[C][L] -> the windows [W][C][T], window w = x[:, w hop : w hop + T]."""
-    v = sliding_window_view(x_ct, T, axis=1)[:, ::hop]
-    return np.ascontiguousarray(v.transpose(1, 0, 2))
-
-
-def _at_offset(torch, arr, offset):
-    """`arr` on the device, its first byte `offset` bytes into the allocation."""
-    a = np.ascontiguousarray(arr)
-    raw = torch.from_numpy(a.view(np.uint8).ravel()).cuda()
-    flat = torch.zeros(offset + raw.numel() + 64, dtype=torch.uint8, device="cuda")
-    flat[offset: offset + raw.numel()] = raw
-    dt = {np.dtype(np.int8): torch.int8, np.dtype(np.float32): torch.float32}[a.dtype]
-    return flat[offset: offset + raw.numel()].view(dt).view(*a.shape)
-
-
-def _recording(ps, L, seed):
-    return np.random.default_rng(seed).integers(-128, 128, size=(ps.dims.C, L)).astype(np.int8)
 
 
 def _check_windows(ps, x_ct, hop, offset=0, layouts=("ct", "tc"), witness=True, oracle_every=1):
@@ -48,7 +23,7 @@ def _check_windows(ps, x_ct, hop, offset=0, layouts=("ct", "tc"), witness=True, 
     import torch
 
     d = ps.dims
-    wins = _materialise(x_ct, d.T, hop)
+    wins = sliding_windows(x_ct, d.T, hop)
     W = wins.shape[0]
     assert W == lib.windows_count(x_ct.shape[1], hop)
     idx = np.arange(0, W, oracle_every)
@@ -58,21 +33,13 @@ def _check_windows(ps, x_ct, hop, offset=0, layouts=("ct", "tc"), witness=True, 
         full = lib.forward_ct_torch(torch.from_numpy(wins).cuda()).cpu().numpy()
         np.testing.assert_array_equal(full[idx], want, err_msg="forward_ct_torch vs oracle")
     for layout in layouts:
-        x = _at_offset(torch, x_ct if layout == "ct" else x_ct.T, offset)
+        x = at_offset(torch, x_ct if layout == "ct" else x_ct.T, offset)
         got = lib.forward_windows_torch(x, hop, layout=layout).cpu().numpy()
         assert got.shape == (W, d.N)
         np.testing.assert_array_equal(got[idx], want, err_msg=f"{layout} hop {hop} offset {offset}")
         if full is not None:
             np.testing.assert_array_equal(got, full, err_msg=f"{layout} hop {hop} vs forward_ct_torch")
     return want
-
-
-def _length(T, hop, residue, wmin=40):
-    """The shortest L with at least wmin windows and L % 16 == residue."""
-    L = T + (wmin - 1) * hop
-    while L % 16 != residue:
-        L += 1
-    return L
 
 
 @pytest.mark.parametrize("hop", [1, 2, 3, 5, 8, 16, 480, 485])
@@ -88,19 +55,13 @@ def test_alignment(hop, gpu):
     assert lib.params_info()["path"] == "general"
     d = ps.dims
     for i, residue in enumerate((0, 1, 15)):
-        L = _length(d.T, hop, residue)
-        x_ct = _recording(ps, L, 1000 * hop + residue)
+        L = length(d.T, hop, residue)
+        x_ct = recording(ps, L, 1000 * hop + residue)
         _check_windows(ps, x_ct, hop, offset=(hop + i) % 4, witness=residue == 1)
         _check_windows(ps, x_ct, hop, offset=(hop + i + 2) % 4, witness=False)
         # float32 recording: the in-kernel quantiser per sample, against the two-pass quantiser
-        g = torch.Generator(device="cuda").manual_seed(L)
-        xf = _at_offset(torch, np.zeros((d.C, L), np.float32), 4 * (i % 2))
-        xf.copy_(torch.randn((d.C, L), dtype=torch.float32, device="cuda", generator=g) * 1.3)
-        xf[0, :7] = torch.tensor([float("nan"), float("inf"), -float("inf"), 3.0, -3.0, 0.0, -0.0])
-        xf[d.C - 1, L - 3:] = torch.tensor([float("nan"), -float("inf"), float("inf")])
-        q = lib.quantize_input_torch(xf[None].contiguous(), 3.0)  # [1][stride], the trial [L][C]
-        q_ct = q.cpu().numpy()[0, : L * d.C].reshape(L, d.C).T
-        want = oracle.COracle(ps).batch(pack_trials(_materialise(q_ct, d.T, hop)), nthreads=NTH)
+        xf, q_ct = float_recording(torch, d.C, L, 4 * (i % 2), L)
+        want = oracle.COracle(ps).batch(pack_trials(sliding_windows(q_ct, d.T, hop)), nthreads=NTH)
         got = lib.forward_windows_f32_torch(xf, hop, 3.0).cpu().numpy()
         np.testing.assert_array_equal(got, want, err_msg=f"f32 hop {hop} L {L}")
 
@@ -116,7 +77,7 @@ def test_compiled_geometries(C, T, gpu):
     info = lib.params_info()
     assert info["path"] == "float"
     hop, W = 7, 33
-    x_ct = _recording(ps, T + (W - 1) * hop, C * T)
+    x_ct = recording(ps, T + (W - 1) * hop, C * T)
     _check_windows(ps, x_ct, hop, offset=1)
     assert lib.params_info() == info
     xp = pack_trials(np.random.default_rng(T).integers(-128, 128, size=(41, C, T)))
@@ -128,12 +89,12 @@ def test_persistent_loop(gpu):
     """More windows than resident workgroups (several windows per workgroup), at hop 1."""
     ps = ParamSet.synthetic(seed=23)
     lib.params_load(ps)
-    x_ct = _recording(ps, 1125 + 1536, 23)
+    x_ct = recording(ps, 1125 + 1536, 23)
     want = _check_windows(ps, x_ct, 1, offset=3, oracle_every=7)
     assert want.shape == (220, 4)
 
 
-_EDGES = [(1, 64, 1, {}), (5, 100, 16, {}), (64, 4096, 5, {}), (64, 513, 2, {})] + [_tile_sweep()[r] for r in (0, 1, 16, 17)]
+_EDGES = [(1, 64, 1, {}), (5, 100, 16, {}), (64, 4096, 5, {}), (64, 513, 2, {})] + [tile_sweep()[r] for r in (0, 1, 16, 17)]
 
 
 @pytest.mark.parametrize("C,T,N,kw", _EDGES)
@@ -145,13 +106,13 @@ def test_edges(C, T, N, kw, gpu):
 
     ps = ParamSet.synthetic(seed=C * T + N, C=C, T=T, N=N, **kw)
     lib.params_load(ps)
-    x_ct = _recording(ps, T + 2 * 37 + 5, C + T)
+    x_ct = recording(ps, T + 2 * 37 + 5, C + T)
     assert lib.windows_count(x_ct.shape[1], 37) == 3
     _check_windows(ps, x_ct, 37, offset=1)
     _check_windows(ps, x_ct[:, :T], 37, offset=2)  # L == T
     # L == T - 1: no window, y and the workspace untouched
     L = T - 1
-    x = _at_offset(torch, x_ct[:, :L], 0)
+    x = at_offset(torch, x_ct[:, :L], 0)
     y = torch.full((64,), 0x5A, dtype=torch.int8, device="cuda")
     ws = torch.full((lib.windows_workspace(L) + 64,), 0x5A, dtype=torch.int8, device="cuda")
     for layout in (0, 1):
@@ -181,7 +142,7 @@ def test_variants(C, T, N, kw, gpu):
     if "extreme" in kw:
         assert lib.params_info()["exact_division"] == (kw["extreme"] > 0)
     hop, W = 9, 29
-    _check_windows(ps, _recording(ps, T + (W - 1) * hop + 4, C + len(kw)), hop, offset=2)
+    _check_windows(ps, recording(ps, T + (W - 1) * hop + 4, C + len(kw)), hop, offset=2)
 
 
 @pytest.mark.parametrize("C,T,N,layout", [(19, 480, 3, 1), (19, 480, 3, 0), (22, 1125, 4, 1), (64, 513, 2, 0)])
@@ -196,10 +157,10 @@ def test_workspace(C, T, N, layout, gpu):
     d = ps.dims
     hop = 11
     L = T + 20 * hop + 3
-    x_ct = _recording(ps, L, L)
+    x_ct = recording(ps, L, L)
     W = lib.windows_count(L, hop)
     wsb, rs = lib.windows_workspace(L), lib.windows_row_stride(L)
-    x = _at_offset(torch, x_ct if layout == 1 else x_ct.T, 3)
+    x = at_offset(torch, x_ct if layout == 1 else x_ct.T, 3)
     y = torch.full((W * N + 64,), 0x5A, dtype=torch.int8, device="cuda")
     ws = torch.full((wsb + 64,), 0x5A, dtype=torch.int8, device="cuda")
     rc = lib.load().net_model_compute_windows(x.data_ptr(), layout, L, hop, y.data_ptr(), ws.data_ptr(), wsb, 0, None)
@@ -211,7 +172,7 @@ def test_workspace(C, T, N, layout, gpu):
         want = co.layer1(oracle.to_tc_align(x_ct[:, s: s + T], d.C_ALIGN))[:, :T]
         np.testing.assert_array_equal(y1[:, s: s + T], want, err_msg=f"workspace at {s}")
     assert not y1[:, L:].any()
-    want = co.batch(pack_trials(_materialise(x_ct, T, hop)), nthreads=NTH)
+    want = co.batch(pack_trials(sliding_windows(x_ct, T, hop)), nthreads=NTH)
     np.testing.assert_array_equal(y[: W * N].view(W, N).cpu().numpy(), want)
     # the Python entry returns the same workspace
     y2, ws2 = lib.forward_windows_torch(x, hop, layout="ct" if layout == 1 else "tc", return_y1=True)
@@ -286,14 +247,6 @@ def test_python_entries_reject_wrong_tensors(gpu):
     assert lib.forward_windows_f32_torch(good.to(torch.float32), 8, 1.0).shape == (16, 3)
 
 
-def _upload_stats():
-    f = lib.load().mibminet_test_upload_stats
-    f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    a, b = ctypes.c_int64(0), ctypes.c_int64(0)
-    assert f(ctypes.byref(a), ctypes.byref(b)) == lib.NET_OK
-    return a.value
-
-
 def test_image_lifetime_and_graph_replay(gpu):
     """Each loaded set keeps its own device copy of the window kernels' image: a reload of a set
     reuses its copy, and a captured windows call keeps replaying the set it was captured with."""
@@ -303,20 +256,20 @@ def test_image_lifetime_and_graph_replay(gpu):
     ps_b = ParamSet.synthetic(seed=62, reorder_bn=False, clip_balanced=True)
     hop, W = 5, 47
     L = 1125 + (W - 1) * hop
-    x_ct = _recording(ps_a, L, 61)
-    packed = pack_trials(_materialise(x_ct, 1125, hop))
+    x_ct = recording(ps_a, L, 61)
+    packed = pack_trials(sliding_windows(x_ct, 1125, hop))
     want_a = oracle.COracle(ps_a).batch(packed, nthreads=NTH)
     want_b = oracle.COracle(ps_b).batch(packed, nthreads=NTH)
     assert not np.array_equal(want_a, want_b)
-    x = _at_offset(torch, x_ct, 1)
+    x = at_offset(torch, x_ct, 1)
     lib.params_load(ps_a)
     np.testing.assert_array_equal(lib.forward_windows_torch(x, hop).cpu().numpy(), want_a)
     lib.params_load(ps_b)
     np.testing.assert_array_equal(lib.forward_windows_torch(x, hop).cpu().numpy(), want_b)
-    up = _upload_stats()
+    up = lib.upload_stats()[0]
     lib.params_load(ps_a)
     np.testing.assert_array_equal(lib.forward_windows_torch(x, hop).cpu().numpy(), want_a)
-    assert _upload_stats() == up  # A's copy was still there
+    assert lib.upload_stats()[0] == up  # A's copy was still there
     # capture on a side stream (a linear graph; the eager call above uploaded the parameters)
     y = torch.zeros((W, 4), dtype=torch.int8, device="cuda")
     ws = torch.zeros((lib.windows_workspace(L),), dtype=torch.int8, device="cuda")

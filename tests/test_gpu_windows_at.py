@@ -6,29 +6,19 @@ The reference is always the C oracle on gathered trials (-> [W][C][T] -> pack_tr
 COracle.batch); the existing entries (forward_windows_torch, forward_ct_torch) are a second
 witness.  Inputs are uniform int8 from seeded generators.
 """
-import os
-
 import numpy as np
 import pytest
 
 import oracle
 from mibminet import lib
 from mibminet.params import ParamSet, pack_trials
-from test_gpu_general import _tile_sweep
-from test_gpu_windows import _at_offset, _length, _recording
+from support import _BAD, NTH, at_offset, float_recording, length, recording, tile_sweep, want, windows_at
 
 pytestmark = pytest.mark.gpu
-NTH = min(16, os.cpu_count() or 1)
 
 
-def _gather(x_ct, onsets, T):
-    """[C][L] -> the windows [W][C][T], window i = x[:, onsets[i] : onsets[i] + T]."""
-    idx = np.asarray(onsets, np.int64)[:, None] + np.arange(T, dtype=np.int64)[None, :]
-    return np.ascontiguousarray(x_ct[:, idx].transpose(1, 0, 2))
-
-
-def _want(ps, x_ct, onsets):
-    return oracle.COracle(ps).batch(pack_trials(_gather(x_ct, onsets, ps.dims.T)), nthreads=NTH)
+def _want_at(ps, x_ct, onsets):
+    return want(ps, windows_at(x_ct, onsets, ps.dims.T))
 
 
 def _check_at(ps, x_ct, onsets, offset=0, layouts=("ct", "tc"), witness=False):
@@ -36,28 +26,16 @@ def _check_at(ps, x_ct, onsets, offset=0, layouts=("ct", "tc"), witness=False):
     the gathered windows.  The set must be loaded.  Returns the expected logits."""
     import torch
 
-    want = _want(ps, x_ct, onsets)
+    want = _want_at(ps, x_ct, onsets)
     if witness:
-        full = lib.forward_ct_torch(torch.from_numpy(_gather(x_ct, onsets, ps.dims.T)).cuda()).cpu().numpy()
+        full = lib.forward_ct_torch(torch.from_numpy(windows_at(x_ct, onsets, ps.dims.T)).cuda()).cpu().numpy()
         np.testing.assert_array_equal(full, want, err_msg="forward_ct_torch vs oracle")
     for layout in layouts:
-        x = _at_offset(torch, x_ct if layout == "ct" else x_ct.T, offset)
+        x = at_offset(torch, x_ct if layout == "ct" else x_ct.T, offset)
         got = lib.forward_windows_at_torch(x, onsets, layout=layout).cpu().numpy()
         assert got.shape == (len(onsets), ps.dims.N)
         np.testing.assert_array_equal(got, want, err_msg=f"{layout} offset {offset}")
     return want
-
-
-def _float_recording(torch, C, L, offset, seed):
-    """A float32 recording [C][L] with non-finite samples planted, and its two-pass quantisation
-    (scale 3) as an int8 [C][L] array."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    xf = _at_offset(torch, np.zeros((C, L), np.float32), offset)
-    xf.copy_(torch.randn((C, L), dtype=torch.float32, device="cuda", generator=g) * 1.3)
-    xf[0, :7] = torch.tensor([float("nan"), float("inf"), -float("inf"), 3.0, -3.0, 0.0, -0.0])
-    xf[C - 1, L - 3:] = torch.tensor([float("nan"), -float("inf"), float("inf")])
-    q = lib.quantize_input_torch(xf[None].contiguous(), 3.0)  # [1][stride], the trial [L][C]
-    return xf, np.ascontiguousarray(q.cpu().numpy()[0, : L * C].reshape(L, C).T)
 
 
 def _irregular(L, T, n, seed):
@@ -77,20 +55,20 @@ def test_regular_onsets_equal_the_regular_entry(hop, gpu):
     lib.params_load(ps)
     assert lib.params_info()["path"] == "general"
     d = ps.dims
-    L = _length(d.T, hop, (5 * hop) % 16)
+    L = length(d.T, hop, (5 * hop) % 16)
     W = lib.windows_count(L, hop)
     assert 40 <= W <= 56
     onsets = (np.arange(W, dtype=np.int64) * hop).tolist()
-    x_ct = _recording(ps, L, 77 + hop)
+    x_ct = recording(ps, L, 77 + hop)
     want = _check_at(ps, x_ct, onsets, offset=hop % 4, witness=True)
     for layout in ("ct", "tc"):
-        x = _at_offset(torch, x_ct if layout == "ct" else x_ct.T, 1)
+        x = at_offset(torch, x_ct if layout == "ct" else x_ct.T, 1)
         reg = lib.forward_windows_torch(x, hop, layout=layout)
         got = lib.forward_windows_at_torch(x, torch.arange(W, dtype=torch.int64, device="cuda") * hop, layout=layout)
         assert bool((reg == got).all())
         np.testing.assert_array_equal(got.cpu().numpy(), want)
-    xf, q_ct = _float_recording(torch, d.C, L, 4 * (hop % 2), L)
-    want_f = _want(ps, q_ct, onsets)
+    xf, q_ct = float_recording(torch, d.C, L, 4 * (hop % 2), L)
+    want_f = _want_at(ps, q_ct, onsets)
     got_f = lib.forward_windows_at_torch(xf, onsets, scale=3.0)
     np.testing.assert_array_equal(got_f.cpu().numpy(), want_f, err_msg="f32")
     assert bool((got_f == lib.forward_windows_f32_torch(xf, hop, 3.0)).all())
@@ -114,21 +92,21 @@ def test_arbitrary_onsets(extra, gpu):
     onsets += [int(v) for v in rng.integers(0, L - T + 1, size=12)]
     assert len(onsets) == 64 and {o % 16 for o in onsets} == set(range(16)) and len(set(onsets)) < 64
     assert onsets != sorted(onsets) and min(onsets) == 0 and max(onsets) == L - T
-    x_ct = _recording(ps, L, L)
+    x_ct = recording(ps, L, L)
     for offset in (1, 2, 3):
         _check_at(ps, x_ct, onsets, offset=offset, witness=offset == 1)
-    x = _at_offset(torch, x_ct, 1 + extra % 3)
+    x = at_offset(torch, x_ct, 1 + extra % 3)
     y, ws = lib.forward_windows_at_torch(x, onsets, return_y1=True)
     y_reg, ws_reg = lib.forward_windows_torch(x, 1, return_y1=True)
     assert tuple(ws.shape) == (16, lib.windows_row_stride(L)) and bool((ws == ws_reg).all())
     assert bool((y == y_reg[torch.tensor(onsets, device="cuda")]).all())
     # float32, the same onsets
-    xf, q_ct = _float_recording(torch, 19, L, 4, L)
+    xf, q_ct = float_recording(torch, 19, L, 4, L)
     got_f = lib.forward_windows_at_torch(xf, onsets, scale=3.0).cpu().numpy()
-    np.testing.assert_array_equal(got_f, _want(ps, q_ct, onsets))
+    np.testing.assert_array_equal(got_f, _want_at(ps, q_ct, onsets))
 
 
-_EDGES = [(1, 64, 1, {}), (5, 100, 16, {}), (64, 513, 2, {})] + [_tile_sweep()[r] for r in (0, 1, 16, 17)]
+_EDGES = [(1, 64, 1, {}), (5, 100, 16, {}), (64, 513, 2, {})] + [tile_sweep()[r] for r in (0, 1, 16, 17)]
 
 
 @pytest.mark.parametrize("C,T,N,kw", _EDGES)
@@ -138,12 +116,9 @@ def test_edges(C, T, N, kw, gpu):
     ps = ParamSet.synthetic(seed=C * T + N, C=C, T=T, N=N, **kw)
     lib.params_load(ps)
     L = T + 37
-    x_ct = _recording(ps, L, C + T)
+    x_ct = recording(ps, L, C + T)
     _check_at(ps, x_ct, [L - T, 0, 7], offset=1)
     _check_at(ps, x_ct[:, :T], [0], offset=2)  # L == T
-
-
-_BAD = [-1, None, 2**31, 2**32, 2**32 + 5, -(2**63), 2**63 - 1]  # None: L - T + 1
 
 
 def test_persistent_loop_with_invalid_onsets(gpu):
@@ -171,9 +146,9 @@ def test_persistent_loop_with_invalid_onsets(gpu):
     # finishes) and on one in between
     assert bad[0] < grid and bad[-1] + grid >= W and any(grid <= i < W - grid for i in bad)
     ok = [i for i in range(W) if i % 7]
-    x_ct = _recording(ps, L, 41)
-    want = _want(ps, x_ct, [onsets[i] for i in ok])
-    x = _at_offset(torch, x_ct, 3)
+    x_ct = recording(ps, L, 41)
+    want = _want_at(ps, x_ct, [onsets[i] for i in ok])
+    x = at_offset(torch, x_ct, 3)
     on = torch.tensor(onsets, dtype=torch.int64, device="cuda")
     wsb = lib.windows_workspace(L)
     y = torch.full((W * N + 64,), 0x5A, dtype=torch.int8, device="cuda")
@@ -220,15 +195,15 @@ def test_many_recordings(kind, gpu):
     assert first_want == [0, 6, 6, 6, 7, 9, 78]
     layout, scale = ("tc", None) if kind == "tc" else ("ct", 3.0 if kind == "f32" else None)
     if kind == "f32":
-        cat, q_ct = _float_recording(torch, 19, total, 0, 5)
+        cat, q_ct = float_recording(torch, 19, total, 0, 5)
         single = lambda t: lib.forward_windows_f32_torch(t, hop, 3.0)
     else:
-        q_ct = _recording(ps, total, 5)
+        q_ct = recording(ps, total, 5)
         cat = torch.from_numpy(np.ascontiguousarray(q_ct if kind == "ct" else q_ct.T)).cuda()
         single = lambda t: lib.forward_windows_torch(t, hop, layout=layout)
     axis = 1 if layout == "ct" else 0
     recs = [cat.narrow(axis, bounds[r], n).contiguous() for r, n in enumerate(_LENGTHS)]
-    want = _want(ps, q_ct, on_want)
+    want = _want_at(ps, q_ct, on_want)
     per_rec = torch.cat([single(t) for t in recs], dim=0)
     np.testing.assert_array_equal(per_rec.cpu().numpy(), want)
     per = max(16, 19 * (4 if kind == "f32" else 1))
@@ -259,7 +234,7 @@ def test_variants(C, T, N, kw, gpu):
     if "extreme" in kw:
         assert lib.params_info()["exact_division"] == (kw["extreme"] > 0)
     L = T + 260
-    _check_at(ps, _recording(ps, L, C + len(kw)), _irregular(L, T, 29, C + T), offset=2)
+    _check_at(ps, recording(ps, L, C + len(kw)), _irregular(L, T, 29, C + T), offset=2)
 
 
 @pytest.mark.parametrize("C,T", [(22, 1125), (64, 1000), (64, 480)])
@@ -273,7 +248,7 @@ def test_compiled_geometries(C, T, gpu):
     info = lib.params_info()
     assert info["path"] == "float"
     L = T + 231
-    _check_at(ps, _recording(ps, L, C * T), _irregular(L, T, 33, T), offset=1, witness=True)
+    _check_at(ps, recording(ps, L, C * T), _irregular(L, T, 33, T), offset=1, witness=True)
     assert lib.params_info() == info
     xp = pack_trials(np.random.default_rng(T).integers(-128, 128, size=(41, C, T)))
     got = lib.forward_torch(torch.from_numpy(xp).cuda()).cpu().numpy()
@@ -291,10 +266,10 @@ def test_graph_capture_and_replay(gpu):
     T, W = 1125, 47
     L = T + 300
     onsets = _irregular(L, T, W, 61)
-    x_ct = _recording(ps_a, L, 61)
-    want_a, want_b = _want(ps_a, x_ct, onsets), _want(ps_b, x_ct, onsets)
+    x_ct = recording(ps_a, L, 61)
+    want_a, want_b = _want_at(ps_a, x_ct, onsets), _want_at(ps_b, x_ct, onsets)
     assert not np.array_equal(want_a, want_b)
-    x = _at_offset(torch, x_ct, 1)
+    x = at_offset(torch, x_ct, 1)
     on = torch.tensor(onsets, dtype=torch.int64, device="cuda")
     lib.params_load(ps_b)
     np.testing.assert_array_equal(lib.forward_windows_at_torch(x, on).cpu().numpy(), want_b)

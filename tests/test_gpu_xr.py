@@ -14,18 +14,16 @@ integers (forward_common.hpp, xdiv).  These tests check:
   single-trial and per-layer entry points.
 The committed fixture ``fixture_xr22.npz`` runs through test_gpu_parity.py's fixture tests too.
 """
-import os
-
 import numpy as np
 import pytest
 
 import oracle
 from mibminet import lib
 from mibminet.params import ParamSet, pack_trials
+from support import NTH
 
 pytestmark = pytest.mark.gpu
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
-NT = min(16, os.cpu_count() or 1)
 
 
 @pytest.mark.parametrize("d", [1, -3, I32_MAX])
@@ -76,7 +74,7 @@ def test_extreme_nets_vs_oracle(case, gpu):
     x[-1] = 127
     x[-2] = -128
     xp = pack_trials(x)
-    want = oracle.COracle(ps).batch(xp, nthreads=NT)
+    want = oracle.COracle(ps).batch(xp, nthreads=NTH)
     got = lib.forward_torch(torch.from_numpy(xp).cuda()).cpu().numpy()
     assert np.array_equal(got, want)
     got_ct = lib.forward_ct_torch(torch.from_numpy(x).cuda()).cpu().numpy()
@@ -127,7 +125,7 @@ def test_extreme_f32_matches_chain(C, T, rb, gpu):
     y = lib.forward_f32_torch(x, 2.0).cpu().numpy()
     xq = lib.quantize_input_torch(x, 2.0)
     assert np.array_equal(y, lib.forward_torch(xq).cpu().numpy())
-    assert np.array_equal(y, oracle.COracle(ps).batch(xq.cpu().numpy(), nthreads=NT))
+    assert np.array_equal(y, oracle.COracle(ps).batch(xq.cpu().numpy(), nthreads=NTH))
 
 
 def test_extreme_full_batch(gpu):
@@ -148,7 +146,7 @@ def test_extreme_full_batch(gpu):
     assert torch.equal(y, y2) and torch.equal(y, yc)
     idx = np.concatenate([np.arange(16), B - 16 + np.arange(16), rng.choice(B, 256, replace=False)])
     xs = xp[torch.from_numpy(idx).cuda()].cpu().numpy()
-    assert np.array_equal(y.cpu().numpy()[idx], oracle.COracle(ps).batch(xs, nthreads=NT))
+    assert np.array_equal(y.cpu().numpy()[idx], oracle.COracle(ps).batch(xs, nthreads=NTH))
 
 
 @pytest.mark.parametrize("C,T,rb,cb", [(22, 1125, True, False), (22, 1125, False, True), (64, 1000, True, True),
@@ -169,7 +167,7 @@ def test_folded_rail_sets_on_the_float_kernels(C, T, rb, cb, gpu):
     x[-2] = -128
     xp = pack_trials(x)
     co = oracle.COracle(ps)
-    want = co.batch(xp, nthreads=NT)
+    want = co.batch(xp, nthreads=NTH)
     assert np.array_equal(lib.forward_torch(torch.from_numpy(xp).cuda()).cpu().numpy(), want)
     assert np.array_equal(lib.forward_ct_torch(torch.from_numpy(x).cuda()).cpu().numpy(), want)
     d = ps.dims
@@ -217,7 +215,7 @@ def test_xr_divisor_extremes_on_varying_filters(gpu):
         x[i] = top[:, None].astype(np.int8)
     xp = pack_trials(x)
     co = oracle.COracle(ps)
-    assert np.array_equal(lib.forward_torch(torch.from_numpy(xp).cuda()).cpu().numpy(), co.batch(xp, nthreads=NT))
+    assert np.array_equal(lib.forward_torch(torch.from_numpy(xp).cuda()).cpu().numpy(), co.batch(xp, nthreads=NTH))
     d = ps.dims
     for i in (0, 1, 2):
         xa = oracle.to_tc_align(x[i], d.C_ALIGN)

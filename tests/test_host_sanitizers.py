@@ -12,7 +12,7 @@ import subprocess
 import pytest
 
 from mibminet.params import ParamSet, dot_ranges
-from test_images_cpu import ROWS
+from support import ROWS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mi-bminet_amd", "csrc")

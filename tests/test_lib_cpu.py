@@ -32,11 +32,11 @@ _C_IMAGE = {"size_t": ctypes.c_size_t, "int": ctypes.c_int, "int32_t": ctypes.c_
             "float": ctypes.c_float, "double": ctypes.c_double}
 
 
-def header_prototypes():
-    """{name: (restype, argtypes)} of every function include/mibminet.h declares, each C type as
-    its ctypes image: any pointer c_void_p (a returned ``const char*`` c_char_p), the scalars as
-    _C_IMAGE, a void return None and ``(void)`` no arguments."""
-    text = open(os.path.join(ROOT, "include", "mibminet.h")).read()
+def header_prototypes(header="mibminet.h"):
+    """{name: (restype, argtypes)} of every function include/``header`` declares, in its order, each
+    C type as its ctypes image: any pointer c_void_p (a returned ``const char*`` c_char_p), the
+    scalars as _C_IMAGE, a void return None and ``(void)`` no arguments."""
+    text = open(os.path.join(ROOT, "include", header)).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     text = re.sub(r"//[^\n]*", "", text)
     text = re.sub(r"typedef\s+struct\s*\{.*?\}\s*\w+\s*;", "", text, flags=re.S)  # net_arrays_t's fields are no functions
@@ -57,21 +57,20 @@ def header_prototypes():
 
 
 def test_prototype_table_matches_header():
-    """lib.PROTOTYPES gives every function the header declares, and no other net_* function, the
-    ctypes image of its declaration, in the header's order, and load() has bound exactly that."""
+    """lib.PROTOTYPES gives every function include/mibminet.h declares, then every hook
+    include/mibminet_testing.h declares, and no other function, the ctypes image of its declaration,
+    in its header's order, and load() has bound exactly that."""
     protos = header_prototypes()
     assert sorted(protos) == declared_functions() and len(protos) >= 42
     assert list(lib.EXPORTED_SYMBOLS) == list(protos)
+    hooks = header_prototypes("mibminet_testing.h")
+    assert len(hooks) >= 14 and all(n.startswith("mibminet_test_") for n in hooks)
+    assert list(lib.PROTOTYPES) == list(protos) + list(hooks)
     L = lib.load()
-    for name, (ret, args) in protos.items():
+    for name, (ret, args) in {**protos, **hooks}.items():
         assert lib.prototype(name) == (ret, args), name
         fn = getattr(L, name)
         assert fn.restype is ret and list(fn.argtypes) == args, name
-    hooks = set(lib.PROTOTYPES) - set(protos)
-    assert hooks and all(n.startswith("mibminet_test_") for n in hooks)
-    for name in hooks:
-        fn = getattr(L, name)
-        assert (fn.restype, list(fn.argtypes)) == lib.prototype(name), name
 
 
 def test_torch_entries_refuse_what_is_no_tensor():
@@ -213,12 +212,9 @@ def test_params_load_rejects_nonzero_pads():
 
 
 def _multi_order(devices, fail_at=-1):
-    L = lib.load()
-    f = L.mibminet_test_multi_order
-    f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
     dev = (ctypes.c_int * len(devices))(*devices)
     buf = ctypes.create_string_buffer(256)
-    rc = f(len(devices), dev, fail_at, buf, 256)
+    rc = lib.load().mibminet_test_multi_order(len(devices), dev, fail_at, buf, 256)
     return rc, buf.value.decode().split()
 
 

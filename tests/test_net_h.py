@@ -58,8 +58,6 @@ def _compile_net_c(tmp_path, ps):
 
 def _arrays(L, ps, flags):
     d = ps.dims
-    A = lib.load()
-    A.net_params_load_arrays.argtypes = [ctypes.c_void_p]
 
     class Arrays(ctypes.Structure):
         _fields_ = [(n, ctypes.c_int32) for n in ("C", "T", "F1", "F2", "D", "N")] + [("flags", ctypes.c_uint32)] + [
@@ -75,14 +73,6 @@ def _arrays(L, ps, flags):
                   sym("net_l2_offset"), sym("net_l2_weight_reverse"), ps.l3_factor, sym("net_l3_weight"),
                   sym("net_l4_factor"), sym("net_l4_offset"), sym("net_l4_weight"), ps.l5_factor,
                   sym("net_l5_bias"), sym("net_l5_weight"))
-
-
-def _digest():
-    A = lib.load()
-    A.mibminet_test_image_digest.argtypes = [ctypes.c_void_p]
-    v = ctypes.c_uint64(0)
-    assert A.mibminet_test_image_digest(ctypes.byref(v)) == lib.NET_OK
-    return v.value
 
 
 @pytest.mark.parametrize("kw", [dict(C=22, T=1125), dict(C=19, T=480, N=3), dict(C=64, T=1000, reorder_bn=False),
@@ -103,12 +93,12 @@ def test_arrays_round_trip_and_load_like_the_blob(tmp_path, kw):
         np.testing.assert_array_equal(got, np.asarray(want).ravel(), err_msg=name)
     # the arrays load through the C entry into the same device image as the blob
     lib.params_load(ps)
-    want_digest = _digest()
+    want_digest = lib.image_digest()
     info = lib.params_info()
     a = _arrays(L, ps, ps.flags)
     lib.params_unload()
     assert lib.load().net_params_load_arrays(ctypes.byref(a)) == lib.NET_OK
-    assert _digest() == want_digest and lib.params_info() == info
+    assert lib.image_digest() == want_digest and lib.params_info() == info
     # the blob's checks: non-zero pads and unknown flags are refused
     a.flags = 4
     assert lib.load().net_params_load_arrays(ctypes.byref(a)) == lib.NET_ERR_BLOB

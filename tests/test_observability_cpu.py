@@ -20,6 +20,7 @@ import observability as ob
 import oracle
 from mibminet.params import ParamSet, pack_trials
 from oracle import golden_np as G
+from support import NTH, tile_sweep
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = [c.name for c in ob.CASES]
@@ -78,7 +79,7 @@ def test_every_audited_site_is_seen(name, audits):
         assert all(r["live"].values()), r["live"]
         assert r["unseen"] == {key: 0 for key in r["unseen"]}, f"unseen audited sites {r['unseen']} of {r['sites']}"
         assert r["trials"] <= len(x) <= 4096
-        z = oracle.COracle(ps).batch(pack_trials(x), nthreads=min(16, os.cpu_count() or 1))
+        z = oracle.COracle(ps).batch(pack_trials(x), nthreads=NTH)
         np.testing.assert_array_equal(z[:64], r["z64"])
         rail = float(((z == 127) | (z <= G._lo(ps))).mean())
         print(f"{name}: B {len(x)}, trials used {r['trials']}, audited {r['sites']}, logits on a rail {rail:.4f}, "
@@ -108,11 +109,9 @@ def _baseline():
     """test_gpu_general.test_layer2_tile_sweep's own inputs (its parameter and input seeds, 7
     trials) at the residues the certified cases share with it: sites of the last 16 y1 samples and
     the last 4 y2 columns that a one-LSB mutation makes visible (both deltas counted)."""
-    from test_gpu_general import _tile_sweep
-
     out = {}
     for r in ob.SWEEP_RESIDUES:
-        C, T, N, kw = _tile_sweep()[r]
+        C, T, N, kw = tile_sweep()[r]
         ps = ParamSet.synthetic(seed=7 * C + T + N, C=C, T=T, N=N, **kw)
         x = _rng_x(ps, 7, C * N)
         sites = {k: np.zeros_like(m) for k, m in ob.full_sites(ps).items()}

@@ -22,6 +22,7 @@ import oracle
 import param_faults as pf
 from mibminet.params import ParamSet, pack_trials
 from oracle import golden_np as G
+from support import NTH
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = [c.name for c in pf.PCASES]
@@ -148,7 +149,7 @@ def test_every_fault_is_seen(name, audits):
         assert not bad, f"(unseen, identical, first unseen) per (array, family): {bad}"
         assert r["trials"] <= len(x) <= 4096 and len(x) % 64 == 0
         assert r["excluded"] <= r["moved_faults"] and (case.exact or r["excluded"] == 0)
-        z = oracle.COracle(ps).batch(pack_trials(x), nthreads=min(16, os.cpu_count() or 1))
+        z = oracle.COracle(ps).batch(pack_trials(x), nthreads=NTH)
         np.testing.assert_array_equal(z[:64], r["z64"])
         rail = float(((z == 127) | (z <= G._lo(ps))).mean())
         print(f"{name}: B {len(x)}, trials used {r['trials']}, faults {pf.totals(r['res'])}, excluded {r['excluded']}, "

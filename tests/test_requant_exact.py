@@ -15,9 +15,7 @@ CHUNK = 1 << 22
 
 
 def _reciprocal(fac, vmax, magic):
-    L = lib.load()
-    fn = L.mibminet_test_reciprocal
-    fn.argtypes = [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    fn = lib.load().mibminet_test_reciprocal
     r, c = ctypes.c_float(), ctypes.c_float()
     rc = fn(fac, vmax, 128, int(magic), ctypes.addressof(r), ctypes.addressof(c))
     return rc, np.float32(r.value), np.float32(c.value)

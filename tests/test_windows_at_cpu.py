@@ -9,24 +9,10 @@ import pytest
 
 from mibminet import lib
 from mibminet.params import ParamSet
+from support import aligned, loaded  # noqa: F401 (loaded: a fixture)
 
 INV, NOP, RNG, OK = lib.NET_ERR_INVALID, lib.NET_ERR_NO_PARAMS, lib.NET_ERR_RANGE, lib.NET_OK
 T = 1125
-
-
-@pytest.fixture
-def loaded():
-    ps = ParamSet.synthetic(seed=5)  # 22 x 1125, N = 4
-    lib.params_load(ps)
-    yield ps
-    lib.params_unload()
-
-
-def _aligned(nbytes, align=16):
-    """A host buffer and an `align`-aligned address inside it."""
-    buf = np.zeros(nbytes + align, np.uint8)
-    a = buf.ctypes.data
-    return buf, (a + align - 1) // align * align
 
 
 def test_ctypes_signatures():
@@ -49,7 +35,7 @@ def test_invalid_arguments_without_a_gpu(loaded):
     fn = lib.load().net_model_compute_windows_at
     L, W = 4000, 9
     wsb = lib.windows_workspace(L)
-    keep, ws = _aligned(128)
+    keep, ws = aligned(128)
     x, y, on, nb = ws + 16, ws + 32, ws + 48, ws + 64  # never read: every call below fails a check
     for layout in (2, 3, -1):
         assert fn(x, layout, L, on, W, y, nb, ws, wsb, 0, None) == INV
@@ -88,7 +74,7 @@ def test_float_entry_checks(loaded):
     fn = lib.load().net_model_compute_windows_at_f32
     L, W = 4000, 9
     wsb = lib.windows_workspace(L)
-    keep, ws = _aligned(128)
+    keep, ws = aligned(128)
     x, y, on, nb = ws + 16, ws + 32, ws + 48, ws + 64
     for scale in (0.0, -1.0, float("nan"), float("inf")):
         assert fn(x, L, on, W, scale, y, nb, ws, wsb, 0, None) == INV
@@ -106,7 +92,7 @@ def test_float_entry_checks(loaded):
 def test_sixteen_bytes_per_sample_limit_with_few_channels():
     """C < 16: the workspace rows (16 bytes per sample over the 16 filters) set the limit."""
     lib.params_load(ParamSet.synthetic(seed=3, C=5, T=100, N=16))
-    keep, ws = _aligned(128)
+    keep, ws = aligned(128)
     x, y, on = ws + 16, ws + 32, ws + 48
     assert lib.load().net_model_compute_windows_at(x, 1, 2**27, on, 3, y, None, ws, 2**62, 0, None) == INV
     assert lib.load().net_model_compute_windows_at_f32(x, 2**27, on, 3, 1.0, y, None, ws, 2**62, 0, None) == INV

@@ -9,23 +9,9 @@ import pytest
 
 from mibminet import lib
 from mibminet.params import ParamSet
+from support import aligned, loaded  # noqa: F401 (loaded: a fixture)
 
 INV, NOP, RNG, OK = lib.NET_ERR_INVALID, lib.NET_ERR_NO_PARAMS, lib.NET_ERR_RANGE, lib.NET_OK
-
-
-@pytest.fixture
-def loaded():
-    ps = ParamSet.synthetic(seed=5)  # 22 x 1125, N = 4
-    lib.params_load(ps)
-    yield ps
-    lib.params_unload()
-
-
-def _aligned(nbytes, align=16):
-    """A host buffer and an `align`-aligned address inside it."""
-    buf = np.zeros(nbytes + align, np.uint8)
-    a = buf.ctypes.data
-    return buf, (a + align - 1) // align * align
 
 
 def test_windows_count(loaded):
@@ -70,7 +56,7 @@ def test_invalid_arguments_without_a_gpu(loaded):
     fn = lib.load().net_model_compute_windows
     L, hop = 4000, 8
     wsb = lib.windows_workspace(L)
-    keep, ws = _aligned(64)
+    keep, ws = aligned(64)
     x, y = ws + 16, ws + 32  # never read: every call below fails a check
     assert fn(x, 1, L, 0, y, ws, wsb, 0, None) == INV            # hop == 0
     for layout in (2, 3, -1):
@@ -100,7 +86,7 @@ def test_invalid_arguments_without_a_gpu(loaded):
 
 def test_offset_limit_counts_float_elements(loaded):
     fn = lib.load().net_model_compute_windows_f32
-    keep, ws = _aligned(64)
+    keep, ws = aligned(64)
     x, y = ws + 16, ws + 32
     big = -(-2**31 // 88)  # C sizeof(float) = 88 bytes per sample
     assert fn(x, big, 2**20, 1.0, y, ws, 2**62, 0, None) == INV
@@ -110,7 +96,7 @@ def test_offset_limit_counts_float_elements(loaded):
 def test_sixteen_bytes_per_sample_limit_with_few_channels():
     """C < 16: the workspace rows (16 bytes per sample over the 16 filters) set the limit."""
     lib.params_load(ParamSet.synthetic(seed=3, C=5, T=100, N=16))
-    keep, ws = _aligned(64)
+    keep, ws = aligned(64)
     assert lib.load().net_model_compute_windows(ws + 16, 1, 2**27, 2**20, ws + 32, ws, 2**62, 0, None) == INV
     assert lib.load().net_model_compute_windows_f32(ws + 16, 2**27, 2**20, 1.0, ws + 32, ws, 2**62, 0, None) == INV
     lib.params_unload()
@@ -120,7 +106,7 @@ def test_float_scale_domain(loaded):
     fn = lib.load().net_model_compute_windows_f32
     L, hop = 4000, 8
     wsb = lib.windows_workspace(L)
-    keep, ws = _aligned(64)
+    keep, ws = aligned(64)
     x, y = ws + 16, ws + 32
     for scale in (0.0, -1.0, float("nan"), float("inf")):
         assert fn(x, L, hop, scale, y, ws, wsb, 0, None) == INV
@@ -152,14 +138,6 @@ def test_python_entries_reject_host_tensors_and_unknown_layouts(loaded):
         lib.forward_windows_torch(np.zeros((22, 2000), np.int8), 8)
 
 
-def _digest():
-    A = lib.load()
-    A.mibminet_test_image_digest.argtypes = [ctypes.c_void_p]
-    v = ctypes.c_uint64(0)
-    assert A.mibminet_test_image_digest(ctypes.byref(v)) == OK
-    return v.value
-
-
 @pytest.mark.parametrize("kw,digest,shape", [
     (dict(seed=42), 0x4CB99661AE2E985F, 0),
     (dict(seed=9, C=64, T=1000), 0x4572132575AB237C, 1),
@@ -170,7 +148,7 @@ def test_compiled_sets_keep_their_image_and_path(kw, digest, shape):
     compiled kernels' image, which stays what it was (digests taken before the window kernels
     existed), as does what net_params_info reports."""
     lib.params_load(ParamSet.synthetic(**kw))
-    assert _digest() == digest
+    assert lib.image_digest() == digest
     info = lib.params_info()
     assert info["path"] == "float" and info["shape"] == shape and not info["exact_division"]
     lib.params_unload()

@@ -17,7 +17,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mi-bminet_amd"))
+from mibminet import lib  # noqa: E402
 from mibminet.params import ParamSet  # noqa: E402
+
+CALLED = ("net_params_load", "net_trial_stride", "net_model_compute_batch_async", "net_model_compute_batch_ct",
+          "net_model_compute_batch_f32", "mibminet_test_force_general")
 
 
 def main():
@@ -43,18 +47,11 @@ def main():
               clip_balanced=a.variant == "clip_balanced").to_blob()
     libs = []
     for p in a.libs:
-        L = ctypes.CDLL(os.path.abspath(p), mode=ctypes.RTLD_LOCAL)
-        L.net_params_load.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
-        L.net_trial_stride.restype = ctypes.c_size_t
-        L.net_model_compute_batch_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                                    ctypes.c_int, ctypes.c_void_p]
+        L = lib.bind(ctypes.CDLL(os.path.abspath(p), mode=ctypes.RTLD_LOCAL), CALLED)
         if a.ct:
-            L.net_model_compute_batch_ct.argtypes = L.net_model_compute_batch_async.argtypes
             L.net_model_compute_batch_async = L.net_model_compute_batch_ct
         if a.f32:  # same call shape, the scale bound in (3 sigma of the standard-normal input)
             f = L.net_model_compute_batch_f32
-            f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_float, ctypes.c_int,
-                          ctypes.c_void_p]
             L.net_model_compute_batch_async = (lambda f: lambda x, y, B, d, s: f(x, y, B, 3.0, d, s))(f)
         if a.force_general:
             L.mibminet_test_force_general(1)

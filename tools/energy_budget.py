@@ -22,6 +22,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mi-bminet_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+from mibminet import lib  # noqa: E402
 from mibminet.params import ParamSet  # noqa: E402
 from power_sample import sampler  # noqa: E402
 
@@ -77,11 +78,8 @@ def main():
     rows = []
     xr = xz = None
     for i, p in enumerate(a.libs):
-        L = ctypes.CDLL(os.path.abspath(p), mode=ctypes.RTLD_LOCAL)
-        L.net_params_load.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
-        L.net_trial_stride.restype = ctypes.c_size_t
-        L.net_model_compute_batch_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
-                                                    ctypes.c_void_p]
+        L = lib.bind(ctypes.CDLL(os.path.abspath(p), mode=ctypes.RTLD_LOCAL),
+                     ("net_params_load", "net_trial_stride", "net_model_compute_batch_async"))
         assert L.net_params_load(blob, len(blob)) == 0
         if xr is None:
             stride = L.net_trial_stride()

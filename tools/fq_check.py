@@ -6,19 +6,18 @@ does the same for the shipped library).
 
     python tools/fq_check.py tools/libX_diag.so [scale ...]
 """
-import ctypes
 import os
 import sys
 
 import torch
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "mi-bminet_amd"))
+from mibminet import lib  # noqa: E402
+
 
 def main():
-    L = ctypes.CDLL(os.path.abspath(sys.argv[1]), mode=ctypes.RTLD_LOCAL)
-    L.mibminet_test_quantize_f32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_float,
-                                              ctypes.c_int, ctypes.c_void_p]
-    L.net_quantize_input_f32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
-                                          ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
+    L = lib.load(os.path.abspath(sys.argv[1]))
     scales = [float(s) for s in sys.argv[2:]] or [1.0, 1.7, 2.0 ** -60, 2.0 ** 60]
     n, T = 1 << 28, 1 << 14
     got = torch.empty(n, dtype=torch.int8, device="cuda")
@@ -29,7 +28,7 @@ def main():
         for chunk in range(16):
             x = torch.arange(chunk * n, (chunk + 1) * n, dtype=torch.int64, device="cuda").to(torch.int32)
             x = x.view(torch.float32)
-            assert L.mibminet_test_quantize_f32(x.data_ptr(), got.data_ptr(), n, scale, 0, None) == 0
+            lib.quantize_f32_flat(x.data_ptr(), got.data_ptr(), n, scale)
             assert L.net_quantize_input_f32(x.data_ptr(), want.data_ptr(), n // T, 1, T, scale, 0, None) == 0
             torch.cuda.synchronize()
             d = got != want

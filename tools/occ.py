@@ -7,12 +7,12 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mi-bminet_amd"))
+from mibminet import lib  # noqa: E402
 from mibminet.params import ParamSet  # noqa: E402
 
 blob = ParamSet.synthetic(seed=1).to_blob()
 for p in sys.argv[1:] or [os.path.join(ROOT, "mi-bminet_amd", "mibminet", "libmibminet.so")]:
-    L = ctypes.CDLL(os.path.abspath(p), mode=ctypes.RTLD_LOCAL)
-    L.net_params_load.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
+    L = lib.bind(ctypes.CDLL(os.path.abspath(p), mode=ctypes.RTLD_LOCAL), ("net_params_load",))
     assert L.net_params_load(blob, len(blob)) == 0
     for name in ("net_launch_info", "net_launch_info_ct"):
         out = (ctypes.c_int32 * 3)()

@@ -16,6 +16,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mi-bminet_amd"))
+from mibminet import lib  # noqa: E402
 from mibminet.params import ParamSet  # noqa: E402
 
 
@@ -35,10 +36,8 @@ def main():
     ap.add_argument("--seconds", type=float, default=4.0)
     ap.add_argument("--zero", action="store_true")
     a = ap.parse_args()
-    L = ctypes.CDLL(os.path.abspath(a.lib), mode=ctypes.RTLD_LOCAL)
-    L.net_params_load.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
-    L.net_trial_stride.restype = ctypes.c_size_t
-    L.net_model_compute_batch_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+    L = lib.bind(ctypes.CDLL(os.path.abspath(a.lib), mode=ctypes.RTLD_LOCAL),
+                 ("net_params_load", "net_trial_stride", "net_model_compute_batch_async"))
     blob = ParamSet.synthetic(seed=1).to_blob()
     assert L.net_params_load(blob, len(blob)) == 0
     B = 65536
