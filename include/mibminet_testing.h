@@ -70,6 +70,14 @@ int mibminet_test_params_xr(void);
  * checked against the oracle on the same set; 0 restores the normal choice. */
 int mibminet_test_force_general(int on);
 
+/* workgroups > 0: every persistent grid launched after this call (the compiled and the general
+ * batched kernels, layer 1 over a recording, the window and the epoch loops) has at most that many
+ * workgroups, and net_launch_info[_ct] reports it, so that a few items walk a workgroup through
+ * its second and later passes at any geometry; 0 restores the normal choice (the occupancy's).
+ * No kernel reads the cap: only the grid changes.  NET_ERR_INVALID for a negative argument, which
+ * leaves the cap as it was. */
+int mibminet_test_grid_cap(int workgroups);
+
 /* FNV-1a digest of the loaded set's device parameter image (the bytes uploaded to every device):
  * equal digests mean the two loads produce the same kernels' inputs. */
 int mibminet_test_image_digest(uint64_t* digest);

@@ -121,9 +121,14 @@ gen::Carve carve_of(const gen::GenParams& g, int layout) {
   return gen::carve_of(g.C, g.T, g.N, g.T8, g.T64A, g.NB1, g.MT, g.NTT, layout);
 }
 
+// test hook (mibminet_test_grid_cap): at most this many workgroups per persistent grid (0: no cap)
+std::atomic<int> g_grid_cap{0};
+
 // persistent grid: one workgroup per item, at most what the occupancy keeps resident
 int capped_grid(const DeviceState& ds, size_t items, int blocks_per_cu) {
-  return (int)std::min(items, (size_t)ds.cus * (size_t)blocks_per_cu);
+  const size_t grid = std::min(items, (size_t)ds.cus * (size_t)blocks_per_cu);
+  const int cap = g_grid_cap.load();
+  return (int)(cap > 0 ? std::min(grid, (size_t)cap) : grid);
 }
 
 // RN(1 / scale) of the float32 entries: IEEE division on the host (0: an int8 entry)

@@ -123,6 +123,12 @@ int mibminet_test_force_general(int on) {
   return NET_OK;
 }
 
+int mibminet_test_grid_cap(int workgroups) {
+  if (workgroups < 0) return NET_ERR_INVALID;
+  g_grid_cap.store(workgroups);
+  return NET_OK;
+}
+
 int mibminet_test_params_xr(void) {
   Snapshot s = snapshot();
   if (!s.host) return NET_ERR_NO_PARAMS;

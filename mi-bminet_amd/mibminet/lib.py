@@ -87,6 +87,7 @@ PROTOTYPES = {
     "mibminet_test_pool_consts": "int (int32_t, int32_t, ptr, ptr)",
     "mibminet_test_params_xr": "int ()",
     "mibminet_test_force_general": "int (int)",
+    "mibminet_test_grid_cap": "int (int)",
     "mibminet_test_image_digest": "int (ptr)",
     "mibminet_test_image_copy": "int (int, ptr, size_t, ptr)",
     "mibminet_test_folded_filters": "int (ptr)",
@@ -279,6 +280,12 @@ def force_general(on: bool) -> None:
     """Test hook (mibminet_test_force_general): later loads run the run-time-dimension kernels
     even for the compiled geometries."""
     _check(load().mibminet_test_force_general(1 if on else 0), "mibminet_test_force_general")
+
+
+def grid_cap(workgroups: int) -> None:
+    """Test hook (mibminet_test_grid_cap): later persistent grids have at most ``workgroups``
+    workgroups, so a few items walk a workgroup through its later passes; 0 restores the normal choice."""
+    _check(load().mibminet_test_grid_cap(int(workgroups)), "mibminet_test_grid_cap")
 
 
 def folded_filters() -> int:

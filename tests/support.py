@@ -146,27 +146,41 @@ def scattered(x, junk):
 
 
 def run_entries(case, path):
-    import torch
-
+    """Every forward entry on a certified case (observability.CASES, param_faults.PCASES), which
+    must run the kernels `path` names."""
     name, ps, x = case
-    d = ps.dims
-    B = len(x)
     lib.params_load(ps)
     info = lib.params_info()
     assert info["path"] == path, info
     assert info["exact_division"] == case.exact
+    run_entries_on(name, ps, x, oracle.COracle(ps).batch(pack_trials(x), nthreads=NTH))
+
+
+def run_entries_on(name, ps, x, want, again=None):
+    """Every forward entry on the trials x [B][C][T] (int8 in [-127, 127]) of the loaded set ps:
+    each must give `want` [B][N], byte for byte, in every row.  `again`: a context manager under
+    which each batched entry runs a second time on the same input, to the same bytes."""
+    import torch
+
+    d = ps.dims
+    B = len(x)
     xp = pack_trials(x)
-    want = oracle.COracle(ps).batch(xp, nthreads=NTH)
     junk = np.random.default_rng(B + d.T)
 
     def check(got, what, rows=None):
         got = got.cpu().numpy()
+        assert got.shape == (B, d.N), f"{name} {what}: {got.shape}"
         bad = np.flatnonzero((got != (want if rows is None else want[rows])).any(1))
         assert bad.size == 0, f"{name} {what}: {bad.size} of {B} trials differ, first {bad[:5]}"
 
-    check(lib.forward_torch(torch.from_numpy(xp).cuda()), "time-major")
-    check(lib.forward_ct_torch(at_offset(torch, x, 1 + B % 3)), "channel-major")
-    check(lib.forward_f32_torch(torch.from_numpy(dequant(x)).cuda(), SCALE), "float32")
+    for what, run in (("time-major", lambda v=torch.from_numpy(xp).cuda(): lib.forward_torch(v)),
+                      ("channel-major", lambda v=at_offset(torch, x, 1 + B % 3): lib.forward_ct_torch(v)),
+                      ("float32", lambda v=torch.from_numpy(dequant(x)).cuda(): lib.forward_f32_torch(v, SCALE))):
+        got = run()
+        check(got, what)
+        if again is not None:
+            with again():
+                assert torch.equal(run(), got), f"{name} {what}: the second run differs"
     for gap in (0, 3):
         rec = trials_as_recording(x, gap, junk)
         for layout in ("ct", "tc"):

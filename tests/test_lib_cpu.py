@@ -121,6 +121,23 @@ def test_version_and_errors():
     assert b"blob" in L.net_error_string(lib.NET_ERR_BLOB)
 
 
+def test_grid_cap_hook_needs_no_device():
+    """mibminet_test_grid_cap takes 0 and positive caps without a device (the state is host-side
+    and only read when a grid is sized), refuses a negative one, and the test leaves the cap at 0."""
+    L = lib.load()
+    try:
+        for n in (0, 1, 3, 2**31 - 1, 0):
+            assert L.mibminet_test_grid_cap(n) == lib.NET_OK, n
+        for n in (-1, -(2**31)):
+            assert L.mibminet_test_grid_cap(n) == lib.NET_ERR_INVALID, n
+        lib.grid_cap(3)
+        with pytest.raises(lib.NetError) as e:
+            lib.grid_cap(-1)
+        assert e.value.code == lib.NET_ERR_INVALID
+    finally:
+        assert L.mibminet_test_grid_cap(0) == lib.NET_OK
+
+
 @pytest.mark.parametrize("C,T,wbits", [(22, 1125, 8), (64, 1000, 8), (22, 1125, 4)])
 def test_params_load_host(C, T, wbits):
     ps = ParamSet.synthetic(seed=9, C=C, T=T, weight_bits=wbits)
