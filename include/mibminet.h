@@ -323,6 +323,64 @@ int net_model_compute_epochs_f32(const float* x, size_t n_elems, size_t row_stri
                                  const int64_t* onsets, size_t E, float scale, int8_t* y, int32_t* n_bad,
                                  int device, void* stream);
 
+/* ---- parameter banks: many networks resident, one set index per epoch -------------------------
+ * A bank is an immutable collection of parameter sets of one geometry (per-subject, per-fold or
+ * per-repeat models), resident on the device side by side; the epochs-bank entries classify epoch e
+ * with set set_of[e], all in one launch ("Many networks in one call").  A bank is
+ * independent of the loaded set: creating, using and destroying one leaves the set net_params_load
+ * installed, net_params_info and the devices' copies of loaded sets as they were, and the bank
+ * entries need no loaded set. */
+typedef struct net_bank net_bank_t;
+#define NET_BANK_MAX_SETS 1024
+
+/* blobs / sizes: HOST arrays of n_sets net_params_load blobs and their lengths; scales: NULL, or
+ * n_sets input-quantiser scales (each network's own quant1 absMaxValue; the domain of
+ * net_model_compute_epochs_f32's scale).  Every blob passes the checks of net_params_load and
+ * becomes the parameter image that set has when loaded alone.  All sets must agree with set 0 on C,
+ * T, N, the REORDER_BN flag and the clip: NET_ERR_UNSUPPORTED otherwise.  A malformed or refused
+ * blob returns its own code (NET_ERR_BLOB, NET_ERR_RANGE, NET_ERR_UNSUPPORTED), a bad scale
+ * NET_ERR_INVALID or NET_ERR_RANGE; *failed (if non-NULL) is then the index of the first such set.
+ * If some sets need exact integer division (net_params_info) and others do not, every set of the
+ * bank runs in the exact-division form: the same logits, and only that bank is slower
+ * (net_bank_info reports it).  n_sets == 0 or > NET_BANK_MAX_SETS: NET_ERR_INVALID.  Host work only:
+ * no device is touched; each device receives its copy on the first call that uses the bank there.
+ * On success *bank is the new bank, otherwise NULL. */
+int net_bank_create(const void* const* blobs, const size_t* sizes, const float* scales, size_t n_sets,
+                    net_bank_t** bank, size_t* failed);
+
+/* info[0..6] = n_sets, C, T, N, exact_division (0/1), has_scales (0/1), bytes per set on the device. */
+int net_bank_info(const net_bank_t* bank, int32_t* info);
+
+/* Synchronises every device that holds a copy of the bank, frees the copies and the bank.  NULL is
+ * allowed.  Destroying a bank while a call on it is in flight in another thread, or replaying a HIP
+ * graph that captured a call on it afterwards, is the caller's error. */
+void net_bank_destroy(net_bank_t* bank);
+
+/* net_model_compute_epochs with the network chosen per epoch: x, n_elems, row_stride, channels,
+ * onsets, E, y, n_bad, device and stream are that entry's, with C and T the bank's, and so are the
+ * checks and their order (a NULL bank, NET_ERR_INVALID, stands where NET_ERR_NO_PARAMS does).
+ * set_of: DEVICE array of E int32 set indices, 4-byte aligned; NULL means set 0 for every epoch
+ * and is allowed only for a bank of one set (NET_ERR_INVALID otherwise).  Logit row e is
+ * byte-identical to what net_model_compute_epochs returns for that epoch with set set_of[e]
+ * loaded.  An index outside 0 .. n_sets - 1 is treated exactly as an invalid onset: no parameter
+ * address is formed from it, the row is N zeros and *n_bad is incremented, once per epoch even if
+ * onset and index are both invalid.  Any order of set_of is correct; GROUPING THE EPOCHS BY SET IS
+ * WHAT MAKES THE CALL FAST: each workgroup takes a contiguous range of epochs and reloads its
+ * parameters whenever the set changes from one valid epoch to the next, so a grouped list costs one
+ * reload per set and workgroup, a shuffled one nearly one per epoch.  The first call on a device
+ * uploads the bank (one allocation, one host sync); after it the entry makes no allocation and no
+ * host sync and is capturable into a HIP graph, like net_model_compute_epochs. */
+int net_model_compute_epochs_bank(const net_bank_t* bank, const int8_t* x, size_t n_elems, size_t row_stride,
+                                  const int32_t* channels, const int64_t* onsets, const int32_t* set_of, size_t E,
+                                  int8_t* y, int32_t* n_bad, int device, void* stream);
+
+/* The same for a float32 source (4-byte aligned).  No scale argument: epoch e is quantised with
+ * the scale the bank was given for set set_of[e]; NET_ERR_INVALID for a bank created without
+ * scales. */
+int net_model_compute_epochs_bank_f32(const net_bank_t* bank, const float* x, size_t n_elems, size_t row_stride,
+                                      const int32_t* channels, const int64_t* onsets, const int32_t* set_of, size_t E,
+                                      int8_t* y, int32_t* n_bad, int device, void* stream);
+
 /* Several devices from one host thread (static split, no collectives): shard i is
  * x[i] / y[i] / B[i] on devices[i] (DEVICE pointers of that device).  Every shard is enqueued
  * before any is waited for, so the devices run concurrently.  streams == NULL: each device's null

@@ -93,6 +93,14 @@ int mibminet_test_image_copy(int which, void* buf, size_t cap, size_t* bytes);
  * stay on the float requant kernels: 0 unless the set as given needed exact division. */
 int mibminet_test_folded_filters(int32_t* count);
 
+/* Parameter banks (net_bank_create, include/mibminet.h).  _copy: the host image of slice `set` of
+ * the bank, with mibminet_test_image_copy's conventions for buf, cap and *bytes (NET_ERR_INVALID
+ * for a NULL bank or a set past the last): what each device receives for that set.
+ * _device_copies: how many devices hold a copy of the bank (0 until the first call on it). */
+typedef struct net_bank net_bank_t;
+int mibminet_test_bank_copy(const net_bank_t* bank, size_t set, void* buf, size_t cap, size_t* bytes);
+int mibminet_test_bank_device_copies(const net_bank_t* bank);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,19 @@
 #include <utility>
 #include <vector>
 
+#include "forward_bank.hpp"
 #include "images.hpp"
+
+// A parameter bank (net_bank_t, include/mibminet.h): the images of its sets, immutable after
+// net_bank_create, and one device copy per device that has run a call on it.  A copy is the n_sets
+// images followed, for a bank with scales, by n_sets bank::Scale entries.  Banks live beside the
+// loaded set, not in it: nothing here touches g_set or a device's image cache.
+struct net_bank {
+  std::vector<mib::gen::GenParams> sets;
+  std::vector<mib::bank::Scale> scales;  // empty: created without scales
+  mutable std::mutex mu;                           // guards dev
+  mutable std::vector<std::pair<int, void*>> dev;  // (device, its copy): the one part a call changes
+};
 
 namespace mib {
 namespace {
@@ -165,6 +177,16 @@ void note_launch(DeviceState& ds, const void* dev, hipStream_t st) {
   }
 }
 
+// ds.cus, the device's compute units (asked once); ds.mu held.
+int ensure_cus(DeviceState& ds, int dev) {
+  if (ds.cus) return NET_OK;
+  int cus = 0;
+  hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (e != hipSuccess) return hip_err(e);
+  ds.cus = cus;
+  return NET_OK;
+}
+
 // Ensure `dev` holds image `which` of snapshot s, ds.cur[which] pointing to its copy; called with
 // ds.mu held and the device current.  The window image of a general set is the copy of its kernels'
 // image (the same bytes).
@@ -172,12 +194,7 @@ int ensure_image(DeviceState& ds, int dev, const Snapshot& s, int which) {
   if (!s.host) return NET_ERR_NO_PARAMS;
   const Image& img = s.img[which];
   if (!img.data) return NET_ERR_UNSUPPORTED;
-  if (ds.cus == 0) {
-    int cus = 0;
-    hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return hip_err(e);
-    ds.cus = cus;
-  }
+  if (const int rc = ensure_cus(ds, dev)) return rc;
   void*& cur = ds.cur[which];
   if (ds.gen[which] == s.gen && cur) return NET_OK;
   for (DevImage& im : ds.images)  // a set loaded before: its copy is still there, unchanged
@@ -232,22 +249,58 @@ int ensure_scratch(DeviceState& ds, size_t bytes) {
   return NET_OK;
 }
 
-// The entry of every call that launches on `device` with the loaded set: checks the device (unless
-// net_set_device already did), takes its lock, makes it current for the scope and ensures image
-// `which` of snapshot s.  rc != NET_OK: nothing else is valid.
+// The device copy of a bank on `dev`, uploaded on the first call there; ds.mu held and the device
+// current.  The upload is the one allocation and host sync of a bank call.
+int ensure_bank(const net_bank& b, int dev, void** copy) {
+  std::lock_guard<std::mutex> lk(b.mu);
+  for (const auto& c : b.dev)
+    if (c.first == dev) {
+      *copy = c.second;
+      return NET_OK;
+    }
+  const size_t ib = b.sets.size() * sizeof(gen::GenParams), sb = b.scales.size() * sizeof(bank::Scale);
+  void* p = nullptr;
+  hipError_t e = hipMalloc(&p, ib + sb);
+  if (e != hipSuccess) return hip_err(e);
+  e = hipMemcpy(p, b.sets.data(), ib, hipMemcpyHostToDevice);
+  if (e == hipSuccess && sb) e = hipMemcpy((char*)p + ib, b.scales.data(), sb, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(p);
+    return hip_err(e);
+  }
+  b.dev.emplace_back(dev, p);
+  *copy = p;
+  return NET_OK;
+}
+
+// The entry of every call that launches on `device`: checks the device (unless net_set_device
+// already did), takes its lock and makes it current for the scope; then, with the loaded set,
+// ensures image `which` of snapshot s, or, with a bank, the bank's copy.  rc != NET_OK: nothing
+// else is valid.
 struct DeviceScope {
   int rc;
   DeviceState& ds;
   std::unique_lock<std::mutex> lk;
   std::optional<DeviceGuard> guard;  // after lk: the caller's device comes back before the lock goes
-  void* image = nullptr;             // the device copy of the requested image
+  void* image = nullptr;             // the device copy of the requested image (of the bank)
   DeviceScope(int device, const Snapshot& s, int which, bool check = true)
       : rc(check ? check_device(device) : NET_OK), ds(g_devs[rc ? 0 : device]) {
-    if (rc) return;
+    if (enter(device)) return;
+    rc = ensure_image(ds, device, s, which);
+    image = ds.cur[which];
+  }
+  DeviceScope(int device, const net_bank& b) : rc(check_device(device)), ds(g_devs[rc ? 0 : device]) {
+    if (enter(device)) return;
+    rc = ensure_cus(ds, device);
+    if (rc == NET_OK) rc = ensure_bank(b, device, &image);
+  }
+
+ private:
+  int enter(int device) {
+    if (rc) return rc;
     lk = std::unique_lock<std::mutex>(ds.mu);
     guard.emplace(device);
-    rc = guard->err != hipSuccess ? hip_err(guard->err) : ensure_image(ds, device, s, which);
-    image = ds.cur[which];
+    return rc = guard->err != hipSuccess ? hip_err(guard->err) : NET_OK;
   }
 };
 

@@ -611,9 +611,9 @@ __device__ __forceinline__ Lds lds_of(const GenParams* __restrict__ gp, int8_t* 
   return Lds{cv, (SmallG*)(smem + cv.sg), smem, smem + cv.y2, smem + cv.y3, smem + cv.y4, smem + cv.w5};
 }
 
-// The wave's layer-2 constants and the LDS initialisation shared by every kernel of the family.
-__device__ __forceinline__ void setup(const GenParams* __restrict__ gp, const Lds& m, L2C& k2, int tid, int wave,
-                                      int lane) {
+// What setup() brings in of one parameter set, in two pieces that a kernel changing sets between
+// items (forward_bank.hpp) runs again: the wave's layer-2 constants ...
+__device__ __forceinline__ void set_l2c(const GenParams* __restrict__ gp, L2C& k2, int wave, int lane) {
 #pragma unroll
   for (int fi = 0; fi < 2; fi++) {
     const int f = 2 * wave + fi;
@@ -628,9 +628,9 @@ __device__ __forceinline__ void setup(const GenParams* __restrict__ gp, const Ld
     k2.r[fi] = gp->l2_r[f];
     k2.c[fi] = gp->l2_c[f];
   }
-  // zero pads of every row (positions past the data are never rewritten), then the small params
-  v4i* z = (v4i*)m.y1;
-  for (int i = tid; i < m.cv.sg / 16; i += NT) z[i] = (v4i){0, 0, 0, 0};
+}
+// ... and the LDS copies of the small params, the layer-5 rows and the biases.
+__device__ __forceinline__ void set_lds(const GenParams* __restrict__ gp, const Lds& m, int tid) {
   const v4i* src = (const v4i*)&gp->sg;
   v4i* dst = (v4i*)m.sg;
   for (int i = tid; i < (int)(sizeof(SmallG) / 16); i += NT) dst[i] = src[i];
@@ -643,12 +643,41 @@ __device__ __forceinline__ void setup(const GenParams* __restrict__ gp, const Ld
   for (int n = tid; n < gp->N; n += NT) w5[gp->N * rp + n] = gp->l5_b[n];
 }
 
+// The wave's layer-2 constants and the LDS initialisation shared by every kernel of the family.
+__device__ __forceinline__ void setup(const GenParams* __restrict__ gp, const Lds& m, L2C& k2, int tid, int wave,
+                                      int lane) {
+  set_l2c(gp, k2, wave, lane);
+  // zero pads of every row (positions past the data are never rewritten), then the small params
+  v4i* z = (v4i*)m.y1;
+  for (int i = tid; i < m.cv.sg / 16; i += NT) z[i] = (v4i){0, 0, 0, 0};
+  set_lds(gp, m, tid);
+}
+
 // Layers 4-5 of the trial whose layer-3 rows are in y3, on one wave: its logits -> out[N].
 template <bool RB, bool XR, bool CB>
 __device__ __forceinline__ void finish_trial(const GenParams* __restrict__ gp, const Lds& m, int8_t* out, int lane) {
   layer4<RB, XR, CB>(gp, m.y3, m.y4, m.sg, lane, 0, 1);
   wg::wave_sync_lds();
   layer5<CB>(gp, m.y4, m.w5, out, 0, 1, lane);
+}
+
+// What the last wave owes the previous item of a persistent loop (item_loop's `prev`: i valid,
+// -2 - i invalid, -1 none): its layers 4-5, or a zero logit row and a count in *n_bad.
+template <bool RB, bool XR, bool CB, bool ONSETS>
+__device__ __forceinline__ void finish_prev(const GenParams* __restrict__ gp, const Lds& m, int8_t* __restrict__ out,
+                                            int* __restrict__ n_bad, int prev, int N, int lane) {
+  if (prev != -1) {
+    const bool vprev = !ONSETS || prev >= 0;
+    int8_t* o = out + (size_t)(vprev ? prev : -2 - prev) * N;
+    if (vprev) {
+      __builtin_amdgcn_s_setprio(wg::PRIO_L45);
+      finish_trial<RB, XR, CB>(gp, m, o, lane);
+      __builtin_amdgcn_s_setprio(0);
+    } else {
+      if (lane < N) o[lane] = 0;
+      if (lane == 0 && n_bad) atomicAdd(n_bad, 1);
+    }
+  }
 }
 
 // The persistent loop of the kernels that read their items where they lie (win::k_forward_y1,
@@ -685,18 +714,7 @@ __device__ __forceinline__ void item_loop(const GenParams* __restrict__ gp, cons
     if (wave < NW - 1) {
       if (more) src.rows(it);
     } else {
-      if (prev != -1) {
-        const bool vprev = !S::ONSETS || prev >= 0;
-        int8_t* o = out + (size_t)(vprev ? prev : -2 - prev) * N;
-        if (vprev) {
-          __builtin_amdgcn_s_setprio(wg::PRIO_L45);
-          finish_trial<RB, XR, CB>(gp, m, o, lane);
-          __builtin_amdgcn_s_setprio(0);
-        } else {
-          if (lane < N) o[lane] = 0;
-          if (lane == 0 && n_bad) atomicAdd(n_bad, 1);
-        }
-      }
+      finish_prev<RB, XR, CB, S::ONSETS>(gp, m, out, n_bad, prev, N, lane);
       if (more) src.rows_last(it);
     }
     MIB_STAMP(0)

@@ -27,6 +27,7 @@
 #include "forward_gen.hpp"
 #include "forward_win.hpp"
 #include "forward_ep.hpp"
+#include "forward_bank.hpp"
 #include "quantize.hpp"
 #include "classify.hpp"
 #include "device_state.hpp"
@@ -356,26 +357,30 @@ size_t windows_multi(const size_t* lengths, size_t R, size_t hop, int64_t* onset
 // ---- epochs cut out of a wider array (forward_ep.hpp) -----------------------------------------
 // f32: the float32 entry (scale qs).  Every argument and parameter check comes before the first
 // device call.
-int epochs_async(const void* x, bool f32, size_t n_elems, size_t row_stride, const int32_t* channels,
-                 const int64_t* onsets, size_t E, float qs, int8_t* y, int32_t* n_bad, int device, void* stream) {
-  const Snapshot s = snapshot();
-  if (!s.host) return NET_ERR_NO_PARAMS;
-  const Dims& d = s.host->d;
+// The argument checks both epochs entries share (the loaded set's and a bank's), in their documented
+// order, for a network of C channels and T samples; on NET_OK what the kernels take of the geometry.
+struct EpochGeom {
+  ep::ChanTab tab;
+  long long last;       // n_elems - span, the largest valid onset
+  unsigned span_bytes;
+};
+int check_epochs(int C, int T, const void* x, bool f32, size_t n_elems, size_t row_stride, const int32_t* channels,
+                 const int64_t* onsets, size_t E, const int8_t* y, const int32_t* n_bad, int device, EpochGeom& g) {
   if (E && (!x || !y || !onsets)) return NET_ERR_INVALID;
   if (((uintptr_t)y & 3) != 0 || ((uintptr_t)n_bad & 3) != 0 || ((uintptr_t)onsets & 7) != 0) return NET_ERR_INVALID;
   if (f32 && ((uintptr_t)x & 3) != 0) return NET_ERR_INVALID;
   if (row_stride == 0) return NET_ERR_INVALID;
-  size_t cmax = (size_t)d.C - 1;  // channels == NULL: rows 0 .. C - 1
+  size_t cmax = (size_t)C - 1;  // channels == NULL: rows 0 .. C - 1
   if (channels) {
     cmax = 0;
-    for (int c = 0; c < d.C; c++) {
+    for (int c = 0; c < C; c++) {
       if (channels[c] < 0) return NET_ERR_INVALID;
       cmax = std::max(cmax, (size_t)channels[c]);
     }
   }
   // span = max(channels) row_stride + T elements, inside the source
-  if (cmax && row_stride > (SIZE_MAX - (size_t)d.T) / cmax) return NET_ERR_INVALID;
-  const size_t span = cmax * row_stride + (size_t)d.T;
+  if (cmax && row_stride > (SIZE_MAX - (size_t)T) / cmax) return NET_ERR_INVALID;
+  const size_t span = cmax * row_stride + (size_t)T;
   if (span > n_elems) return NET_ERR_INVALID;
   // each epoch is one buffer view with 32-bit offsets (delta <= 3 and the dword rounding on top)
   const size_t esz = f32 ? sizeof(float) : 1;
@@ -383,14 +388,25 @@ int epochs_async(const void* x, bool f32, size_t n_elems, size_t row_stride, con
   // epoch indices are int in the kernel: e + gridDim.x (grid <= 2 per CU) must not wrap
   if (E > (size_t)INT32_MAX - 65535) return NET_ERR_INVALID;
   if (device < 0 || device >= MAX_DEVICES) return NET_ERR_INVALID;
+  for (int c = 0; c < 64; c++) g.tab.c[c] = c < C ? (channels ? channels[c] : c) : 0;
+  g.last = (long long)std::min(n_elems - span, (size_t)INT64_MAX);
+  g.span_bytes = (unsigned)(esz * span);
+  return NET_OK;
+}
+
+int epochs_async(const void* x, bool f32, size_t n_elems, size_t row_stride, const int32_t* channels,
+                 const int64_t* onsets, size_t E, float qs, int8_t* y, int32_t* n_bad, int device, void* stream) {
+  const Snapshot s = snapshot();
+  if (!s.host) return NET_ERR_NO_PARAMS;
+  const Dims& d = s.host->d;
+  EpochGeom g;
+  if (const int rc = check_epochs(d.C, d.T, x, f32, n_elems, row_stride, channels, onsets, E, y, n_bad, device, g))
+    return rc;
   if (f32)
     if (const int rc = check_scale(qs)) return rc;
   const Image& win = s.img[IMG_WINDOWS];
   if (!win.data) return NET_ERR_UNSUPPORTED;
   if (E == 0) return NET_OK;
-  ep::ChanTab tab;
-  for (int c = 0; c < 64; c++) tab.c[c] = c < d.C ? (channels ? channels[c] : c) : 0;
-  const long long last = (long long)std::min(n_elems - span, (size_t)INT64_MAX);  // n_elems - span
   DeviceScope sc(device, s, IMG_WINDOWS);
   if (sc.rc) return sc.rc;
   const gen::GenParams& hg = *(const gen::GenParams*)win.data.get();
@@ -399,13 +415,106 @@ int epochs_async(const void* x, bool f32, size_t n_elems, size_t row_stride, con
   return with_flags(hg, [&](auto rb, auto xr, auto cb) {
     auto go = [&](auto kern) {
       const int rc = launch_items(sc.ds, kern, lds, E, st, (const gen::GenParams*)sc.image, (const int8_t*)x,
-                                  (const long long*)onsets, y, (int*)n_bad, (int)E, last, (unsigned)(esz * span),
-                                  (unsigned long long)row_stride, tab, qs, recip_scale(qs));
+                                  (const long long*)onsets, y, (int*)n_bad, (int)E, g.last, g.span_bytes,
+                                  (unsigned long long)row_stride, g.tab, qs, recip_scale(qs));
       if (rc == NET_OK) note_launch(sc.ds, sc.image, st);
       return rc;
     };
     constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
     return f32 ? go(ep::k_forward_ep<gen::F32, RB, XR, CB>) : go(ep::k_forward_ep<gen::CT, RB, XR, CB>);
+  });
+}
+
+// ---- parameter banks (forward_bank.hpp, bank_host.hpp) ---------------------------------------
+// One set of a bank: the blob through the loader's own path (parse_blob, build_set), its window
+// image kept.  hp comes back as build_set leaves it.
+int bank_set(const void* blob, size_t len, HostParams& hp, gen::GenParams& gp) {
+  if (const int rc = parse_blob(blob, len, hp)) return rc;
+  Image img, win;
+  if (const int rc = build_set(hp, g_force_general.load() != 0, &img, &win)) return rc;
+  if (!win.data) return NET_ERR_UNSUPPORTED;
+  gp = *(const gen::GenParams*)win.data.get();
+  return NET_OK;
+}
+
+// The image of a float set in the exact-division form (bank::force_exact), for a bank some other set
+// of which needs exact division.
+int bank_set_exact(const HostParams& hp, gen::GenParams& gp) {
+  Ranges rg;
+  if (const int rc = check_ranges(hp, rg)) return rc;
+  Plan pl = make_plan(hp, rg);
+  bank::force_exact(hp, pl);
+  return build_genparams(hp, pl, gp);
+}
+
+int bank_create(const void* const* blobs, const size_t* sizes, const float* scales, size_t n_sets, net_bank** out,
+                size_t* failed) {
+  if (out) *out = nullptr;
+  if (!blobs || !sizes || !out || n_sets == 0 || n_sets > NET_BANK_MAX_SETS) return NET_ERR_INVALID;
+  auto fail = [&](size_t i, int rc) {
+    if (failed) *failed = i;
+    return rc;
+  };
+  auto b = std::make_unique<net_bank>();
+  b->sets.resize(n_sets);
+  std::vector<HostParams> hps(n_sets);
+  bool any_xr = false, all_xr = true;
+  for (size_t i = 0; i < n_sets; i++) {
+    if (const int rc = bank_set(blobs[i], sizes[i], hps[i], b->sets[i])) return fail(i, rc);
+    if (!bank::agree(hps[0], hps[i])) return fail(i, NET_ERR_UNSUPPORTED);
+    if (scales) {
+      if (const int rc = check_scale(scales[i])) return fail(i, rc);
+      b->scales.push_back(bank::Scale{scales[i], recip_scale(scales[i])});
+    }
+    any_xr = any_xr || b->sets[i].xr;
+    all_xr = all_xr && b->sets[i].xr;
+  }
+  if (any_xr && !all_xr)
+    for (size_t i = 0; i < n_sets; i++)
+      if (!b->sets[i].xr)
+        if (const int rc = bank_set_exact(hps[i], b->sets[i])) return fail(i, rc);
+  *out = b.release();
+  return NET_OK;
+}
+
+void bank_destroy(net_bank* b) {
+  if (!b) return;
+  for (const auto& c : b->dev) {
+    DeviceState& ds = g_devs[c.first];
+    std::lock_guard<std::mutex> lk(ds.mu);
+    DeviceGuard guard(c.first);
+    if (guard.err == hipSuccess) (void)hipDeviceSynchronize();  // no launch still reads the copy
+    (void)hipFree(c.second);
+  }
+  delete b;
+}
+
+// epochs_async on a bank: the same checks in the same order, C and T the bank's; then the set
+// indices' and, for float input, the bank's scales.
+int bank_epochs_async(const net_bank* b, const void* x, bool f32, size_t n_elems, size_t row_stride,
+                      const int32_t* channels, const int64_t* onsets, const int32_t* set_of, size_t E, int8_t* y,
+                      int32_t* n_bad, int device, void* stream) {
+  if (!b) return NET_ERR_INVALID;
+  const gen::GenParams& hg = b->sets[0];
+  EpochGeom g;
+  if (const int rc = check_epochs(hg.C, hg.T, x, f32, n_elems, row_stride, channels, onsets, E, y, n_bad, device, g))
+    return rc;
+  if (((uintptr_t)set_of & 3) != 0 || (E && !set_of && b->sets.size() != 1)) return NET_ERR_INVALID;
+  if (f32 && b->scales.empty()) return NET_ERR_INVALID;
+  if (E == 0) return NET_OK;
+  DeviceScope sc(device, *b);
+  if (sc.rc) return sc.rc;
+  const auto* sets = (const gen::GenParams*)sc.image;
+  const auto* scales = f32 ? (const bank::Scale*)(sets + b->sets.size()) : nullptr;
+  const int lds = carve_of(hg, gen::F32).bytes;
+  return with_flags(hg, [&](auto rb, auto xr, auto cb) {
+    auto go = [&](auto kern) {
+      return launch_items(sc.ds, kern, lds, E, (hipStream_t)stream, sets, (int)b->sets.size(), (const int*)set_of, scales,
+                          (const int8_t*)x, (const long long*)onsets, y, (int*)n_bad, (int)E, g.last, g.span_bytes,
+                          (unsigned long long)row_stride, g.tab);
+    };
+    constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
+    return f32 ? go(bank::k_forward_ep_bank<gen::F32, RB, XR, CB>) : go(bank::k_forward_ep_bank<gen::CT, RB, XR, CB>);
   });
 }
 
@@ -789,6 +898,33 @@ int net_model_compute_epochs_f32(const float* x, size_t n_elems, size_t row_stri
                                  const int64_t* onsets, size_t E, float scale, int8_t* y, int32_t* n_bad,
                                  int device, void* stream) {
   return epochs_async(x, true, n_elems, row_stride, channels, onsets, E, scale, y, n_bad, device, stream);
+}
+
+int net_bank_create(const void* const* blobs, const size_t* sizes, const float* scales, size_t n_sets,
+                    net_bank_t** bank, size_t* failed) {
+  return bank_create(blobs, sizes, scales, n_sets, bank, failed);
+}
+
+int net_bank_info(const net_bank_t* bank, int32_t* info) {
+  if (!bank || !info) return NET_ERR_INVALID;
+  const gen::GenParams& g = bank->sets[0];
+  info[0] = (int32_t)bank->sets.size(); info[1] = g.C; info[2] = g.T; info[3] = g.N; info[4] = g.xr;
+  info[5] = bank->scales.empty() ? 0 : 1; info[6] = (int32_t)sizeof(gen::GenParams);
+  return NET_OK;
+}
+
+void net_bank_destroy(net_bank_t* bank) { bank_destroy(bank); }
+
+int net_model_compute_epochs_bank(const net_bank_t* bank, const int8_t* x, size_t n_elems, size_t row_stride,
+                                  const int32_t* channels, const int64_t* onsets, const int32_t* set_of, size_t E,
+                                  int8_t* y, int32_t* n_bad, int device, void* stream) {
+  return bank_epochs_async(bank, x, false, n_elems, row_stride, channels, onsets, set_of, E, y, n_bad, device, stream);
+}
+
+int net_model_compute_epochs_bank_f32(const net_bank_t* bank, const float* x, size_t n_elems, size_t row_stride,
+                                      const int32_t* channels, const int64_t* onsets, const int32_t* set_of, size_t E,
+                                      int8_t* y, int32_t* n_bad, int device, void* stream) {
+  return bank_epochs_async(bank, x, true, n_elems, row_stride, channels, onsets, set_of, E, y, n_bad, device, stream);
 }
 
 int net_quantize_input_f32(const float* x, int8_t* y, size_t B, int C, int T, float scale, int device, void* stream) {

@@ -142,4 +142,21 @@ int mibminet_test_device_images(int device) {
   return (int)ds.images.size();
 }
 
+int mibminet_test_bank_copy(const net_bank_t* bank, size_t set, void* buf, size_t cap, size_t* bytes) {
+  if (!bytes) return NET_ERR_INVALID;
+  *bytes = 0;
+  if (!bank || set >= bank->sets.size()) return NET_ERR_INVALID;
+  *bytes = sizeof(gen::GenParams);
+  if (!buf) return NET_OK;
+  if (cap < *bytes) return NET_ERR_INVALID;
+  std::memcpy(buf, &bank->sets[set], *bytes);
+  return NET_OK;
+}
+
+int mibminet_test_bank_device_copies(const net_bank_t* bank) {
+  if (!bank) return NET_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(bank->mu);
+  return (int)bank->dev.size();
+}
+
 }  // extern "C"

@@ -90,6 +90,41 @@ def evaluate(ps: ParamSet, samples, labels, scale: float, predictions=None, devi
     return out
 
 
+def _score(got: np.ndarray, labels: np.ndarray, N: int) -> Dict[str, object]:
+    conf = np.zeros((N, N), np.int64)  # [label][prediction]
+    ok = (labels >= 0) & (labels < N)
+    np.add.at(conf, (labels[ok], got[ok]), 1)
+    return {"n": int(got.shape[0]), "correct": int((got == labels).sum()),
+            "accuracy": float((got == labels).mean()) if got.size else 0.0, "confusion": conf.tolist()}
+
+
+def evaluate_bank(param_sets, scales, samples, labels, set_of, device: str = "cuda:0") -> Dict[str, object]:
+    """Accuracy of many networks of one geometry (per-subject, per-fold models) on one labelled set:
+    trial i is classified by ``param_sets[set_of[i]]`` with the input scale ``scales[set_of[i]]``.
+    One float32 bank call (``lib.forward_bank_torch``: no parameter load per network, no int8 copy
+    of the samples) and one ``argmax_torch``.  ``samples``: float32 [n][C][T].  Returns evaluate's
+    "n", "correct", "accuracy" and "confusion" over all trials, and under "per_set" the same for
+    the trials of each set.  Trials grouped by set run fastest."""
+    import torch
+
+    labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+    set_of = np.asarray(set_of, dtype=np.int64).reshape(-1)
+    n_sets = len(param_sets)
+    if set_of.shape != labels.shape or (set_of.size and (set_of.min() < 0 or set_of.max() >= n_sets)):
+        raise ValueError(f"set_of must hold one index below {n_sets} per label")
+    x = torch.as_tensor(samples, dtype=torch.float32).to(device).contiguous()
+    with lib.Bank(param_sets, scales) as bank:
+        so = torch.as_tensor(set_of, dtype=torch.int32)
+        cls = lib.argmax_torch(lib.forward_bank_torch(bank, x, so, check=False))
+        got = cls.cpu().numpy().astype(np.int64)  # (the copy waits for the launches: the bank may go)
+        N = bank.dims.N
+    if got.shape != labels.shape:
+        raise ValueError(f"{labels.shape[0]} labels for {got.shape[0]} samples")
+    out = _score(got, labels, N)
+    out["per_set"] = [_score(got[set_of == s], labels[set_of == s], N) for s in range(n_sets)]
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--net", required=True, help="QuantLab export net.npz (export_net_data.py:83-84)")

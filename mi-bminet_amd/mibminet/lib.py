@@ -65,6 +65,11 @@ PROTOTYPES = {
     "net_windows_multi_onsets": "size_t (ptr, size_t, size_t, ptr, size_t, ptr)",
     "net_model_compute_epochs": "int (ptr, size_t, size_t, ptr, ptr, size_t, ptr, ptr, int, ptr)",
     "net_model_compute_epochs_f32": "int (ptr, size_t, size_t, ptr, ptr, size_t, float, ptr, ptr, int, ptr)",
+    "net_bank_create": "int (ptr, ptr, ptr, size_t, ptr, ptr)",
+    "net_bank_info": "int (ptr, ptr)",
+    "net_bank_destroy": "void (ptr)",
+    "net_model_compute_epochs_bank": "int (ptr, ptr, size_t, size_t, ptr, ptr, ptr, size_t, ptr, ptr, int, ptr)",
+    "net_model_compute_epochs_bank_f32": "int (ptr, ptr, size_t, size_t, ptr, ptr, ptr, size_t, ptr, ptr, int, ptr)",
     "net_model_compute_batch_multi": "int (int, ptr, ptr, ptr, ptr, ptr)",
     "net_model_compute_batch_multi_ct": "int (int, ptr, ptr, ptr, ptr, ptr)",
     "net_quantize_input_f32": "int (ptr, ptr, size_t, int, int, float, int, ptr)",
@@ -91,6 +96,8 @@ PROTOTYPES = {
     "mibminet_test_image_digest": "int (ptr)",
     "mibminet_test_image_copy": "int (int, ptr, size_t, ptr)",
     "mibminet_test_folded_filters": "int (ptr)",
+    "mibminet_test_bank_copy": "int (ptr, size_t, ptr, size_t, ptr)",
+    "mibminet_test_bank_device_copies": "int (ptr)",
 }
 EXPORTED_SYMBOLS = tuple(n for n in PROTOTYPES if n.startswith("net_"))
 NET_PATH_FLOAT, NET_PATH_EXACT, NET_PATH_GENERAL = 0, 1, 2
@@ -189,6 +196,87 @@ def _dims():
     if _loaded is None:
         raise NetError(NET_ERR_NO_PARAMS, "no parameters loaded")
     return _loaded.dims
+
+
+class Bank:
+    """net_bank_create: many parameter sets of one geometry resident side by side, for
+    forward_epochs_bank_torch and forward_bank_torch.  ``param_sets`` holds ParamSets or blobs,
+    ``scales`` nothing or one input-quantiser scale per set (needed for float32 input).  Independent
+    of the loaded set.  A set the library refuses raises NetError with its index in ``.failed``.
+    ``close()`` (or leaving the ``with`` block) frees the bank and its device copies after
+    synchronising the devices that hold one; no call on the bank may be in flight then."""
+
+    def __init__(self, param_sets, scales=None):
+        self._h = None
+        blobs = [p.to_blob() if isinstance(p, ParamSet) else bytes(p) for p in param_sets]
+        n = len(blobs)
+        if scales is not None and len(scales) != n:
+            raise ValueError(f"{len(scales)} scales for {n} parameter sets")
+        bufs = [ctypes.create_string_buffer(b, len(b)) for b in blobs]
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[ctypes.addressof(b) for b in bufs])
+        sizes = (ctypes.c_size_t * max(n, 1))(*[len(b) for b in blobs])
+        sc = None if scales is None else (ctypes.c_float * max(n, 1))(*[float(v) for v in scales])
+        h, failed = ctypes.c_void_p(), ctypes.c_size_t(0)
+        rc = load().net_bank_create(ptrs, sizes, sc, n, ctypes.byref(h), ctypes.byref(failed))
+        if rc != NET_OK:
+            err = NetError(rc, f"net_bank_create, set {failed.value}" if n else "net_bank_create")
+            err.failed = failed.value
+            raise err
+        self._h = h.value
+        info = self.info()
+        self.n_sets, self.exact_division, self.has_scales = info[0], bool(info[4]), bool(info[5])
+        self.dims = ParamSet.from_blob(blobs[0]).dims
+
+    @property
+    def handle(self) -> int:
+        if self._h is None:
+            raise ValueError("the bank is closed")
+        return self._h
+
+    def info(self) -> list:
+        """net_bank_info: [n_sets, C, T, N, exact_division, has_scales, bytes per set]."""
+        arr = (ctypes.c_int32 * 7)()
+        _check(load().net_bank_info(self.handle, arr), "net_bank_info")
+        return list(arr)
+
+    def image(self, s: int) -> bytes:
+        """Test hook (mibminet_test_bank_copy): the parameter image of set ``s`` as the devices get it."""
+        n = ctypes.c_size_t(0)
+        _check(load().mibminet_test_bank_copy(self.handle, s, None, 0, ctypes.byref(n)), "mibminet_test_bank_copy")
+        buf = ctypes.create_string_buffer(n.value)
+        _check(load().mibminet_test_bank_copy(self.handle, s, buf, n.value, ctypes.byref(n)), "mibminet_test_bank_copy")
+        return buf.raw
+
+    def device_copies(self) -> int:
+        """Test hook (mibminet_test_bank_device_copies): devices that hold a copy of the bank."""
+        return int(load().mibminet_test_bank_device_copies(self.handle))
+
+    def close(self) -> None:
+        if self._h is not None:
+            load().net_bank_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover - interpreter shutdown
+            pass
+
+
+def image_copy(which: int) -> bytes:
+    """Test hook (mibminet_test_image_copy): image ``which`` of the loaded set (0 the batched
+    kernels', 1 the window and epoch kernels')."""
+    n = ctypes.c_size_t(0)
+    _check(load().mibminet_test_image_copy(which, None, 0, ctypes.byref(n)), "mibminet_test_image_copy")
+    buf = ctypes.create_string_buffer(n.value)
+    _check(load().mibminet_test_image_copy(which, buf, n.value, ctypes.byref(n)), "mibminet_test_image_copy")
+    return buf.raw
 
 
 # ---- reference single-trial API (host arrays, reference layouts) --------------------------------
@@ -521,35 +609,53 @@ def forward_windows_f32_torch(x, hop: int, scale: float, stream=None):
     return y
 
 
-def _forward_onsets(name: str, x, head, onsets, scale, mid, stream, check: bool, noun: str):
+def _forward_onsets(name: str, x, head, onsets, scale, mid, stream, check: bool, noun: str, bank=None, set_of=None):
     """The call of an entry that takes an onset list, ``name`` or, with a ``scale``, ``name``_f32:
     entry(x, *head, onsets, n, [scale,] y, n_bad, *mid, device, stream).  ``onsets`` is a 1-D int64
     tensor or a sequence of ints; its device copy and, with ``check``, the zeroed counter are made
     on the launch stream.  An empty list passes NULL for the onsets and the logits, ``check=False``
     NULL for the counter.  With ``check`` and a non-empty list the stream is synchronised, the
     count of onsets outside the ``noun`` read back and a ValueError raised if it is not zero.
-    Returns the logits [n][N]."""
+    Returns the logits [n][N].
+    With a ``bank`` (a Bank) the entry is ``name``, or ``name``_f32 for a float32 ``x``, and takes
+    no scale: entry(bank, x, *head, onsets, set_of, n, y, n_bad, *mid, device, stream).  ``set_of``
+    is a 1-D int32 tensor or a sequence of as many ints as there are onsets, copied like them, or
+    None (NULL: set 0 for every item, a bank of one set only); the count then covers set indices
+    outside the bank too."""
     torch = _torch()
     if not isinstance(onsets, torch.Tensor):
         onsets = torch.as_tensor([int(o) for o in onsets], dtype=torch.int64).reshape(-1)
     elif onsets.dtype != torch.int64 or onsets.dim() != 1:
         raise ValueError("onsets must be a 1-D int64 tensor or a sequence of ints")
+    n = int(onsets.numel())
+    if set_of is not None:
+        if not isinstance(set_of, torch.Tensor):
+            set_of = torch.as_tensor([int(v) for v in set_of], dtype=torch.int32).reshape(-1)
+        elif set_of.dtype != torch.int32 or set_of.dim() != 1:
+            raise ValueError("set_of must be a 1-D int32 tensor or a sequence of ints")
+        if int(set_of.numel()) != n:
+            raise ValueError(f"{int(set_of.numel())} set indices for {n} onsets")
+    elif bank is not None and bank.n_sets != 1:
+        raise ValueError(f"set_of may be None only for a bank of one set, this one has {bank.n_sets}")
     s, dev = _launch(x, stream)
-    with torch.cuda.stream(s):  # the onsets' copy and the counter's zeroing precede the launch on its stream
+    with torch.cuda.stream(s):  # the lists' copies and the counter's zeroing precede the launch on its stream
         on = onsets.to(x.device).contiguous()
+        so = None if set_of is None else set_of.to(x.device).contiguous()
         nbad = torch.zeros((1,), dtype=torch.int32, device=x.device) if check else None
-    n = int(on.numel())
-    y = _logits(x, n)
-    if scale is not None:
+    y = _logits(x, n) if bank is None else torch.empty((n, bank.dims.N), dtype=torch.int8, device=x.device)
+    if scale is not None or (bank is not None and x.dtype == torch.float32):
         name += "_f32"
-    _check(getattr(load(), name)(x.data_ptr(), *head, on.data_ptr() if n else None, n,
+    _check(getattr(load(), name)(*(() if bank is None else (bank.handle,)), x.data_ptr(), *head,
+                                 on.data_ptr() if n else None,
+                                 *(() if bank is None else (so.data_ptr() if n and so is not None else None,)), n,
                                  *(() if scale is None else (scale,)), y.data_ptr() if n else None,
                                  nbad.data_ptr() if check else None, *mid, dev, s.cuda_stream), name)
     if check and n:
         s.synchronize()
         bad = int(nbad.item())
         if bad:
-            raise ValueError(f"{bad} of {n} onsets lie outside the {noun} (their logit rows are zero)")
+            what = "onsets" if bank is None else "onsets or set indices"
+            raise ValueError(f"{bad} of {n} {what} lie outside the {noun} (their logit rows are zero)")
     return y
 
 
@@ -723,6 +829,47 @@ def forward_crop_torch(x, t0: int, channels=None, scale: Optional[float] = None,
         onsets = torch.arange(B, dtype=torch.int64, device=x.device) * (R * Tf) + t0
     # every onset is in range by the checks above: no counter, no host sync
     return forward_epochs_torch(x, onsets, channels=ch, row_stride=Tf, scale=scale, stream=s, check=False)
+
+
+def forward_epochs_bank_torch(bank, x, onsets, set_of, channels=None, row_stride: Optional[int] = None, stream=None,
+                              check: bool = True):
+    """net_model_compute_epochs_bank / _f32: forward_epochs_torch with the network chosen per
+    epoch: epoch e is classified by set ``set_of[e]`` of ``bank`` (a Bank; the loaded set plays no
+    part).  ``x``, ``onsets``, ``channels`` and ``row_stride`` are forward_epochs_torch's, C and T
+    the bank's; a float32 ``x`` needs a bank with scales and is quantised with the scale of each
+    epoch's set.  ``set_of`` is an int32 tensor or a sequence, one index per onset (None: a bank of
+    one set).  Returns the logits [E][N] int8, row e what forward_epochs_torch returns for that
+    epoch with set ``set_of[e]`` loaded.  Any order is correct; grouped by set is fast.  The rows
+    of invalid onsets and of indices outside the bank are zero; with ``check`` their count is read
+    back (a host sync) and a ValueError names it."""
+    if not isinstance(bank, Bank):
+        raise ValueError(f"bank must be a Bank, got {type(bank).__name__}")
+    d = bank.dims
+    f32 = _check_tensor(x, "x", ("int8", "float32")) == "float32"
+    if f32 and not bank.has_scales:
+        raise ValueError("a float32 source needs a bank created with scales")
+    if x.dim() < 1:
+        raise ValueError("x must have at least one dimension")
+    rs = int(x.shape[-1]) if row_stride is None else int(row_stride)
+    if rs < 1:
+        raise ValueError("row_stride must be at least 1")
+    return _forward_onsets("net_model_compute_epochs_bank", x, (x.numel(), rs, _channel_table(channels, d.C)), onsets,
+                           None, (), stream, check, "source or the bank", bank=bank, set_of=set_of)
+
+
+def forward_bank_torch(bank, x, set_of, stream=None, check: bool = True):
+    """A batch ``x`` [B][C][T] (int8, or float32 for a bank with scales), trial b classified by set
+    ``set_of[b]`` of ``bank``, through forward_epochs_bank_torch as forward_crop_torch does it:
+    row_stride = T, onsets[b] = b C T, built on the device.  Returns the logits [B][N]."""
+    torch = _torch()
+    if not isinstance(bank, Bank):
+        raise ValueError(f"bank must be a Bank, got {type(bank).__name__}")
+    d = bank.dims
+    _check_tensor(x, "x", ("int8", "float32"), ("B", d.C, d.T))
+    s, _ = _launch(x, stream)
+    with torch.cuda.stream(s):
+        onsets = torch.arange(x.shape[0], dtype=torch.int64, device=x.device) * (d.C * d.T)
+    return forward_epochs_bank_torch(bank, x, onsets, set_of, row_stride=d.T, stream=s, check=check)
 
 
 def quantize_input_torch(x, scale: float, stream=None):
