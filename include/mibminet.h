@@ -381,6 +381,66 @@ int net_model_compute_epochs_bank_f32(const net_bank_t* bank, const float* x, si
                                       const int32_t* channels, const int64_t* onsets, const int32_t* set_of, size_t E,
                                       int8_t* y, int32_t* n_bad, int device, void* stream);
 
+/* ---- windows through a bank: many recordings, each with its own network ----------------------
+ * The windows-at entries with the network chosen per recording.  R recordings lie along time in one
+ * array x of L samples, in the layouts of net_model_compute_windows[_f32] (0 = [L][C] int8, 1 =
+ * [C][L] int8; float32 [C][L]).  Recording r starts at starts[r], a multiple of 16 samples:
+ * starts[0] = 0, starts[r+1] = starts[r] + lengths[r] rounded up to 16, and L = starts[R-1] +
+ * lengths[R-1] (no rounding after the last recording); the pad samples between recordings may hold
+ * anything.  blk_set (DEVICE, ceil(L/16) int32, 4-byte aligned) names the set of each 16-sample
+ * block: samples 16b .. 16b+15 are processed by set blk_set[b].  C, T and N are the bank's; no
+ * loaded set is needed, and the loaded set, net_params_info and the image cache are untouched.
+ * Workspace: ws is the [16][net_windows_row_stride(L)] workspace of the windows entries.  For a
+ * block with s = blk_set[b] in 0 .. n_sets-1, after the call ws[f][t] is the reference net_layer1
+ * output of sample t under set s, for t in the block and t < L (the float entry quantises each
+ * sample with set s's scale first, as net_quantize_input_f32 does).  For any other value of
+ * blk_set[b] no parameter address is formed and the block's 16 bytes of all sixteen rows are zeros;
+ * -1 is the documented "gap" value.  Bytes L .. row_stride-1 of each row are zero.
+ * Windows: window i covers samples onsets[i] .. onsets[i]+T-1.  With s = blk_set[onsets[i] >> 4] it
+ * is valid iff 0 <= onsets[i] <= L-T, s is in 0 .. n_sets-1, and blk_set[(onsets[i]+T-1) >> 4] == s
+ * (the two blk_set reads happen only after the onset has passed its range check).  A valid window's
+ * logit row is byte-identical to what net_model_compute_batch_ct returns for x[:, on : on+T] with
+ * set s loaded (the float entry quantises with set s's scale first).  From an invalid window no
+ * workspace or parameter address is formed, its row is N zeros and *n_bad (if non-NULL; the caller
+ * zeroes it) is incremented once.  There is no per-window set argument: the window's set is read
+ * from the list layer 1 ran by, so the two cannot disagree, and a window that starts in one
+ * network's recording and ends in another's is counted as invalid, not answered.  A window that
+ * crosses between two adjacent recordings of the same set is an ordinary window of the array, pad
+ * samples included.  ONLY THE FIRST AND LAST BLOCK OF A WINDOW ARE CHECKED: a block of another set
+ * (or a gap) strictly inside a window is the caller's error, and the result is then set s's layers
+ * 2-5 over ws as it is.
+ * onsets (W int64, 8-byte aligned), y ([W][N] int8, 4-byte aligned) and n_bad (one int32, 4-byte
+ * aligned, or NULL) are DEVICE pointers, as in net_model_compute_windows_at.
+ * Checks, all before any device call, in this order: a NULL bank, NET_ERR_INVALID (where
+ * NET_ERR_NO_PARAMS stands in the windows-at entries); every argument check of
+ * net_model_compute_windows_at[_f32] with the bank's C and T; blk_set NULL with W > 0, or misaligned
+ * for any W, NET_ERR_INVALID; the float entry on a bank created without scales, NET_ERR_INVALID.
+ * W == 0 returns NET_OK and touches nothing.  Two kernels are enqueued on `stream`.  The first call
+ * on a device uploads the bank (one allocation, one host sync); after it the entry makes no
+ * allocation and no host sync and is capturable into a HIP graph, like
+ * net_model_compute_epochs_bank.  Each workgroup takes a contiguous range of windows and reloads
+ * its parameters when the set changes, so list the windows recording by recording
+ * (net_bank_windows_lists does). */
+int net_model_compute_windows_bank(const net_bank_t* bank, const int8_t* x, int layout, size_t L,
+                                   const int32_t* blk_set, const int64_t* onsets, size_t W, int8_t* y,
+                                   int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream);
+int net_model_compute_windows_bank_f32(const net_bank_t* bank, const float* x, size_t L,
+                                       const int32_t* blk_set, const int64_t* onsets, size_t W, int8_t* y,
+                                       int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream);
+
+/* Host only: the layout above.  starts[0..R-1] (HOST, may be NULL); returns L, 0 on overflow of
+ * int64 or R == 0. */
+size_t net_bank_windows_starts(const size_t* lengths, size_t R, int64_t* starts);
+/* Host only: the lists of the sliding windows of those recordings; sets[r] = the set of recording r.
+ * Fills blk_set (HOST, if non-NULL and n_blk >= ceil(L/16)): every block from starts[r] >> 4 up to
+ * the block before starts[r+1] >> 4 (for the last recording, up to ceil(L/16)) gets sets[r]; onsets
+ * (HOST, if non-NULL and cap >= W) and first[0..R] (if non-NULL) as net_windows_multi_onsets does,
+ * with the aligned starts: recording r contributes starts[r] + k*hop, k < the windows of
+ * lengths[r] (none if it is shorter than T, though it still has its blocks).  Returns W.  0 and
+ * nothing written for a NULL bank, hop == 0, overflow, or a set outside the bank. */
+size_t net_bank_windows_lists(const net_bank_t* bank, const size_t* lengths, const int32_t* sets, size_t R,
+                              size_t hop, int32_t* blk_set, size_t n_blk, int64_t* onsets, size_t cap, size_t* first);
+
 /* Several devices from one host thread (static split, no collectives): shard i is
  * x[i] / y[i] / B[i] on devices[i] (DEVICE pointers of that device).  Every shard is enqueued
  * before any is waited for, so the devices run concurrently.  streams == NULL: each device's null

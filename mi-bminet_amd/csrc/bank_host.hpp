@@ -1,8 +1,12 @@
 // bank_host.hpp — the HIP-free part of a parameter bank (net_bank_create, include/mibminet.h): which
-// sets may share a bank, the exact-division form every slice of a mixed bank takes, and the
-// partition of an epoch list over the workgroups of bank::k_forward_ep_bank (forward_bank.hpp).
+// sets may share a bank, the exact-division form every slice of a mixed bank takes, the
+// partition of an item list over the workgroups of bank::bank_loop (forward_bank.hpp), and the
+// layout and lists of many recordings' windows (net_bank_windows_starts, net_bank_windows_lists).
 // HIP-free like params_host.hpp; the kernel includes it for range_of alone.
 #pragma once
+#include <cstddef>
+#include <cstdint>
+
 #include "params_host.hpp"
 
 #ifdef __HIPCC__
@@ -53,6 +57,65 @@ struct Range64 {
 };
 MIB_BANK_HD inline Range64 range_of(unsigned w, unsigned G, unsigned long long E) {
   return Range64{(long long)((unsigned long long)w * E / G), (long long)(((unsigned long long)w + 1) * E / G)};
+}
+
+// ---- windows through a bank (net_model_compute_windows_bank): the layout of R recordings -----
+// Recording r starts at starts[r], a multiple of 16 samples: starts[0] = 0, starts[r + 1] =
+// starts[r] + lengths[r] rounded up to 16, and L = starts[R - 1] + lengths[R - 1] (no rounding after
+// the last).  Fills starts[0 .. R - 1] if non-null and returns L; 0 (starts then unspecified) for
+// R == 0, null lengths, or an L or a start past INT64_MAX (the onsets are int64).
+inline size_t windows_starts(const size_t* lengths, size_t R, int64_t* starts) {
+  if (R == 0 || !lengths) return 0;
+  constexpr size_t LIM = (size_t)INT64_MAX;
+  size_t at = 0;  // <= LIM, a multiple of 16
+  for (size_t r = 0; r < R; r++) {
+    if (starts) starts[r] = (int64_t)at;
+    if (lengths[r] > LIM - at) return 0;
+    const size_t e = at + lengths[r];  // <= LIM
+    if (r + 1 == R) return e;
+    if (e > LIM - 15) return 0;
+    at = (e + 15) / 16 * 16;
+  }
+  return 0;
+}
+
+// The lists of the sliding windows (hop) of those recordings for a bank of n_sets sets of T samples:
+// blk_set (every block from starts[r] / 16 up to the block before starts[r + 1] / 16, for the last
+// recording up to ceil(L / 16), gets sets[r]; filled if non-null and n_blk >= ceil(L / 16)), onsets
+// (starts[r] + k hop, k < the windows of lengths[r]; filled if non-null and cap >= W) and
+// first[0 .. R] (if non-null).  Returns W; 0 and nothing written for hop == 0, null lengths or sets,
+// R == 0, overflow, or a set outside the bank.
+inline size_t windows_lists(size_t T, size_t n_sets, const size_t* lengths, const int32_t* sets, size_t R,
+                            size_t hop, int32_t* blk_set, size_t n_blk, int64_t* onsets, size_t cap, size_t* first) {
+  if (hop == 0 || !sets || T == 0) return 0;
+  const size_t L = windows_starts(lengths, R, nullptr);
+  if (L == 0) {
+    // L == 0 is also R recordings of no samples: then there is nothing to fill but first
+    bool empty = R > 0 && lengths;
+    for (size_t r = 0; empty && r < R; r++) empty = lengths[r] == 0;
+    if (!empty) return 0;
+  }
+  for (size_t r = 0; r < R; r++)
+    if (sets[r] < 0 || (size_t)sets[r] >= n_sets) return 0;
+  auto count = [&](size_t len) { return len < T ? (size_t)0 : (len - T) / hop + 1; };
+  size_t W = 0;  // <= L
+  for (size_t r = 0; r < R; r++) W += count(lengths[r]);
+  const size_t nb = L / 16 + (L % 16 != 0);
+  const bool fill_b = blk_set && n_blk >= nb, fill_o = onsets && cap >= W;
+  size_t at = 0, i = 0;
+  for (size_t r = 0; r < R; r++) {
+    const size_t e = at + lengths[r], next = r + 1 == R ? nb * 16 : (e + 15) / 16 * 16;
+    if (fill_b)
+      for (size_t b = at / 16; b < next / 16; b++) blk_set[b] = sets[r];
+    if (first) first[r] = i;
+    const size_t n = count(lengths[r]);
+    if (fill_o)
+      for (size_t k = 0; k < n; k++) onsets[i + k] = (int64_t)(at + k * hop);
+    i += n;
+    at = next;
+  }
+  if (first) first[R] = W;
+  return W;
 }
 
 }  // namespace bank

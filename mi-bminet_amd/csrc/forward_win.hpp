@@ -13,6 +13,8 @@
 //   k_forward_y1_at  the same body with each window's first sample read from a device list and
 //                  range-checked (net_model_compute_windows_at): irregular and overlapping
 //                  windows, and the windows of many recordings laid end to end.
+// The same windows with the network chosen per recording (net_model_compute_windows_bank) are
+// forward_bank.hpp's kernels, on Rows in its bank form below.
 // All read a gen::GenParams image (every geometry, the compiled ones included) and are built
 // from the run-time-dimension family (forward_gen.hpp); the compiled wg:: kernels are untouched.
 #pragma once
@@ -102,8 +104,15 @@ __device__ __forceinline__ void copy_rows(const gen::View& v, int8_t* y1, int y1
 // the last wave only finishes the previous window.  HT: T is held across the loop; else it is one
 // scalar load per window.  The plain-BN float builds read it (held, they spilled 13 more scalar
 // registers and ran 1-2 % slower), the others hold it (reading cost them 0.7 %).
-template <bool AT, bool HT>
+// BK (with AT): the windows of many recordings, each under its own set of a bank
+// (net_model_compute_windows_bank).  blk_set[b] is the set of samples 16 b .. 16 b + 15, the list
+// layer 1 ran by (bank::k_layer1_rec_bank).  A window is valid when its onset is in range, the set
+// s of its first block lies in 0 .. n_sets - 1 and its last block has the same entry; the two
+// entries are read only after the range check (both blocks then lie inside the list), and s
+// travels in the item.  gp is then the current set's, changed by the bank loop.
+template <bool AT, bool HT, bool BK = false>
 struct Rows {
+  static_assert(AT || !BK, "a bank's windows come from an onset list");
   static constexpr bool ONSETS = AT;
   const int8_t* ws;
   const long long* onsets;
@@ -111,14 +120,26 @@ struct Rows {
   const gen::GenParams* gp;
   int hop, rs, T, NB1, y1s, tid;
   int8_t* y1;
+  const int* blk_set = nullptr;  // BK
+  int n_sets = 0;
   struct Item {
     long long on;  // the window's first sample
     bool valid;
+    int s;         // BK: the window's set, meaningful if valid
   };
   __device__ __forceinline__ Item open(int w, bool more) const {
-    if constexpr (!AT) return Item{(long long)w * hop, true};
+    if constexpr (!AT) return Item{(long long)w * hop, true, 0};
     const long long on = more ? onsets[w] : 0;  // (wave-uniform: one scalar load)
-    return Item{on, (unsigned long long)on <= (unsigned long long)last};  // last >= 0: negative onsets fail too
+    const bool in = (unsigned long long)on <= (unsigned long long)last;  // last >= 0: negative onsets fail too
+    if constexpr (!BK) return Item{on, in, 0};
+    int s = 0;
+    bool valid = false;
+    if (more && in) {  // (wave-uniform: two scalar loads)
+      s = blk_set[on >> 4];
+      const int e = blk_set[(on + (HT ? T : gp->T) - 1) >> 4];
+      valid = (unsigned)s < (unsigned)n_sets && e == s;
+    }
+    return Item{on, valid, s};
   }
   __device__ __forceinline__ void rows(const Item& it) const {
     const int t = HT ? T : gp->T;

@@ -286,35 +286,54 @@ int launch_windows(DeviceState& ds, const gen::GenParams& hg, const void* p, int
   });
 }
 
-// Both windows entries.  arg_layout: the int8 entry's layout argument (0 time-major, 1
-// channel-major); f32: the float32 entry (channel-major, scale qs).  at selects the entry: false,
-// the windows at every hop-th sample (onsets, W_at and n_bad unused); true, the W_at windows at the
-// device list onsets (win::k_forward_y1_at; hop unused), invalid ones counted in *n_bad.  The list
-// may be null only with W_at == 0, which returns before any launch, so launch_windows, reached
-// with W > 0 only, tells the two by the list.  Every argument and parameter check comes before the
-// first device call.
-int windows_async(const void* x, int arg_layout, bool f32, size_t L, bool at, size_t hop, const int64_t* onsets,
-                  size_t W_at, float qs, int8_t* y, int32_t* n_bad, void* ws, size_t ws_bytes, int device,
-                  void* stream) {
-  const Snapshot s = snapshot();
-  if (!s.host) return NET_ERR_NO_PARAMS;
-  const Dims& d = s.host->d;
+// The argument checks the windows entries share (the loaded set's and a bank's), in their
+// documented order, for a network of C channels and T samples.  arg_layout: the int8 entries' layout
+// argument (0 time-major, 1 channel-major); f32: a float32 entry (channel-major).  at: false, the
+// windows at every hop-th sample (onsets, W_at and n_bad unused); true, the W_at windows at the
+// device list onsets (hop unused).  On NET_OK what the launch takes: the gen::Layout and W.
+struct WindowsGeom {
+  int layout;
+  size_t W;
+};
+int check_windows(int C, int T, const void* x, int arg_layout, bool f32, size_t L, bool at, size_t hop,
+                  const int64_t* onsets, size_t W_at, const int8_t* y, const int32_t* n_bad, const void* ws,
+                  size_t ws_bytes, int device, WindowsGeom& g) {
   if ((!at && hop == 0) || (!f32 && arg_layout != 0 && arg_layout != 1)) return NET_ERR_INVALID;
   const int layout = f32 ? (int)gen::F32 : arg_layout;  // gen::Layout
-  const size_t W = at ? W_at : windows_count(d, L, hop);
+  const size_t W = at ? W_at : (hop == 0 || L < (size_t)T ? 0 : (L - (size_t)T) / hop + 1);
   if (W && (!x || !y || !ws || (at && !onsets))) return NET_ERR_INVALID;
   if (((uintptr_t)y & 3) != 0 || (layout == 2 && ((uintptr_t)x & 3) != 0)) return NET_ERR_INVALID;
   if (at && (((uintptr_t)n_bad & 3) != 0 || ((uintptr_t)onsets & 7) != 0)) return NET_ERR_INVALID;
   if (L > SIZE_MAX / 32) return NET_ERR_INVALID;  // (far past the offset limit below; 16 rs cannot wrap)
   const size_t rs = windows_row_stride(L);
   if (((uintptr_t)ws & 15) != 0 || ws_bytes < 16 * rs) return NET_ERR_INVALID;
-  if (at && W && L < (size_t)d.T) return NET_ERR_INVALID;  // no onset can be valid
+  if (at && W && L < (size_t)T) return NET_ERR_INVALID;  // no onset can be valid
   if (device < 0 || device >= MAX_DEVICES) return NET_ERR_INVALID;
   // window indices are int in the kernel: w + gridDim.x (grid <= 2 per CU) must not wrap
   if (W > (size_t)INT32_MAX - 65535) return NET_ERR_INVALID;
   // the recording and the workspace are each one buffer view with 32-bit offsets
-  const size_t per = std::max((size_t)16, (size_t)d.C * (layout == 2 ? sizeof(float) : 1));
+  const size_t per = std::max((size_t)16, (size_t)C * (layout == 2 ? sizeof(float) : 1));
   if (L > (((size_t)1 << 31) - 1) / per) return NET_ERR_INVALID;
+  g.layout = layout;
+  g.W = W;
+  return NET_OK;
+}
+
+// Both windows entries of the loaded set.  at selects the entry (check_windows); the float scale qs.
+// The list may be null only with W_at == 0, which returns before any launch, so launch_windows,
+// reached with W > 0 only, tells the two by the list.  Every argument and parameter check comes
+// before the first device call.
+int windows_async(const void* x, int arg_layout, bool f32, size_t L, bool at, size_t hop, const int64_t* onsets,
+                  size_t W_at, float qs, int8_t* y, int32_t* n_bad, void* ws, size_t ws_bytes, int device,
+                  void* stream) {
+  const Snapshot s = snapshot();
+  if (!s.host) return NET_ERR_NO_PARAMS;
+  const Dims& d = s.host->d;
+  WindowsGeom g;
+  if (const int rc = check_windows(d.C, d.T, x, arg_layout, f32, L, at, hop, onsets, W_at, y, n_bad, ws, ws_bytes, device, g))
+    return rc;
+  const int layout = g.layout;
+  const size_t W = g.W;
   if (layout == 2)
     if (const int rc = check_scale(qs)) return rc;
   const Image& win = s.img[IMG_WINDOWS];
@@ -515,6 +534,41 @@ int bank_epochs_async(const net_bank* b, const void* x, bool f32, size_t n_elems
     };
     constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
     return f32 ? go(bank::k_forward_ep_bank<gen::F32, RB, XR, CB>) : go(bank::k_forward_ep_bank<gen::CT, RB, XR, CB>);
+  });
+}
+
+// The windows of many recordings, each under its own set (forward_bank.hpp): check_windows with the
+// bank's C and T, then the block list's and, for float input, the bank's scales.
+int bank_windows_async(const net_bank* b, const void* x, int arg_layout, bool f32, size_t L, const int32_t* blk_set,
+                       const int64_t* onsets, size_t W, int8_t* y, int32_t* n_bad, void* ws, size_t ws_bytes,
+                       int device, void* stream) {
+  if (!b) return NET_ERR_INVALID;
+  const gen::GenParams& hg = b->sets[0];
+  WindowsGeom g;
+  if (const int rc = check_windows(hg.C, hg.T, x, arg_layout, f32, L, true, 0, onsets, W, y, n_bad, ws, ws_bytes, device, g))
+    return rc;
+  if ((W && !blk_set) || ((uintptr_t)blk_set & 3) != 0) return NET_ERR_INVALID;
+  if (f32 && b->scales.empty()) return NET_ERR_INVALID;
+  if (W == 0) return NET_OK;
+  DeviceScope sc(device, *b);
+  if (sc.rc) return sc.rc;
+  const auto* sets = (const gen::GenParams*)sc.image;
+  const auto* scales = f32 ? (const bank::Scale*)(sets + b->sets.size()) : nullptr;
+  const int n_sets = (int)b->sets.size(), rs = (int)windows_row_stride(L), lds = carve_of(hg, 3).bytes;
+  const size_t nb = (L + 15) / 16, wgs = (nb + win::NW1 - 1) / win::NW1;
+  const hipStream_t st = (hipStream_t)stream;
+  return with_layout(g.layout, [&](auto lc) {
+    return with_flags(hg, [&](auto rb, auto xr, auto cb) {
+      constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
+      // 8 workgroups of 4 waves fill a CU (launch_windows)
+      hipLaunchKernelGGL((bank::k_layer1_rec_bank<decltype(lc)::value, XR, CB>),
+                         dim3((unsigned)capped_grid(sc.ds, wgs, 8)), dim3(win::NT1), 0, st, sets, n_sets,
+                         (const int*)blk_set, scales, (const int8_t*)x, (int8_t*)ws, (int)L, rs);
+      if (const int rc = hip_err(hipGetLastError())) return rc;
+      return launch_items(sc.ds, bank::k_forward_y1_bank<RB, XR, CB>, lds, W, st, sets, n_sets, (const int*)blk_set,
+                          (const int8_t*)ws, (const long long*)onsets, y, (int*)n_bad, (int)W,
+                          (long long)(L - (size_t)hg.T), rs);
+    });
   });
 }
 
@@ -925,6 +979,29 @@ int net_model_compute_epochs_bank_f32(const net_bank_t* bank, const float* x, si
                                       const int32_t* channels, const int64_t* onsets, const int32_t* set_of, size_t E,
                                       int8_t* y, int32_t* n_bad, int device, void* stream) {
   return bank_epochs_async(bank, x, true, n_elems, row_stride, channels, onsets, set_of, E, y, n_bad, device, stream);
+}
+
+int net_model_compute_windows_bank(const net_bank_t* bank, const int8_t* x, int layout, size_t L,
+                                   const int32_t* blk_set, const int64_t* onsets, size_t W, int8_t* y,
+                                   int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream) {
+  return bank_windows_async(bank, x, layout, false, L, blk_set, onsets, W, y, n_bad, ws, ws_bytes, device, stream);
+}
+
+int net_model_compute_windows_bank_f32(const net_bank_t* bank, const float* x, size_t L, const int32_t* blk_set,
+                                       const int64_t* onsets, size_t W, int8_t* y, int32_t* n_bad, void* ws,
+                                       size_t ws_bytes, int device, void* stream) {
+  return bank_windows_async(bank, x, 1, true, L, blk_set, onsets, W, y, n_bad, ws, ws_bytes, device, stream);
+}
+
+size_t net_bank_windows_starts(const size_t* lengths, size_t R, int64_t* starts) {
+  return bank::windows_starts(lengths, R, starts);
+}
+
+size_t net_bank_windows_lists(const net_bank_t* bank, const size_t* lengths, const int32_t* sets, size_t R,
+                              size_t hop, int32_t* blk_set, size_t n_blk, int64_t* onsets, size_t cap, size_t* first) {
+  if (!bank) return 0;
+  return bank::windows_lists((size_t)bank->sets[0].T, bank->sets.size(), lengths, sets, R, hop, blk_set, n_blk, onsets,
+                             cap, first);
 }
 
 int net_quantize_input_f32(const float* x, int8_t* y, size_t B, int C, int T, float scale, int device, void* stream) {

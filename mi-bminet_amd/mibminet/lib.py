@@ -70,6 +70,10 @@ PROTOTYPES = {
     "net_bank_destroy": "void (ptr)",
     "net_model_compute_epochs_bank": "int (ptr, ptr, size_t, size_t, ptr, ptr, ptr, size_t, ptr, ptr, int, ptr)",
     "net_model_compute_epochs_bank_f32": "int (ptr, ptr, size_t, size_t, ptr, ptr, ptr, size_t, ptr, ptr, int, ptr)",
+    "net_model_compute_windows_bank": "int (ptr, ptr, int, size_t, ptr, ptr, size_t, ptr, ptr, ptr, size_t, int, ptr)",
+    "net_model_compute_windows_bank_f32": "int (ptr, ptr, size_t, ptr, ptr, size_t, ptr, ptr, ptr, size_t, int, ptr)",
+    "net_bank_windows_starts": "size_t (ptr, size_t, ptr)",
+    "net_bank_windows_lists": "size_t (ptr, ptr, ptr, size_t, size_t, ptr, size_t, ptr, size_t, ptr)",
     "net_model_compute_batch_multi": "int (int, ptr, ptr, ptr, ptr, ptr)",
     "net_model_compute_batch_multi_ct": "int (int, ptr, ptr, ptr, ptr, ptr)",
     "net_quantize_input_f32": "int (ptr, ptr, size_t, int, int, float, int, ptr)",
@@ -609,7 +613,8 @@ def forward_windows_f32_torch(x, hop: int, scale: float, stream=None):
     return y
 
 
-def _forward_onsets(name: str, x, head, onsets, scale, mid, stream, check: bool, noun: str, bank=None, set_of=None):
+def _forward_onsets(name: str, x, head, onsets, scale, mid, stream, check: bool, noun: str, bank=None, set_of=None,
+                    per_item_sets: bool = True):
     """The call of an entry that takes an onset list, ``name`` or, with a ``scale``, ``name``_f32:
     entry(x, *head, onsets, n, [scale,] y, n_bad, *mid, device, stream).  ``onsets`` is a 1-D int64
     tensor or a sequence of ints; its device copy and, with ``check``, the zeroed counter are made
@@ -621,7 +626,8 @@ def _forward_onsets(name: str, x, head, onsets, scale, mid, stream, check: bool,
     no scale: entry(bank, x, *head, onsets, set_of, n, y, n_bad, *mid, device, stream).  ``set_of``
     is a 1-D int32 tensor or a sequence of as many ints as there are onsets, copied like them, or
     None (NULL: set 0 for every item, a bank of one set only); the count then covers set indices
-    outside the bank too."""
+    outside the bank too.  ``per_item_sets=False``: a bank entry that takes no ``set_of`` at all
+    (the windows of a bank, whose block list travels in ``head``)."""
     torch = _torch()
     if not isinstance(onsets, torch.Tensor):
         onsets = torch.as_tensor([int(o) for o in onsets], dtype=torch.int64).reshape(-1)
@@ -635,7 +641,7 @@ def _forward_onsets(name: str, x, head, onsets, scale, mid, stream, check: bool,
             raise ValueError("set_of must be a 1-D int32 tensor or a sequence of ints")
         if int(set_of.numel()) != n:
             raise ValueError(f"{int(set_of.numel())} set indices for {n} onsets")
-    elif bank is not None and bank.n_sets != 1:
+    elif bank is not None and per_item_sets and bank.n_sets != 1:
         raise ValueError(f"set_of may be None only for a bank of one set, this one has {bank.n_sets}")
     s, dev = _launch(x, stream)
     with torch.cuda.stream(s):  # the lists' copies and the counter's zeroing precede the launch on its stream
@@ -647,14 +653,15 @@ def _forward_onsets(name: str, x, head, onsets, scale, mid, stream, check: bool,
         name += "_f32"
     _check(getattr(load(), name)(*(() if bank is None else (bank.handle,)), x.data_ptr(), *head,
                                  on.data_ptr() if n else None,
-                                 *(() if bank is None else (so.data_ptr() if n and so is not None else None,)), n,
+                                 *((so.data_ptr() if n and so is not None else None,) if bank is not None and per_item_sets
+                                   else ()), n,
                                  *(() if scale is None else (scale,)), y.data_ptr() if n else None,
                                  nbad.data_ptr() if check else None, *mid, dev, s.cuda_stream), name)
     if check and n:
         s.synchronize()
         bad = int(nbad.item())
         if bad:
-            what = "onsets" if bank is None else "onsets or set indices"
+            what = "onsets or set indices" if bank is not None and per_item_sets else "onsets"
             raise ValueError(f"{bad} of {n} {what} lie outside the {noun} (their logit rows are zero)")
     return y
 
@@ -870,6 +877,122 @@ def forward_bank_torch(bank, x, set_of, stream=None, check: bool = True):
     with torch.cuda.stream(s):
         onsets = torch.arange(x.shape[0], dtype=torch.int64, device=x.device) * (d.C * d.T)
     return forward_epochs_bank_torch(bank, x, onsets, set_of, row_stride=d.T, stream=s, check=check)
+
+
+def bank_windows_lists(bank, lengths, sets, hop: int):
+    """net_bank_windows_starts / net_bank_windows_lists: the layout and lists of the sliding windows
+    (hop ``hop``) of recordings of ``lengths`` samples, recording r under set ``sets[r]`` of ``bank``,
+    each starting at a multiple of 16 samples.  Returns (starts, L, blk_set, onsets, first): NumPy
+    arrays int64[R], int32[ceil(L / 16)], int64[W] and int64[R + 1], and L as an int."""
+    if not isinstance(bank, Bank):
+        raise ValueError(f"bank must be a Bank, got {type(bank).__name__}")
+    lens, ss = [int(v) for v in lengths], [int(v) for v in sets]
+    R = len(lens)
+    if len(ss) != R:
+        raise ValueError(f"{len(ss)} sets for {R} recordings")
+    if R == 0 or hop < 1 or min(lens) < 0 or min(ss) < 0 or max(ss) >= bank.n_sets:
+        raise ValueError(f"at least one recording, hop at least 1, non-negative lengths and sets in 0 .. {bank.n_sets - 1}")
+    if sum(lens) + 16 * R >= 2**63:
+        raise ValueError("the recordings must end below 2^63 samples")
+    arr = (ctypes.c_size_t * R)(*lens)
+    sarr = (ctypes.c_int32 * R)(*ss)
+    starts = np.zeros(R, np.int64)
+    L = int(load().net_bank_windows_starts(arr, R, starts.ctypes.data))
+    nb = (L + 15) // 16
+    first = (ctypes.c_size_t * (R + 1))()
+    W = int(load().net_bank_windows_lists(bank.handle, arr, sarr, R, hop, None, 0, None, 0, None))
+    blk_set, onsets = np.empty(nb, np.int32), np.empty(W, np.int64)
+    load().net_bank_windows_lists(bank.handle, arr, sarr, R, hop, blk_set.ctypes.data if nb else None, nb,
+                                  onsets.ctypes.data if W else None, W, first)
+    return starts, L, blk_set, onsets, np.array(list(first), np.int64)
+
+
+def forward_windows_bank_torch(bank, x, blk_set, onsets, layout: str = "ct", stream=None, check: bool = True,
+                               return_y1: bool = False):
+    """net_model_compute_windows_bank / _f32: the windows x[:, onsets[i] : onsets[i] + T] of many
+    recordings laid along time in ``x`` at multiples of 16 samples, each classified by the set of
+    its recording.  ``x`` is int8 ("ct" = [C][L] or "tc" = [L][C]) or float32 ([C][L]; needs a bank
+    with scales), C and T the bank's; ``blk_set`` a device int32 tensor of ceil(L / 16) entries, the
+    set of each 16-sample block (-1: a gap); ``onsets`` an int64 tensor or a sequence
+    (bank_windows_lists builds both).  Returns the logits [W][N] int8, row i what forward_ct_torch
+    returns for that window with its set loaded; with ``return_y1`` also the workspace
+    [16][row_stride].  A window is invalid when its onset lies outside 0 .. L - T, its first block's
+    set lies outside the bank or its last block has another entry; such rows are zero, and with
+    ``check`` their count is read back (a host sync) and a ValueError names it."""
+    if not isinstance(bank, Bank):
+        raise ValueError(f"bank must be a Bank, got {type(bank).__name__}")
+    code = _layout_code(layout)
+    d = bank.dims
+    dt = _check_tensor(x, "the recordings' array", ("int8", "float32"), (d.C, "L") if layout == "ct" else ("L", d.C))
+    f32 = dt == "float32"
+    if f32 and layout != "ct":
+        raise ValueError('a float32 array is "ct" ([C][L])')
+    if f32 and not bank.has_scales:
+        raise ValueError("a float32 source needs a bank created with scales")
+    L = int(x.shape[1 if layout == "ct" else 0])
+    _check_tensor(blk_set, "blk_set", ("int32",), ((L + 15) // 16,))
+    if blk_set.device != x.device:
+        raise ValueError("blk_set must be on the array's device")
+    ws = _workspace(x, L)
+    y = _forward_onsets("net_model_compute_windows_bank", x, (L, blk_set.data_ptr()) if f32 else (code, L, blk_set.data_ptr()),
+                        onsets, None, (ws.data_ptr(), ws.numel()), stream, check, "recording or the bank", bank=bank,
+                        per_item_sets=False)
+    return (y, ws) if return_y1 else y
+
+
+def forward_windows_multi_bank_torch(bank, recordings, sets, hop: int, layout: str = "ct", stream=None,
+                                     max_bytes: Optional[int] = None):
+    """The sliding windows (hop ``hop``) of many recordings, recording r classified by set
+    ``sets[r]`` of ``bank``, in one call per chunk.  ``recordings`` is a list of CUDA/HIP tensors
+    ([C][L_r] each, or [L_r][C] for "tc"; int8, or float32 for a bank with scales).  Returns
+    (logits [W][N] int8, first): rows first[r] .. first[r + 1] - 1 are what forward_windows_torch
+    returns for recording r with set ``sets[r]`` loaded.  The tensors are laid at starts that are
+    multiples of 16 samples, zero pads between them, and whole recordings are grouped into chunks
+    whose samples times max(16, C * element size) stay below ``max_bytes`` (default: the entries'
+    2^31 limit), each chunk one forward_windows_bank_torch call; no host sync."""
+    torch = _torch()
+    if not isinstance(bank, Bank):
+        raise ValueError(f"bank must be a Bank, got {type(bank).__name__}")
+    _layout_code(layout)
+    axis = 1 if layout == "ct" else 0  # the time axis
+    if hop < 1:
+        raise ValueError("hop must be at least 1")
+    d = bank.dims
+    tensors, sets = list(recordings), [int(v) for v in sets]
+    if not tensors:
+        raise ValueError("recordings must hold at least one tensor")
+    if len(sets) != len(tensors):
+        raise ValueError(f"{len(sets)} sets for {len(tensors)} recordings")
+    for t in tensors:
+        dt = _check_tensor(t, "the recording", ("int8", "float32"), (d.C, "L") if layout == "ct" else ("L", d.C))
+        if t.device != tensors[0].device or t.dtype != tensors[0].dtype:
+            raise ValueError("the recordings must be on one device and of one element type")
+    f32 = dt == "float32"
+    if f32 and not bank.has_scales:
+        raise ValueError("a float32 source needs a bank created with scales")
+    lengths = [int(t.shape[axis]) for t in tensors]
+    per = max(16, d.C * (4 if f32 else 1))
+    # a chunk's pads add at most 15 samples per recording
+    chunks = _plan_chunks([n + 15 for n in lengths], per, 2**31 if max_bytes is None else int(max_bytes))
+    s, _ = _launch(tensors[0], stream)
+    out, first = [], [0]
+    with torch.cuda.stream(s):  # the chunks' copies precede their launches on the stream
+        for a, b in chunks:
+            starts, L, blk_set, onsets, f = bank_windows_lists(bank, lengths[a:b], sets[a:b], hop)
+            first += [first[a] + int(v) for v in f[1:]]
+            parts = []
+            for r in range(a, b):
+                parts.append(tensors[r])
+                pad = (int(starts[r - a + 1]) if r + 1 < b else L) - int(starts[r - a]) - lengths[r]
+                if pad:
+                    shape = (d.C, pad) if axis == 1 else (pad, d.C)
+                    parts.append(torch.zeros(shape, dtype=tensors[r].dtype, device=tensors[r].device))
+            xc = parts[0] if len(parts) == 1 else torch.cat(parts, dim=axis)
+            # every generated window is valid: no counter, no host sync
+            out.append(forward_windows_bank_torch(bank, xc, torch.from_numpy(blk_set).to(xc.device),
+                                                  torch.from_numpy(onsets), layout=layout, stream=s, check=False))
+        y = out[0] if len(out) == 1 else torch.cat(out, dim=0)
+    return y, first
 
 
 def quantize_input_torch(x, scale: float, stream=None):

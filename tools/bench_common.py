@@ -1,4 +1,4 @@
-"""What bench_windows.py, bench_windows_at.py, bench_epochs.py and bench_bank.py share: the alternating HIP-event
+"""What bench_windows.py, bench_windows_at.py, bench_epochs.py, bench_bank.py and bench_windows_bank.py share: the alternating HIP-event
 timing loop and its summaries, the command line, and the loop that runs the cases, writes one JSON
 line per case and turns mismatches into the exit status.  No tool of its own."""
 import argparse
