@@ -2,11 +2,13 @@
 // sets may share a bank, the exact-division form every slice of a mixed bank takes, the
 // partition of an item list over the workgroups of bank::bank_loop (forward_bank.hpp), and the
 // layout and lists of many recordings' windows (net_bank_windows_starts, net_bank_windows_lists).
-// HIP-free like params_host.hpp; the kernel includes it for range_of alone.
+// HIP-free like params_host.hpp and entry_host.hpp (whose windows_count the lists use); the kernel
+// includes it for range_of alone.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 
+#include "entry_host.hpp"
 #include "params_host.hpp"
 
 #ifdef __HIPCC__
@@ -97,9 +99,8 @@ inline size_t windows_lists(size_t T, size_t n_sets, const size_t* lengths, cons
   }
   for (size_t r = 0; r < R; r++)
     if (sets[r] < 0 || (size_t)sets[r] >= n_sets) return 0;
-  auto count = [&](size_t len) { return len < T ? (size_t)0 : (len - T) / hop + 1; };
   size_t W = 0;  // <= L
-  for (size_t r = 0; r < R; r++) W += count(lengths[r]);
+  for (size_t r = 0; r < R; r++) W += windows_count(T, lengths[r], hop);
   const size_t nb = L / 16 + (L % 16 != 0);
   const bool fill_b = blk_set && n_blk >= nb, fill_o = onsets && cap >= W;
   size_t at = 0, i = 0;
@@ -108,7 +109,7 @@ inline size_t windows_lists(size_t T, size_t n_sets, const size_t* lengths, cons
     if (fill_b)
       for (size_t b = at / 16; b < next / 16; b++) blk_set[b] = sets[r];
     if (first) first[r] = i;
-    const size_t n = count(lengths[r]);
+    const size_t n = windows_count(T, lengths[r], hop);
     if (fill_o)
       for (size_t k = 0; k < n; k++) onsets[i + k] = (int64_t)(at + k * hop);
     i += n;

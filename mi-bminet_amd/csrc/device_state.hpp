@@ -1,6 +1,7 @@
 // device_state.hpp — the loaded set and the per-device state of libmibminet.so: the parameter-image
 // cache, the single-trial scratch and the scoped entry every launching call goes through.  Holds
-// the library's globals: included by mibminet.hip only.
+// the library's globals: included by mibminet.hip only.  (MAX_DEVICES, which the entries' argument
+// checks need too, is entry_host.hpp's.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,7 @@
 #include <utility>
 #include <vector>
 
+#include "entry_host.hpp"  // MAX_DEVICES
 #include "forward_bank.hpp"
 #include "images.hpp"
 
@@ -26,8 +28,6 @@ struct net_bank {
 
 namespace mib {
 namespace {
-
-constexpr int MAX_DEVICES = 64;
 
 // One device copy of the parameter image per loaded generation: a load never overwrites a copy
 // that a kernel may still read, so launches in flight and launches captured into a HIP graph keep

@@ -15,15 +15,11 @@
 // window kernels run too), on a gen::GenParams image (every geometry, the compiled ones included:
 // the image the window kernels use).
 #pragma once
+#include "entry_host.hpp"  // ep::ChanTab
 #include "forward_gen.hpp"
 
 namespace mib {
 namespace ep {
-
-// The loaded network's channel -> source row table, a by-value kernel argument.
-struct ChanTab {
-  int c[64];
-};
 
 // The view of the epoch at element onset `on` (valid: 0 <= on <= n_elems - span).  The span lies
 // inside the source, so no load through the view leaves it by more than the dword rounding.

@@ -37,6 +37,7 @@
 // division (xdiv, forward_common.hpp) at layers 1-4.  Layer 5 always divides exactly (its
 // sums pass 2^24 at T = 4096).  CB: balanced clipping ([-127, 127], golden model clip_balanced).
 #pragma once
+#include "entry_host.hpp"  // gen::Layout
 #include "forward_wg.hpp"
 
 namespace mib {
@@ -48,8 +49,6 @@ constexpr int TMAX = 4096;             // samples per trial (16 s at 250 Hz)
 constexpr int NMAX = 16;               // classes
 constexpr int T64A_MAX = TMAX / 64;
 constexpr int L5W = F2 * T64A_MAX;     // bytes of one class's layer-5 weight row
-
-enum Layout { TM = 0, CT = 1, F32 = 2 };
 
 // Per-filter constants read by layers 3 and 4 of every wave: copied into LDS once per workgroup.
 struct SmallG {

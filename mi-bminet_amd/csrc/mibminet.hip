@@ -4,6 +4,9 @@
 // * params_host.hpp: the blob parser (mibminet/params.py, ParamSet.to_blob, holding the reference's
 //   net.h arrays, edge-eegnet_wolf/data/gen_net_header.py:91-224), range checks, folding and the
 //   requant plan;
+// * entry_host.hpp: the entries' argument arithmetic (scale, strides, counts, the windows and epochs
+//   checks with the launch geometry they validate);
+// * bank_host.hpp: the HIP-free part of a parameter bank;
 // * images.hpp: the gfx950 operand fragments and both parameter images;
 // * device_state.hpp: the loaded set, the per-device image cache and the scoped launch entry;
 // * test_hooks.hpp: include/mibminet_testing.h.
@@ -23,6 +26,7 @@
 
 #include "../../include/mibminet.h"
 #include "../../include/mibminet_testing.h"
+#include "entry_host.hpp"
 #include "forward_wg.hpp"
 #include "forward_gen.hpp"
 #include "forward_win.hpp"
@@ -121,6 +125,10 @@ int with_layout(int layout, F&& f) {
 gen::Carve carve_of(const gen::GenParams& g, int layout) {
   return gen::carve_of(g.C, g.T, g.N, g.T8, g.T64A, g.NB1, g.MT, g.NTT, layout);
 }
+// the LDS bytes of the windows' layers 2-5 (the loaded set's and a bank's), and of the epoch kernels
+// (the float32 carve for both layouts)
+int windows_lds(const gen::GenParams& g) { return carve_of(g, 3).bytes; }
+int epochs_lds(const gen::GenParams& g) { return carve_of(g, gen::F32).bytes; }
 
 // test hook (mibminet_test_grid_cap): at most this many workgroups per persistent grid (0: no cap)
 std::atomic<int> g_grid_cap{0};
@@ -131,19 +139,6 @@ int capped_grid(const DeviceState& ds, size_t items, int blocks_per_cu) {
   const int cap = g_grid_cap.load();
   return (int)(cap > 0 ? std::min(grid, (size_t)cap) : grid);
 }
-
-// RN(1 / scale) of the float32 entries: IEEE division on the host (0: an int8 entry)
-float recip_scale(float qs) { return qs > 0.0f ? 1.0f / qs : 0.0f; }
-
-// The scale of a float32 entry.  The in-kernel quotient correction stays exact while its products
-// are normal floats: scales in [2^-60, 2^60] (checked on every float32 input,
-// tests/test_gpu_f32.py); others: the two-pass quantiser (net_quantize_input_f32), which divides.
-int check_scale(float qs) {
-  if (!(qs > 0.0f && qs <= 3.4e38f)) return NET_ERR_INVALID;
-  return qs >= 0x1p-60f && qs <= 0x1p60f ? NET_OK : NET_ERR_RANGE;
-}
-
-size_t trial_stride(const Dims& d) { return ((size_t)d.C * d.T + 15) / 16 * 16; }
 
 // Persistent grid: as many resident workgroups as the occupancy allows (two per CU).
 template <class K>
@@ -252,77 +247,37 @@ int launch_layer(const Variant& v, const void* himg, const void* p, const int8_t
 }
 
 // ---- sliding windows over a recording (forward_win.hpp) --------------------------------------
-size_t windows_row_stride(size_t L) { return L > SIZE_MAX - 15 ? 0 : (L + 15) / 16 * 16; }
-
-size_t windows_count(const Dims& d, size_t L, size_t hop) {
-  return hop == 0 || L < (size_t)d.T ? 0 : (L - (size_t)d.T) / hop + 1;
-}
-
-// Layer 1 over the recording (layout as gen::Layout) into ws, then the W windows' layers 2-5:
-// window w at sample w hop, or, with onsets (a device list, net_model_compute_windows_at), at
-// onsets[w], invalid ones counted in *n_bad.  hg: the host copy of the gen::GenParams p points to.
-int launch_windows(DeviceState& ds, const gen::GenParams& hg, const void* p, int layout, const int8_t* x, size_t Lr,
-                   size_t hop, size_t W, int8_t* y, int8_t* ws, hipStream_t st, float qs,
+// Layer 1 over the recording (g.layout) into ws, then the g.W windows' layers 2-5: window w at
+// sample w hop, or, with onsets (a device list, net_model_compute_windows_at), at onsets[w], invalid
+// ones counted in *n_bad.  g: check_windows' geometry of the Lr samples; hg: the host copy of the
+// gen::GenParams p points to.
+int launch_windows(DeviceState& ds, const gen::GenParams& hg, const void* p, const WindowsGeom& g, const int8_t* x,
+                   size_t Lr, size_t hop, int8_t* y, int8_t* ws, hipStream_t st, float qs,
                    const int64_t* onsets = nullptr, int32_t* n_bad = nullptr) {
-  const int rs = (int)windows_row_stride(Lr), lds = carve_of(hg, 3).bytes;
-  const size_t nb = (Lr + 15) / 16, wgs = (nb + win::NW1 - 1) / win::NW1;
+  const int lds = windows_lds(hg);
   const gen::GenParams* gp = (const gen::GenParams*)p;
-  return with_layout(layout, [&](auto lc) {
+  return with_layout(g.layout, [&](auto lc) {
     return with_flags(hg, [&](auto rb, auto xr, auto cb) {
       constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
       // 8 workgroups of 4 waves fill a CU
-      hipLaunchKernelGGL((win::k_layer1_rec<decltype(lc)::value, XR, CB>), dim3((unsigned)capped_grid(ds, wgs, 8)),
-                         dim3(win::NT1), 0, st, gp, x, ws, (int)Lr, rs, qs, recip_scale(qs));
+      hipLaunchKernelGGL((win::k_layer1_rec<decltype(lc)::value, XR, CB>), dim3((unsigned)capped_grid(ds, g.wgs, 8)),
+                         dim3(win::NT1), 0, st, gp, x, ws, (int)Lr, g.rs, qs, recip_scale(qs));
       if (const int rc = hip_err(hipGetLastError())) return rc;
       // hop > INT32_MAX: a single window (hop <= L - T < 2^27 otherwise), at sample 0 whatever hop is
-      const int rc = onsets ? launch_items(ds, win::k_forward_y1_at<RB, XR, CB>, lds, W, st, gp, (const int8_t*)ws,
-                                           (const long long*)onsets, y, (int*)n_bad, (int)W,
-                                           (long long)(Lr - (size_t)hg.T), rs)
-                            : launch_items(ds, win::k_forward_y1<RB, XR, CB>, lds, W, st, gp, (const int8_t*)ws, y, (int)W,
-                                           (int)std::min(hop, (size_t)INT32_MAX), rs);
+      const int rc = onsets ? launch_items(ds, win::k_forward_y1_at<RB, XR, CB>, lds, g.W, st, gp, (const int8_t*)ws,
+                                           (const long long*)onsets, y, (int*)n_bad, (int)g.W, g.last, g.rs)
+                            : launch_items(ds, win::k_forward_y1<RB, XR, CB>, lds, g.W, st, gp, (const int8_t*)ws, y,
+                                           (int)g.W, (int)std::min(hop, (size_t)INT32_MAX), g.rs);
       note_launch(ds, p, st);  // the layer-1 kernel reads the copy even if the second launch failed
       return rc;
     });
   });
 }
 
-// The argument checks the windows entries share (the loaded set's and a bank's), in their
-// documented order, for a network of C channels and T samples.  arg_layout: the int8 entries' layout
-// argument (0 time-major, 1 channel-major); f32: a float32 entry (channel-major).  at: false, the
-// windows at every hop-th sample (onsets, W_at and n_bad unused); true, the W_at windows at the
-// device list onsets (hop unused).  On NET_OK what the launch takes: the gen::Layout and W.
-struct WindowsGeom {
-  int layout;
-  size_t W;
-};
-int check_windows(int C, int T, const void* x, int arg_layout, bool f32, size_t L, bool at, size_t hop,
-                  const int64_t* onsets, size_t W_at, const int8_t* y, const int32_t* n_bad, const void* ws,
-                  size_t ws_bytes, int device, WindowsGeom& g) {
-  if ((!at && hop == 0) || (!f32 && arg_layout != 0 && arg_layout != 1)) return NET_ERR_INVALID;
-  const int layout = f32 ? (int)gen::F32 : arg_layout;  // gen::Layout
-  const size_t W = at ? W_at : (hop == 0 || L < (size_t)T ? 0 : (L - (size_t)T) / hop + 1);
-  if (W && (!x || !y || !ws || (at && !onsets))) return NET_ERR_INVALID;
-  if (((uintptr_t)y & 3) != 0 || (layout == 2 && ((uintptr_t)x & 3) != 0)) return NET_ERR_INVALID;
-  if (at && (((uintptr_t)n_bad & 3) != 0 || ((uintptr_t)onsets & 7) != 0)) return NET_ERR_INVALID;
-  if (L > SIZE_MAX / 32) return NET_ERR_INVALID;  // (far past the offset limit below; 16 rs cannot wrap)
-  const size_t rs = windows_row_stride(L);
-  if (((uintptr_t)ws & 15) != 0 || ws_bytes < 16 * rs) return NET_ERR_INVALID;
-  if (at && W && L < (size_t)T) return NET_ERR_INVALID;  // no onset can be valid
-  if (device < 0 || device >= MAX_DEVICES) return NET_ERR_INVALID;
-  // window indices are int in the kernel: w + gridDim.x (grid <= 2 per CU) must not wrap
-  if (W > (size_t)INT32_MAX - 65535) return NET_ERR_INVALID;
-  // the recording and the workspace are each one buffer view with 32-bit offsets
-  const size_t per = std::max((size_t)16, (size_t)C * (layout == 2 ? sizeof(float) : 1));
-  if (L > (((size_t)1 << 31) - 1) / per) return NET_ERR_INVALID;
-  g.layout = layout;
-  g.W = W;
-  return NET_OK;
-}
-
-// Both windows entries of the loaded set.  at selects the entry (check_windows); the float scale qs.
-// The list may be null only with W_at == 0, which returns before any launch, so launch_windows,
-// reached with W > 0 only, tells the two by the list.  Every argument and parameter check comes
-// before the first device call.
+// Both windows entries of the loaded set.  at selects the entry (check_windows, entry_host.hpp); the
+// float scale qs.  The list may be null only with W_at == 0, which returns before any launch, so
+// launch_windows, reached with W > 0 only, tells the two by the list.  Every argument and parameter
+// check comes before the first device call.
 int windows_async(const void* x, int arg_layout, bool f32, size_t L, bool at, size_t hop, const int64_t* onsets,
                   size_t W_at, float qs, int8_t* y, int32_t* n_bad, void* ws, size_t ws_bytes, int device,
                   void* stream) {
@@ -330,89 +285,30 @@ int windows_async(const void* x, int arg_layout, bool f32, size_t L, bool at, si
   if (!s.host) return NET_ERR_NO_PARAMS;
   const Dims& d = s.host->d;
   WindowsGeom g;
-  if (const int rc = check_windows(d.C, d.T, x, arg_layout, f32, L, at, hop, onsets, W_at, y, n_bad, ws, ws_bytes, device, g))
+  if (const int rc = check_windows(d.C, d.T, x, arg_layout, f32, L, at, hop, onsets, W_at, y, n_bad, ws, ws_bytes, device,
+                                   win::NW1, g))
     return rc;
-  const int layout = g.layout;
-  const size_t W = g.W;
-  if (layout == 2)
+  if (g.layout == 2)
     if (const int rc = check_scale(qs)) return rc;
   const Image& win = s.img[IMG_WINDOWS];
   if (!win.data) return NET_ERR_UNSUPPORTED;
-  if (W == 0) return NET_OK;
+  if (g.W == 0) return NET_OK;
   DeviceScope sc(device, s, IMG_WINDOWS);
   if (sc.rc) return sc.rc;
-  return launch_windows(sc.ds, *(const gen::GenParams*)win.data.get(), sc.image, layout, (const int8_t*)x, L, hop, W, y,
+  return launch_windows(sc.ds, *(const gen::GenParams*)win.data.get(), sc.image, g, (const int8_t*)x, L, hop, y,
                         (int8_t*)ws, (hipStream_t)stream, qs, onsets, n_bad);
 }
 
-// The sliding windows of R recordings laid end to end (lengths[r] samples each): recording r, at
-// sample s_r = the sum of the lengths before it, contributes the onsets s_r + k hop, k <
-// windows_count(lengths[r], hop).  Returns their number W (0 on an error, writing nothing); fills
-// onsets if cap >= W and first[0 .. R] (each recording's first index, first[R] = W) if non-null.
-size_t windows_multi(const size_t* lengths, size_t R, size_t hop, int64_t* onsets, size_t cap, size_t* first) {
+// net_windows_multi_count / _onsets: windows_multi (entry_host.hpp) for the loaded network's T; 0
+// when no set is loaded.
+size_t windows_multi_loaded(const size_t* lengths, size_t R, size_t hop, int64_t* onsets, size_t cap, size_t* first) {
   const Snapshot s = snapshot();
-  if (!s.host || hop == 0 || (R && !lengths)) return 0;
-  const Dims& d = s.host->d;
-  size_t sum = 0, W = 0;  // W <= sum
-  for (size_t r = 0; r < R; r++) {
-    if (lengths[r] > (size_t)INT64_MAX - sum) return 0;  // the onsets are int64
-    sum += lengths[r];
-    W += windows_count(d, lengths[r], hop);
-  }
-  const bool fill = onsets && cap >= W;
-  size_t start = 0, i = 0;
-  for (size_t r = 0; r < R; r++) {
-    if (first) first[r] = i;
-    const size_t n = windows_count(d, lengths[r], hop);
-    if (fill)
-      for (size_t k = 0; k < n; k++) onsets[i + k] = (int64_t)(start + k * hop);
-    i += n;
-    start += lengths[r];
-  }
-  if (first) first[R] = W;
-  return W;
+  return s.host ? windows_multi((size_t)s.host->d.T, lengths, R, hop, onsets, cap, first) : 0;
 }
 
 // ---- epochs cut out of a wider array (forward_ep.hpp) -----------------------------------------
-// f32: the float32 entry (scale qs).  Every argument and parameter check comes before the first
-// device call.
-// The argument checks both epochs entries share (the loaded set's and a bank's), in their documented
-// order, for a network of C channels and T samples; on NET_OK what the kernels take of the geometry.
-struct EpochGeom {
-  ep::ChanTab tab;
-  long long last;       // n_elems - span, the largest valid onset
-  unsigned span_bytes;
-};
-int check_epochs(int C, int T, const void* x, bool f32, size_t n_elems, size_t row_stride, const int32_t* channels,
-                 const int64_t* onsets, size_t E, const int8_t* y, const int32_t* n_bad, int device, EpochGeom& g) {
-  if (E && (!x || !y || !onsets)) return NET_ERR_INVALID;
-  if (((uintptr_t)y & 3) != 0 || ((uintptr_t)n_bad & 3) != 0 || ((uintptr_t)onsets & 7) != 0) return NET_ERR_INVALID;
-  if (f32 && ((uintptr_t)x & 3) != 0) return NET_ERR_INVALID;
-  if (row_stride == 0) return NET_ERR_INVALID;
-  size_t cmax = (size_t)C - 1;  // channels == NULL: rows 0 .. C - 1
-  if (channels) {
-    cmax = 0;
-    for (int c = 0; c < C; c++) {
-      if (channels[c] < 0) return NET_ERR_INVALID;
-      cmax = std::max(cmax, (size_t)channels[c]);
-    }
-  }
-  // span = max(channels) row_stride + T elements, inside the source
-  if (cmax && row_stride > (SIZE_MAX - (size_t)T) / cmax) return NET_ERR_INVALID;
-  const size_t span = cmax * row_stride + (size_t)T;
-  if (span > n_elems) return NET_ERR_INVALID;
-  // each epoch is one buffer view with 32-bit offsets (delta <= 3 and the dword rounding on top)
-  const size_t esz = f32 ? sizeof(float) : 1;
-  if (span > (((size_t)1 << 31) - 7) / esz) return NET_ERR_INVALID;
-  // epoch indices are int in the kernel: e + gridDim.x (grid <= 2 per CU) must not wrap
-  if (E > (size_t)INT32_MAX - 65535) return NET_ERR_INVALID;
-  if (device < 0 || device >= MAX_DEVICES) return NET_ERR_INVALID;
-  for (int c = 0; c < 64; c++) g.tab.c[c] = c < C ? (channels ? channels[c] : c) : 0;
-  g.last = (long long)std::min(n_elems - span, (size_t)INT64_MAX);
-  g.span_bytes = (unsigned)(esz * span);
-  return NET_OK;
-}
-
+// f32: the float32 entry (scale qs).  Every argument and parameter check (check_epochs,
+// entry_host.hpp) comes before the first device call.
 int epochs_async(const void* x, bool f32, size_t n_elems, size_t row_stride, const int32_t* channels,
                  const int64_t* onsets, size_t E, float qs, int8_t* y, int32_t* n_bad, int device, void* stream) {
   const Snapshot s = snapshot();
@@ -430,10 +326,9 @@ int epochs_async(const void* x, bool f32, size_t n_elems, size_t row_stride, con
   if (sc.rc) return sc.rc;
   const gen::GenParams& hg = *(const gen::GenParams*)win.data.get();
   const hipStream_t st = (hipStream_t)stream;
-  const int lds = carve_of(hg, gen::F32).bytes;
   return with_flags(hg, [&](auto rb, auto xr, auto cb) {
     auto go = [&](auto kern) {
-      const int rc = launch_items(sc.ds, kern, lds, E, st, (const gen::GenParams*)sc.image, (const int8_t*)x,
+      const int rc = launch_items(sc.ds, kern, epochs_lds(hg), E, st, (const gen::GenParams*)sc.image, (const int8_t*)x,
                                   (const long long*)onsets, y, (int*)n_bad, (int)E, g.last, g.span_bytes,
                                   (unsigned long long)row_stride, g.tab, qs, recip_scale(qs));
       if (rc == NET_OK) note_launch(sc.ds, sc.image, st);
@@ -525,10 +420,9 @@ int bank_epochs_async(const net_bank* b, const void* x, bool f32, size_t n_elems
   if (sc.rc) return sc.rc;
   const auto* sets = (const gen::GenParams*)sc.image;
   const auto* scales = f32 ? (const bank::Scale*)(sets + b->sets.size()) : nullptr;
-  const int lds = carve_of(hg, gen::F32).bytes;
   return with_flags(hg, [&](auto rb, auto xr, auto cb) {
     auto go = [&](auto kern) {
-      return launch_items(sc.ds, kern, lds, E, (hipStream_t)stream, sets, (int)b->sets.size(), (const int*)set_of, scales,
+      return launch_items(sc.ds, kern, epochs_lds(hg), E, (hipStream_t)stream, sets, (int)b->sets.size(), (const int*)set_of, scales,
                           (const int8_t*)x, (const long long*)onsets, y, (int*)n_bad, (int)E, g.last, g.span_bytes,
                           (unsigned long long)row_stride, g.tab);
     };
@@ -545,7 +439,8 @@ int bank_windows_async(const net_bank* b, const void* x, int arg_layout, bool f3
   if (!b) return NET_ERR_INVALID;
   const gen::GenParams& hg = b->sets[0];
   WindowsGeom g;
-  if (const int rc = check_windows(hg.C, hg.T, x, arg_layout, f32, L, true, 0, onsets, W, y, n_bad, ws, ws_bytes, device, g))
+  if (const int rc = check_windows(hg.C, hg.T, x, arg_layout, f32, L, true, 0, onsets, W, y, n_bad, ws, ws_bytes, device,
+                                   win::NW1, g))
     return rc;
   if ((W && !blk_set) || ((uintptr_t)blk_set & 3) != 0) return NET_ERR_INVALID;
   if (f32 && b->scales.empty()) return NET_ERR_INVALID;
@@ -554,20 +449,19 @@ int bank_windows_async(const net_bank* b, const void* x, int arg_layout, bool f3
   if (sc.rc) return sc.rc;
   const auto* sets = (const gen::GenParams*)sc.image;
   const auto* scales = f32 ? (const bank::Scale*)(sets + b->sets.size()) : nullptr;
-  const int n_sets = (int)b->sets.size(), rs = (int)windows_row_stride(L), lds = carve_of(hg, 3).bytes;
-  const size_t nb = (L + 15) / 16, wgs = (nb + win::NW1 - 1) / win::NW1;
+  const int n_sets = (int)b->sets.size();
   const hipStream_t st = (hipStream_t)stream;
   return with_layout(g.layout, [&](auto lc) {
     return with_flags(hg, [&](auto rb, auto xr, auto cb) {
       constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
       // 8 workgroups of 4 waves fill a CU (launch_windows)
       hipLaunchKernelGGL((bank::k_layer1_rec_bank<decltype(lc)::value, XR, CB>),
-                         dim3((unsigned)capped_grid(sc.ds, wgs, 8)), dim3(win::NT1), 0, st, sets, n_sets,
-                         (const int*)blk_set, scales, (const int8_t*)x, (int8_t*)ws, (int)L, rs);
+                         dim3((unsigned)capped_grid(sc.ds, g.wgs, 8)), dim3(win::NT1), 0, st, sets, n_sets,
+                         (const int*)blk_set, scales, (const int8_t*)x, (int8_t*)ws, (int)L, g.rs);
       if (const int rc = hip_err(hipGetLastError())) return rc;
-      return launch_items(sc.ds, bank::k_forward_y1_bank<RB, XR, CB>, lds, W, st, sets, n_sets, (const int*)blk_set,
-                          (const int8_t*)ws, (const long long*)onsets, y, (int*)n_bad, (int)W,
-                          (long long)(L - (size_t)hg.T), rs);
+      return launch_items(sc.ds, bank::k_forward_y1_bank<RB, XR, CB>, windows_lds(hg), W, st, sets, n_sets,
+                          (const int*)blk_set, (const int8_t*)ws, (const long long*)onsets, y, (int*)n_bad, (int)W,
+                          g.last, g.rs);
     });
   });
 }
@@ -904,15 +798,12 @@ int net_model_compute_batch_multi_ct(int ndev, const int* devices, const int8_t*
 
 size_t net_windows_count(size_t L, size_t hop) {
   const Snapshot s = snapshot();
-  return s.host ? windows_count(s.host->d, L, hop) : 0;
+  return s.host ? windows_count((size_t)s.host->d.T, L, hop) : 0;
 }
 
 size_t net_windows_row_stride(size_t L) { return windows_row_stride(L); }
 
-size_t net_windows_workspace(size_t L) {
-  const size_t rs = windows_row_stride(L);
-  return rs > SIZE_MAX / 16 ? 0 : 16 * rs;
-}
+size_t net_windows_workspace(size_t L) { return windows_workspace(L); }
 
 int net_model_compute_windows(const int8_t* x, int layout, size_t L, size_t hop, int8_t* y, void* ws, size_t ws_bytes,
                               int device, void* stream) {
@@ -935,12 +826,12 @@ int net_model_compute_windows_at_f32(const float* x, size_t L, const int64_t* on
 }
 
 size_t net_windows_multi_count(const size_t* lengths, size_t R, size_t hop) {
-  return windows_multi(lengths, R, hop, nullptr, 0, nullptr);
+  return windows_multi_loaded(lengths, R, hop, nullptr, 0, nullptr);
 }
 
 size_t net_windows_multi_onsets(const size_t* lengths, size_t R, size_t hop, int64_t* onsets, size_t cap,
                                 size_t* first) {
-  return windows_multi(lengths, R, hop, onsets, cap, first);
+  return windows_multi_loaded(lengths, R, hop, onsets, cap, first);
 }
 
 int net_model_compute_epochs(const int8_t* x, size_t n_elems, size_t row_stride, const int32_t* channels,

@@ -503,11 +503,6 @@ def _layout_code(layout: str) -> int:
     return 1 if layout == "ct" else 0
 
 
-def _check_scale(f32: bool, scale, noun: str) -> None:
-    if f32 != (scale is not None):
-        raise ValueError(f"scale is required for a float32 {noun} and not accepted for an int8 one")
-
-
 def _packed_stride(C: int, T: int) -> int:
     """Bytes per trial of the batched time-major layout: C*T rounded up to 16."""
     return (C * T + 15) // 16 * 16
@@ -568,11 +563,10 @@ def windows_workspace(L: int) -> int:
     return int(load().net_windows_workspace(L))
 
 
-def _check_recording(x, dtypes, channels_first: bool):
-    """_check_tensor for a recording of the loaded network's C channels ([C][L] or [L][C]) of one
-    of ``dtypes``; returns (L, whether it is float32)."""
-    C = _dims().C
-    dt = _check_tensor(x, "the recording", dtypes, (C, "L") if channels_first else ("L", C))
+def _check_recording(x, dtypes, channels_first: bool, C: int, noun: str = "the recording"):
+    """_check_tensor for a recording of C channels ([C][L] or [L][C]) of one of ``dtypes``; returns
+    (L, whether it is float32)."""
+    dt = _check_tensor(x, noun, dtypes, (C, "L") if channels_first else ("L", C))
     return int(x.shape[1 if channels_first else 0]), dt == "float32"
 
 
@@ -594,7 +588,7 @@ def forward_windows_torch(x, hop: int, layout: str = "ct", stream=None, return_y
     forward_ct_torch returns for that window; with ``return_y1`` also the workspace
     [16][row_stride] int8, whose row f holds layer 1's filter f over the whole recording."""
     code = _layout_code(layout)
-    L, _ = _check_recording(x, ("int8",), layout == "ct")
+    L, _ = _check_recording(x, ("int8",), layout == "ct", _dims().C)
     y, ws = _windows_buffers(x, L, hop)
     s, dev = _launch(x, stream)
     _check(load().net_model_compute_windows(x.data_ptr(), code, L, hop, y.data_ptr(), ws.data_ptr(), ws.numel(), dev,
@@ -605,7 +599,7 @@ def forward_windows_torch(x, hop: int, layout: str = "ct", stream=None, return_y
 def forward_windows_f32_torch(x, hop: int, scale: float, stream=None):
     """net_model_compute_windows_f32: x is a CUDA/HIP float32 recording [C][L], quantised per
     sample as forward_f32_torch does; returns the logits [W][N] of its sliding windows."""
-    L, _ = _check_recording(x, ("float32",), True)
+    L, _ = _check_recording(x, ("float32",), True, _dims().C)
     y, ws = _windows_buffers(x, L, hop)
     s, dev = _launch(x, stream)
     _check(load().net_model_compute_windows_f32(x.data_ptr(), L, hop, scale, y.data_ptr(), ws.data_ptr(), ws.numel(),
@@ -613,57 +607,87 @@ def forward_windows_f32_torch(x, hop: int, scale: float, stream=None):
     return y
 
 
-def _forward_onsets(name: str, x, head, onsets, scale, mid, stream, check: bool, noun: str, bank=None, set_of=None,
-                    per_item_sets: bool = True):
-    """The call of an entry that takes an onset list, ``name`` or, with a ``scale``, ``name``_f32:
-    entry(x, *head, onsets, n, [scale,] y, n_bad, *mid, device, stream).  ``onsets`` is a 1-D int64
-    tensor or a sequence of ints; its device copy and, with ``check``, the zeroed counter are made
-    on the launch stream.  An empty list passes NULL for the onsets and the logits, ``check=False``
-    NULL for the counter.  With ``check`` and a non-empty list the stream is synchronised, the
-    count of onsets outside the ``noun`` read back and a ValueError raised if it is not zero.
-    Returns the logits [n][N].
-    With a ``bank`` (a Bank) the entry is ``name``, or ``name``_f32 for a float32 ``x``, and takes
-    no scale: entry(bank, x, *head, onsets, set_of, n, y, n_bad, *mid, device, stream).  ``set_of``
-    is a 1-D int32 tensor or a sequence of as many ints as there are onsets, copied like them, or
-    None (NULL: set 0 for every item, a bank of one set only); the count then covers set indices
-    outside the bank too.  ``per_item_sets=False``: a bank entry that takes no ``set_of`` at all
-    (the windows of a bank, whose block list travels in ``head``)."""
+def _require_bank(bank):
+    if not isinstance(bank, Bank):
+        raise ValueError(f"bank must be a Bank, got {type(bank).__name__}")
+    return bank
+
+
+class _Net:
+    """The network a forward entry runs, the loaded set or ``bank``: its dims, the handle that leads the
+    C call's arguments, and a float32 input's scale: an argument for the loaded set, a bank has its own."""
+
+    def __init__(self, bank=None):
+        self.bank, self.handle, self.scale = bank, () if bank is None else (bank.handle,), ()
+
+    dims = property(lambda self: _dims() if self.bank is None else self.bank.dims)
+
+    def float_input(self, f32: bool, scale, noun: str) -> None:
+        if self.bank is not None and f32 and not self.bank.has_scales:
+            raise ValueError("a float32 source needs a bank created with scales")
+        if self.bank is None and f32 != (scale is not None):
+            raise ValueError(f"scale is required for a float32 {noun} and not accepted for an int8 one")
+        self.scale = () if scale is None else (scale,)
+
+
+def _index_list(v, dtype, what: str):
+    """A 1-D tensor of ``dtype`` from one (checked) or from a sequence of ints."""
     torch = _torch()
-    if not isinstance(onsets, torch.Tensor):
-        onsets = torch.as_tensor([int(o) for o in onsets], dtype=torch.int64).reshape(-1)
-    elif onsets.dtype != torch.int64 or onsets.dim() != 1:
-        raise ValueError("onsets must be a 1-D int64 tensor or a sequence of ints")
-    n = int(onsets.numel())
-    if set_of is not None:
-        if not isinstance(set_of, torch.Tensor):
-            set_of = torch.as_tensor([int(v) for v in set_of], dtype=torch.int32).reshape(-1)
-        elif set_of.dtype != torch.int32 or set_of.dim() != 1:
-            raise ValueError("set_of must be a 1-D int32 tensor or a sequence of ints")
-        if int(set_of.numel()) != n:
-            raise ValueError(f"{int(set_of.numel())} set indices for {n} onsets")
-    elif bank is not None and per_item_sets and bank.n_sets != 1:
-        raise ValueError(f"set_of may be None only for a bank of one set, this one has {bank.n_sets}")
+    if not isinstance(v, torch.Tensor):
+        return torch.as_tensor([int(o) for o in v], dtype=dtype).reshape(-1)
+    if v.dtype != dtype or v.dim() != 1:
+        raise ValueError(f"{what} must be a 1-D {str(dtype).rpartition('.')[2]} tensor or a sequence of ints")
+    return v
+
+
+def _forward_onsets(net, name: str, x, head, onsets, mid, stream, check: bool, noun: str, set_of=False):
+    """The call of an entry of ``net`` (a _Net) that takes an onset list, ``name`` or, for a float32
+    ``x``, ``name``_f32: entry([bank,] x, *head, onsets, [set_of,] n, [scale,] y, n_bad, *mid, device,
+    stream).  ``onsets`` is a 1-D int64 tensor or a sequence of ints; ``set_of`` False (the entry takes
+    no set index per item), as many indices (a 1-D int32 tensor or a sequence), or None (NULL: set 0
+    for every item, a bank of one set only).  The lists' device copies and, with ``check``, the zeroed
+    counter are made on the launch stream.  An empty list passes NULL for the lists and the logits,
+    ``check=False`` NULL for the counter.  With ``check`` and a non-empty list the stream is
+    synchronised, the count of items outside the ``noun`` read back and a ValueError raised if it is
+    not zero.  Returns the logits [n][N]."""
+    torch = _torch()
+    lists = [_index_list(onsets, torch.int64, "onsets")]
+    n = int(lists[0].numel())
+    if set_of is None:
+        if net.bank.n_sets != 1:
+            raise ValueError(f"set_of may be None only for a bank of one set, this one has {net.bank.n_sets}")
+    elif set_of is not False:
+        lists.append(_index_list(set_of, torch.int32, "set_of"))
+        if int(lists[1].numel()) != n:
+            raise ValueError(f"{int(lists[1].numel())} set indices for {n} onsets")
     s, dev = _launch(x, stream)
     with torch.cuda.stream(s):  # the lists' copies and the counter's zeroing precede the launch on its stream
-        on = onsets.to(x.device).contiguous()
-        so = None if set_of is None else set_of.to(x.device).contiguous()
+        lists = [v.to(x.device).contiguous() for v in lists]
         nbad = torch.zeros((1,), dtype=torch.int32, device=x.device) if check else None
-    y = _logits(x, n) if bank is None else torch.empty((n, bank.dims.N), dtype=torch.int8, device=x.device)
-    if scale is not None or (bank is not None and x.dtype == torch.float32):
-        name += "_f32"
-    _check(getattr(load(), name)(*(() if bank is None else (bank.handle,)), x.data_ptr(), *head,
-                                 on.data_ptr() if n else None,
-                                 *((so.data_ptr() if n and so is not None else None,) if bank is not None and per_item_sets
-                                   else ()), n,
-                                 *(() if scale is None else (scale,)), y.data_ptr() if n else None,
-                                 nbad.data_ptr() if check else None, *mid, dev, s.cuda_stream), name)
+    y = torch.empty((n, net.dims.N), dtype=torch.int8, device=x.device)
+    name += "_f32" if x.dtype == torch.float32 else ""
+    ptrs = [v.data_ptr() if n else None for v in lists] + [None] * (set_of is None)
+    y_ptr, nbad_ptr = y.data_ptr() if n else None, nbad.data_ptr() if check else None
+    _check(getattr(load(), name)(*net.handle, x.data_ptr(), *head, *ptrs, n, *net.scale, y_ptr, nbad_ptr, *mid, dev,
+                                 s.cuda_stream), name)
     if check and n:
         s.synchronize()
         bad = int(nbad.item())
         if bad:
-            what = "onsets or set indices" if bank is not None and per_item_sets else "onsets"
+            what = "onsets" if set_of is False else "onsets or set indices"
             raise ValueError(f"{bad} of {n} {what} lie outside the {noun} (their logit rows are zero)")
     return y
+
+
+def _windows_source(net, x, layout: str, scale, noun: str):
+    """The checks of the array ``x`` (``noun``) the windows-at entries of ``net`` read: int8 ("ct" =
+    [C][L] or "tc" = [L][C]) or float32 ([C][L]).  Returns (L, the arguments that follow x)."""
+    code = _layout_code(layout)
+    L, f32 = _check_recording(x, ("int8", "float32"), layout == "ct", net.dims.C, noun)
+    if f32 and layout != "ct":
+        raise ValueError(f'a float32 {noun.rpartition(" ")[2]} is "ct" ([C][L])')
+    net.float_input(f32, scale, "recording")
+    return L, ((L,) if f32 else (code, L))
 
 
 def forward_windows_at_torch(x, onsets, layout: str = "ct", scale: Optional[float] = None, stream=None,
@@ -675,14 +699,11 @@ def forward_windows_at_torch(x, onsets, layout: str = "ct", scale: Optional[floa
     what forward_ct_torch returns for that window; with ``return_y1`` also the workspace
     [16][row_stride].  The rows of onsets outside 0 .. L - T are zero; with ``check`` their count
     is read back (a host sync) and a ValueError names it."""
-    code = _layout_code(layout)
-    L, f32 = _check_recording(x, ("int8", "float32"), layout == "ct")
-    if f32 and layout != "ct":
-        raise ValueError('a float32 recording is "ct" ([C][L])')
-    _check_scale(f32, scale, "recording")
+    net = _Net()
+    L, lead = _windows_source(net, x, layout, scale, "the recording")
     ws = _workspace(x, L)
-    y = _forward_onsets("net_model_compute_windows_at", x, (L,) if f32 else (code, L), onsets, scale,
-                        (ws.data_ptr(), ws.numel()), stream, check, "recording")
+    y = _forward_onsets(net, "net_model_compute_windows_at", x, lead, onsets, (ws.data_ptr(), ws.numel()), stream, check,
+                        "recording")
     return (y, ws) if return_y1 else y
 
 
@@ -724,6 +745,30 @@ def _plan_chunks(lengths, bytes_per_sample: int, max_bytes: int):
     return chunks
 
 
+def _check_recordings(net, tensors, layout: str, hop: int):
+    """Layout, hop and the list of recordings of a sliding-windows call on ``net``, all on one device
+    and of one element type.  Returns (the time axis, their lengths, whether they are float32)."""
+    _layout_code(layout)
+    if hop < 1:
+        raise ValueError("hop must be at least 1")
+    C = net.dims.C
+    if not tensors:
+        raise ValueError("recordings must hold at least one tensor")
+    for t in tensors:
+        _, f32 = _check_recording(t, ("int8", "float32"), layout == "ct", C)
+        if t.device != tensors[0].device or t.dtype != tensors[0].dtype:
+            raise ValueError("the recordings must be on one device and of one element type")
+    axis = 1 if layout == "ct" else 0
+    return axis, [int(t.shape[axis]) for t in tensors], f32
+
+
+def _stitch(net, x, out):
+    """The chunks' logits [W_k][N] as one tensor on ``x``'s device (no chunk: no rows)."""
+    if not out:
+        return _torch().empty((0, net.dims.N), dtype=_torch().int8, device=x.device)
+    return out[0] if len(out) == 1 else _torch().cat(out, dim=0)
+
+
 def forward_windows_multi_torch(recordings, hop: int, layout: str = "ct", scale: Optional[float] = None, stream=None,
                                 max_bytes: Optional[int] = None):
     """The sliding windows (hop ``hop``) of many recordings in one call per chunk, no window
@@ -734,31 +779,17 @@ def forward_windows_multi_torch(recordings, hop: int, layout: str = "ct", scale:
     grouped into chunks whose samples times max(16, C * element size) stay below ``max_bytes``
     (default: the entries' 2^31 limit), each chunk one forward_windows_at_torch call; no host sync."""
     torch = _torch()
-    _layout_code(layout)
-    axis = 1 if layout == "ct" else 0  # the time axis
-    if hop < 1:
-        raise ValueError("hop must be at least 1")
-    d = _dims()
+    net = _Net()
     pair = (isinstance(recordings, (tuple, list)) and len(recordings) == 2 and hasattr(recordings[0], "is_cuda")
             and not hasattr(recordings[1], "is_cuda"))
+    tensors = [recordings[0]] if pair else list(recordings)
+    axis, lengths, f32 = _check_recordings(net, tensors, layout, hop)
     if pair:
-        x, lengths = recordings[0], [int(v) for v in recordings[1]]
-        tensors = [x]
-    else:
-        tensors = list(recordings)
-        if not tensors:
-            raise ValueError("recordings must hold at least one tensor")
-    for t in tensors:
-        n, f32 = _check_recording(t, ("int8", "float32"), layout == "ct")
-        if t.device != tensors[0].device or t.dtype != tensors[0].dtype:
-            raise ValueError("the recordings must be on one device and of one element type")
-    if pair:
+        x, n, lengths = tensors[0], lengths[0], [int(v) for v in recordings[1]]
         if min(lengths, default=0) < 0 or sum(lengths) != n:
             raise ValueError(f"the lengths must be non-negative and sum to the tensor's {n} samples")
-    else:
-        lengths = [int(t.shape[axis]) for t in tensors]
-    _check_scale(f32, scale, "recording")
-    per = max(16, d.C * (4 if f32 else 1))
+    net.float_input(f32, scale, "recording")
+    per = max(16, net.dims.C * (4 if f32 else 1))
     chunks = _plan_chunks(lengths, per, 2**31 if max_bytes is None else int(max_bytes))
     s, _ = _launch(tensors[0], stream)
     starts = np.concatenate(([0], np.cumsum(lengths))).tolist()
@@ -774,10 +805,7 @@ def forward_windows_multi_torch(recordings, hop: int, layout: str = "ct", scale:
             # every generated onset is valid: no counter, no host sync
             out.append(forward_windows_at_torch(xc, torch.from_numpy(onsets), layout=layout, scale=scale, stream=s,
                                                 check=False))
-        if not out:  # no recording
-            out.append(_logits(tensors[0], 0))
-        y = out[0] if len(out) == 1 else torch.cat(out, dim=0)
-    return y, first
+        return _stitch(net, tensors[0], out), first
 
 
 def _channel_table(channels, C: int):
@@ -792,6 +820,20 @@ def _channel_table(channels, C: int):
     return (ctypes.c_int32 * C)(*ch)
 
 
+def _epoch_source(net, x, channels, row_stride, scale):
+    """The checks of the flat source ``x`` the epochs entries of ``net`` read, its ``row_stride``
+    (None: x.shape[-1]) and ``channels``.  Returns the arguments that follow x."""
+    C = net.dims.C
+    f32 = _check_tensor(x, "x", ("int8", "float32")) == "float32"
+    net.float_input(f32, scale, "source")
+    if x.dim() < 1:
+        raise ValueError("x must have at least one dimension")
+    rs = int(x.shape[-1]) if row_stride is None else int(row_stride)
+    if rs < 1:
+        raise ValueError("row_stride must be at least 1")
+    return x.numel(), rs, _channel_table(channels, C)
+
+
 def forward_epochs_torch(x, onsets, channels=None, row_stride: Optional[int] = None, scale: Optional[float] = None,
                          stream=None, check: bool = True):
     """net_model_compute_epochs / _f32: epochs of the loaded network's C x T read straight out of a
@@ -802,16 +844,9 @@ def forward_epochs_torch(x, onsets, channels=None, row_stride: Optional[int] = N
     int64 tensor or a sequence.  Returns the logits [E][N] int8, row e what forward_ct_torch
     returns for the materialised epoch.  The rows of onsets outside the source are zero; with
     ``check`` their count is read back (a host sync) and a ValueError names it."""
-    d = _dims()
-    f32 = _check_tensor(x, "x", ("int8", "float32")) == "float32"
-    _check_scale(f32, scale, "source")
-    if x.dim() < 1:
-        raise ValueError("x must have at least one dimension")
-    rs = int(x.shape[-1]) if row_stride is None else int(row_stride)
-    if rs < 1:
-        raise ValueError("row_stride must be at least 1")
-    return _forward_onsets("net_model_compute_epochs", x, (x.numel(), rs, _channel_table(channels, d.C)), onsets,
-                           scale, (), stream, check, "source")
+    net = _Net()
+    return _forward_onsets(net, "net_model_compute_epochs", x, _epoch_source(net, x, channels, row_stride, scale), onsets,
+                           (), stream, check, "source")
 
 
 def forward_crop_torch(x, t0: int, channels=None, scale: Optional[float] = None, stream=None):
@@ -849,19 +884,9 @@ def forward_epochs_bank_torch(bank, x, onsets, set_of, channels=None, row_stride
     epoch with set ``set_of[e]`` loaded.  Any order is correct; grouped by set is fast.  The rows
     of invalid onsets and of indices outside the bank are zero; with ``check`` their count is read
     back (a host sync) and a ValueError names it."""
-    if not isinstance(bank, Bank):
-        raise ValueError(f"bank must be a Bank, got {type(bank).__name__}")
-    d = bank.dims
-    f32 = _check_tensor(x, "x", ("int8", "float32")) == "float32"
-    if f32 and not bank.has_scales:
-        raise ValueError("a float32 source needs a bank created with scales")
-    if x.dim() < 1:
-        raise ValueError("x must have at least one dimension")
-    rs = int(x.shape[-1]) if row_stride is None else int(row_stride)
-    if rs < 1:
-        raise ValueError("row_stride must be at least 1")
-    return _forward_onsets("net_model_compute_epochs_bank", x, (x.numel(), rs, _channel_table(channels, d.C)), onsets,
-                           None, (), stream, check, "source or the bank", bank=bank, set_of=set_of)
+    net = _Net(_require_bank(bank))
+    return _forward_onsets(net, "net_model_compute_epochs_bank", x, _epoch_source(net, x, channels, row_stride, None),
+                           onsets, (), stream, check, "source or the bank", set_of=set_of)
 
 
 def forward_bank_torch(bank, x, set_of, stream=None, check: bool = True):
@@ -869,9 +894,7 @@ def forward_bank_torch(bank, x, set_of, stream=None, check: bool = True):
     ``set_of[b]`` of ``bank``, through forward_epochs_bank_torch as forward_crop_torch does it:
     row_stride = T, onsets[b] = b C T, built on the device.  Returns the logits [B][N]."""
     torch = _torch()
-    if not isinstance(bank, Bank):
-        raise ValueError(f"bank must be a Bank, got {type(bank).__name__}")
-    d = bank.dims
+    d = _require_bank(bank).dims
     _check_tensor(x, "x", ("int8", "float32"), ("B", d.C, d.T))
     s, _ = _launch(x, stream)
     with torch.cuda.stream(s):
@@ -884,8 +907,7 @@ def bank_windows_lists(bank, lengths, sets, hop: int):
     (hop ``hop``) of recordings of ``lengths`` samples, recording r under set ``sets[r]`` of ``bank``,
     each starting at a multiple of 16 samples.  Returns (starts, L, blk_set, onsets, first): NumPy
     arrays int64[R], int32[ceil(L / 16)], int64[W] and int64[R + 1], and L as an int."""
-    if not isinstance(bank, Bank):
-        raise ValueError(f"bank must be a Bank, got {type(bank).__name__}")
+    _require_bank(bank)
     lens, ss = [int(v) for v in lengths], [int(v) for v in sets]
     R = len(lens)
     if len(ss) != R:
@@ -919,24 +941,14 @@ def forward_windows_bank_torch(bank, x, blk_set, onsets, layout: str = "ct", str
     [16][row_stride].  A window is invalid when its onset lies outside 0 .. L - T, its first block's
     set lies outside the bank or its last block has another entry; such rows are zero, and with
     ``check`` their count is read back (a host sync) and a ValueError names it."""
-    if not isinstance(bank, Bank):
-        raise ValueError(f"bank must be a Bank, got {type(bank).__name__}")
-    code = _layout_code(layout)
-    d = bank.dims
-    dt = _check_tensor(x, "the recordings' array", ("int8", "float32"), (d.C, "L") if layout == "ct" else ("L", d.C))
-    f32 = dt == "float32"
-    if f32 and layout != "ct":
-        raise ValueError('a float32 array is "ct" ([C][L])')
-    if f32 and not bank.has_scales:
-        raise ValueError("a float32 source needs a bank created with scales")
-    L = int(x.shape[1 if layout == "ct" else 0])
+    net = _Net(_require_bank(bank))
+    L, lead = _windows_source(net, x, layout, None, "the recordings' array")
     _check_tensor(blk_set, "blk_set", ("int32",), ((L + 15) // 16,))
     if blk_set.device != x.device:
         raise ValueError("blk_set must be on the array's device")
     ws = _workspace(x, L)
-    y = _forward_onsets("net_model_compute_windows_bank", x, (L, blk_set.data_ptr()) if f32 else (code, L, blk_set.data_ptr()),
-                        onsets, None, (ws.data_ptr(), ws.numel()), stream, check, "recording or the bank", bank=bank,
-                        per_item_sets=False)
+    y = _forward_onsets(net, "net_model_compute_windows_bank", x, lead + (blk_set.data_ptr(),), onsets,
+                        (ws.data_ptr(), ws.numel()), stream, check, "recording or the bank")
     return (y, ws) if return_y1 else y
 
 
@@ -951,28 +963,15 @@ def forward_windows_multi_bank_torch(bank, recordings, sets, hop: int, layout: s
     whose samples times max(16, C * element size) stay below ``max_bytes`` (default: the entries'
     2^31 limit), each chunk one forward_windows_bank_torch call; no host sync."""
     torch = _torch()
-    if not isinstance(bank, Bank):
-        raise ValueError(f"bank must be a Bank, got {type(bank).__name__}")
-    _layout_code(layout)
-    axis = 1 if layout == "ct" else 0  # the time axis
-    if hop < 1:
-        raise ValueError("hop must be at least 1")
+    net = _Net(_require_bank(bank))
     d = bank.dims
     tensors, sets = list(recordings), [int(v) for v in sets]
-    if not tensors:
-        raise ValueError("recordings must hold at least one tensor")
+    axis, lengths, f32 = _check_recordings(net, tensors, layout, hop)
     if len(sets) != len(tensors):
         raise ValueError(f"{len(sets)} sets for {len(tensors)} recordings")
-    for t in tensors:
-        dt = _check_tensor(t, "the recording", ("int8", "float32"), (d.C, "L") if layout == "ct" else ("L", d.C))
-        if t.device != tensors[0].device or t.dtype != tensors[0].dtype:
-            raise ValueError("the recordings must be on one device and of one element type")
-    f32 = dt == "float32"
-    if f32 and not bank.has_scales:
-        raise ValueError("a float32 source needs a bank created with scales")
-    lengths = [int(t.shape[axis]) for t in tensors]
-    per = max(16, d.C * (4 if f32 else 1))
+    net.float_input(f32, None, "recording")
     # a chunk's pads add at most 15 samples per recording
+    per = max(16, d.C * (4 if f32 else 1))
     chunks = _plan_chunks([n + 15 for n in lengths], per, 2**31 if max_bytes is None else int(max_bytes))
     s, _ = _launch(tensors[0], stream)
     out, first = [], [0]
@@ -991,8 +990,7 @@ def forward_windows_multi_bank_torch(bank, recordings, sets, hop: int, layout: s
             # every generated window is valid: no counter, no host sync
             out.append(forward_windows_bank_torch(bank, xc, torch.from_numpy(blk_set).to(xc.device),
                                                   torch.from_numpy(onsets), layout=layout, stream=s, check=False))
-        y = out[0] if len(out) == 1 else torch.cat(out, dim=0)
-    return y, first
+        return _stitch(net, tensors[0], out), first
 
 
 def quantize_input_torch(x, scale: float, stream=None):

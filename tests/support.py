@@ -1,9 +1,11 @@
 """What more than one test module uses: the oracle's thread count, device placement at a byte
 offset, the materialisers and recordings of the window and epoch suites, the geometry sweep, the
-observability suites' entry runner, the pinned parameter images' table and the argument-check
-suites' fixture.  A plain module, imported as ``observability`` is; no test module imports another.
+observability suites' entry runner, the pinned parameter images' table, the argument-check
+suites' fixture and the runner of the stand-alone host programs.  A plain module, imported as ``observability`` is; no test module imports another.
 A helper with one user stays in that user's file."""
 import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -239,6 +241,31 @@ def loaded():
     lib.params_load(ps)
     yield ps
     lib.params_unload()
+
+
+# ---- the stand-alone host programs under the sanitizers ---------------------------------------------
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "mi-bminet_amd", "csrc")
+
+
+def run_host_program(main_cpp, args, tmp_path):
+    """Builds tests/`main_cpp` (it includes HIP-free headers of csrc/ only) with the host C++ compiler
+    under AddressSanitizer and UndefinedBehaviorSanitizer (once per `tmp_path`), runs it on `args` as
+    an ordinary child process, nothing loaded into Python, and returns its stdout.  A compile error,
+    a non-zero exit or anything on stderr (a sanitizer report) fails the test."""
+    exe = str(tmp_path / os.path.splitext(main_cpp)[0])
+    if not os.path.exists(exe):
+        cxx = next((shutil.which(c) for c in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++")
+                    if c and shutil.which(c)), None)
+        assert cxx, "no host C++ compiler"
+        cmd = [cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+               "-static-libasan",  # the runtime inside the program: its place in the library list cannot matter
+               "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", main_cpp)]
+        cc = subprocess.run(cmd, capture_output=True, text=True)
+        assert cc.returncode == 0, cc.stderr[-4000:]
+    run = subprocess.run([exe] + list(args), capture_output=True, text=True)
+    assert run.returncode == 0 and not run.stderr.strip(), (args, run.stdout[-2000:], run.stderr[-4000:])
+    return run.stdout
 
 
 def aligned(nbytes, align=16):

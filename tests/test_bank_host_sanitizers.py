@@ -4,17 +4,10 @@ built here with the host C++ compiler and run as an ordinary child process, once
 agreement check, the forced exact-division plan of every set and the partition bank::range_of of E
 items over G workgroups for E in {0, 1, G - 1, G, G + 1, 2^31 - 65,536} and G in {1, 3, 512}, whose
 ranges must tile [0, E) exactly.  Any sanitizer report, failed check or compile error fails the test."""
-import os
-import shutil
-import subprocess
-
-import pytest
-
 import support_bank as sb
 from mibminet.params import ParamSet
+from support import run_host_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mi-bminet_amd", "csrc")
 S, X = ParamSet.synthetic, ParamSet.synthetic_extreme
 # (the sets, the first that disagrees with set 0 or -1, which need exact division before it is forced)
 BANKS = [
@@ -28,26 +21,12 @@ BANKS = [
 ]
 
 
-def _compiler():
-    for cxx in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    pytest.fail("no host C++ compiler")
-
-
 def test_bank_host_runs_clean_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "bank_host")
-    cmd = [_compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-static-libasan",  # the runtime inside the program: its place in the library list cannot matter
-           "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "bank_host_main.cpp")]
-    cc = subprocess.run(cmd, capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-4000:]
     for b, (make, mismatch, xr) in enumerate(BANKS):
         paths = []
         for i, ps in enumerate(make()):
             paths.append(str(tmp_path / f"bank{b}_set{i}.blob"))
             with open(paths[-1], "wb") as f:
                 f.write(ps.to_blob())
-        run = subprocess.run([exe] + paths, capture_output=True, text=True)
-        assert run.returncode == 0 and not run.stderr.strip(), (b, run.stdout[-2000:], run.stderr[-4000:])
-        assert run.stdout.splitlines() == [f"bank {len(paths)} mismatch {mismatch} xr {xr}", "ranges 18"], (b, run.stdout)
+        stdout = run_host_program("bank_host_main.cpp", paths, tmp_path)
+        assert stdout.splitlines() == [f"bank {len(paths)} mismatch {mismatch} xr {xr}", "ranges 18"], (b, stdout)

@@ -4,26 +4,12 @@ csrc/requant_host.hpp and csrc/params_host.hpp, is built here with the host C++ 
 an ordinary child process.  It parses the blobs of the sets tests/test_images_cpu.py pins, plus one
 whose layer-1 offset sits at the int32 end, runs range check, folding and requant plan on each, and
 sweeps choose_reciprocal, choose_floor_form and xdiv over the factor classes against 64-bit
-division.  Any sanitizer report, failed check or compile error fails the test."""
-import os
-import shutil
-import subprocess
-
-import pytest
-
+division.  tests/entry_host_main.cpp does the same for the entries' argument arithmetic
+(csrc/entry_host.hpp).  Any sanitizer report, failed check or compile error fails the test."""
 from mibminet.params import ParamSet, dot_ranges
-from support import ROWS
+from support import ROWS, run_host_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mi-bminet_amd", "csrc")
 I32_MAX = 2 ** 31 - 1
-
-
-def _compiler():
-    for cxx in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    pytest.fail("no host C++ compiler")
 
 
 def _int32_end_set():
@@ -38,21 +24,14 @@ def _int32_end_set():
 
 
 def test_host_arithmetic_runs_clean_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "host_arith")
-    cmd = [_compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-static-libasan",  # the runtime inside the program: its place in the library list cannot matter
-           "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "host_arith_main.cpp")]
-    cc = subprocess.run(cmd, capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-4000:]
     sets = [row[0]() for row in ROWS] + [_int32_end_set()]
     paths = []
     for i, ps in enumerate(sets):
         paths.append(str(tmp_path / f"set{i}.blob"))
         with open(paths[-1], "wb") as f:
             f.write(ps.to_blob())
-    run = subprocess.run([exe] + paths, capture_output=True, text=True)
-    assert run.returncode == 0 and not run.stderr.strip(), (run.stdout[-2000:], run.stderr[-4000:])
-    lines = [ln.split() for ln in run.stdout.splitlines() if ln.startswith("set ")]
+    stdout = run_host_program("host_arith_main.cpp", paths, tmp_path)
+    lines = [ln.split() for ln in stdout.splitlines() if ln.startswith("set ")]
     assert [ln[1] for ln in lines] == paths
     got = [tuple(int(v) for v in ln[2:]) for ln in lines]  # rc, xr, layer, filter, folded
     # the plan's verdict as net_params_info reports it for the compiled geometries (the general
@@ -62,4 +41,11 @@ def test_host_arithmetic_runs_clean_under_sanitizers(tmp_path):
         want.append((0, int(exact)) + (first if path != "general" else got[len(want)][2:4]) + (folded,))
     want.append((0, 1, 1, 5, 0))
     assert got == want
-    assert "sweep 125 factors" in run.stdout
+    assert "sweep 125 factors" in stdout
+
+
+def test_entry_arithmetic_runs_clean_under_sanitizers(tmp_path):
+    """tests/entry_host_main.cpp includes only csrc/entry_host.hpp: check_windows, check_epochs,
+    windows_multi and check_scale at the documented edges of include/mibminet.h, each result held to
+    the header's rule restated in 128-bit arithmetic, the lists in arrays of exactly their size."""
+    assert run_host_program("entry_host_main.cpp", [], tmp_path).splitlines() == ["cases 4730"]

@@ -5,9 +5,6 @@ a check or has no window, so nothing is launched), what the Python entries rejec
 certification of the inputs tests/test_gpu_windows_bank.py uses, and the helpers' arithmetic in a
 stand-alone program under AddressSanitizer and UndefinedBehaviorSanitizer."""
 import ctypes
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,12 +12,10 @@ import pytest
 import support_bank as sb
 import support_windows_bank as swb
 from mibminet import lib
-from support import want, windows_at
+from support import run_host_program, want, windows_at
 
 INV, OK = lib.NET_ERR_INVALID, lib.NET_OK
 C, T, N = 22, 1125, 4
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mi-bminet_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -240,23 +235,9 @@ def test_inputs_are_certified(C, T, N):
 
 
 # ---- the helpers' arithmetic under the sanitizers ---------------------------------------------------
-def _compiler():
-    for cxx in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    pytest.fail("no host C++ compiler")
-
-
 def test_list_arithmetic_runs_clean_under_sanitizers(tmp_path):
     """tests/windows_bank_host_main.cpp includes only csrc/bank_host.hpp, is built with the host C++
     compiler and run as an ordinary child process: lengths near SIZE_MAX and INT64_MAX, R = 0, every
     list in an array of exactly its size.  Any sanitizer report, failed check or compile error fails."""
-    exe = str(tmp_path / "windows_bank_host")
-    cmd = [_compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-static-libasan",  # the runtime inside the program: its place in the library list cannot matter
-           "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "windows_bank_host_main.cpp")]
-    cc = subprocess.run(cmd, capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-4000:]
-    run = subprocess.run([exe], capture_output=True, text=True)
-    assert run.returncode == 0 and not run.stderr.strip(), (run.stdout[-2000:], run.stderr[-4000:])
-    assert run.stdout.splitlines() == ["cases 41"], run.stdout
+    stdout = run_host_program("windows_bank_host_main.cpp", [], tmp_path)
+    assert stdout.splitlines() == ["cases 41"], stdout
