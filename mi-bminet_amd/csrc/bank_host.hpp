@@ -1,21 +1,20 @@
 // bank_host.hpp — the HIP-free part of a parameter bank (net_bank_create, include/mibminet.h): which
-// sets may share a bank, the exact-division form every slice of a mixed bank takes, the
+// sets may share a bank, the exact-division form every slice of a mixed bank takes, the images of
+// a bank built from its blobs (bank::build: all of net_bank_create but the allocation), the
 // partition of an item list over the workgroups of bank::bank_loop (forward_bank.hpp), and the
 // layout and lists of many recordings' windows (net_bank_windows_starts, net_bank_windows_lists).
-// HIP-free like params_host.hpp and entry_host.hpp (whose windows_count the lists use); the kernel
-// includes it for range_of alone.
+// HIP-free like params_host.hpp, entry_host.hpp (whose windows_count the lists use) and images.hpp:
+// included by mibminet.hip and the stand-alone host programs (tests/bank_host_main.cpp,
+// tests/windows_bank_host_main.cpp); forward_bank.hpp includes it for range_of alone.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include "entry_host.hpp"
+#include "image_layout.hpp"  // MIB_HD, gen::GenParams, bank::Scale
+#include "images.hpp"
 #include "params_host.hpp"
-
-#ifdef __HIPCC__
-#define MIB_BANK_HD __host__ __device__
-#else
-#define MIB_BANK_HD
-#endif
 
 namespace mib {
 namespace bank {
@@ -26,13 +25,6 @@ namespace bank {
 inline bool agree(const HostParams& a, const HostParams& b) {
   return a.d.C == b.d.C && a.d.T == b.d.T && a.d.N == b.d.N && a.d.F1 == b.d.F1 && a.d.F2 == b.d.F2 &&
          a.d.D == b.d.D && a.reorder_bn == b.reorder_bn && a.clip_balanced == b.clip_balanced;
-}
-
-// The first set that disagrees with set 0, or -1.
-inline long first_mismatch(const HostParams* const* sets, size_t n) {
-  for (size_t i = 1; i < n; i++)
-    if (!agree(*sets[0], *sets[i])) return (long)i;
-  return -1;
 }
 
 // The plan of a set whose float forms are all proven, as make_plan leaves one that has an unproven
@@ -50,6 +42,59 @@ inline void force_exact(const HostParams& hp, Plan& pl) {
   }
 }
 
+// One set of a bank: the blob through the loader's own path (parse_blob, build_set), its window
+// image kept.  hp comes back as build_set leaves it.
+inline int bank_set(const void* blob, size_t len, bool force_general, HostParams& hp, gen::GenParams& gp) {
+  if (const int rc = parse_blob(blob, len, hp)) return rc;
+  Image img, win;
+  if (const int rc = build_set(hp, force_general, &img, &win)) return rc;
+  if (!win.data) return NET_ERR_UNSUPPORTED;
+  gp = *(const gen::GenParams*)win.data.get();
+  return NET_OK;
+}
+
+// The image of a float set in the exact-division form (force_exact), for a bank some other set of
+// which needs exact division.
+inline int bank_set_exact(const HostParams& hp, gen::GenParams& gp) {
+  Ranges rg;
+  if (const int rc = check_ranges(hp, rg)) return rc;
+  Plan pl = make_plan(hp, rg);
+  force_exact(hp, pl);
+  return build_genparams(hp, pl, gp);
+}
+
+// The images of a bank of n_sets blobs (scales: one per set, or null), in order: each set parsed and
+// built as bank_set does, held to set 0 (agree), its scale checked; then, where some sets need exact
+// division and others do not, the others promoted (bank_set_exact).  Returns the first error, *failed
+// (if non-null) the set it belongs to; sets and scales then hold nothing a caller may use.
+inline int build(const void* const* blobs, const size_t* sizes, const float* scales, size_t n_sets, bool force_general,
+                 std::vector<gen::GenParams>& sets, std::vector<Scale>& out_scales, size_t* failed) {
+  auto fail = [&](size_t i, int rc) {
+    if (failed) *failed = i;
+    return rc;
+  };
+  sets.clear();
+  sets.resize(n_sets);
+  out_scales.clear();
+  std::vector<HostParams> hps(n_sets);
+  bool any_xr = false, all_xr = true;
+  for (size_t i = 0; i < n_sets; i++) {
+    if (const int rc = bank_set(blobs[i], sizes[i], force_general, hps[i], sets[i])) return fail(i, rc);
+    if (!agree(hps[0], hps[i])) return fail(i, NET_ERR_UNSUPPORTED);
+    if (scales) {
+      if (const int rc = check_scale(scales[i])) return fail(i, rc);
+      out_scales.push_back(Scale{scales[i], recip_scale(scales[i])});
+    }
+    any_xr = any_xr || sets[i].xr;
+    all_xr = all_xr && sets[i].xr;
+  }
+  if (any_xr && !all_xr)
+    for (size_t i = 0; i < n_sets; i++)
+      if (!sets[i].xr)
+        if (const int rc = bank_set_exact(hps[i], sets[i])) return fail(i, rc);
+  return NET_OK;
+}
+
 // Workgroup w of G takes the items [lo, hi) = [floor(w E / G), floor((w + 1) E / G)): contiguous, so
 // that on a list grouped by set a workgroup changes sets at most once per set its range touches.
 // The ranges of w = 0 .. G - 1 tile [0, E) in order; w E < 2^63 for every grid and every E the
@@ -57,7 +102,7 @@ inline void force_exact(const HostParams& hp, Plan& pl) {
 struct Range64 {
   long long lo, hi;
 };
-MIB_BANK_HD inline Range64 range_of(unsigned w, unsigned G, unsigned long long E) {
+MIB_HD inline Range64 range_of(unsigned w, unsigned G, unsigned long long E) {
   return Range64{(long long)((unsigned long long)w * E / G), (long long)(((unsigned long long)w + 1) * E / G)};
 }
 

@@ -11,9 +11,9 @@
 #include <utility>
 #include <vector>
 
-#include "entry_host.hpp"  // MAX_DEVICES
-#include "forward_bank.hpp"
-#include "images.hpp"
+#include "entry_host.hpp"    // MAX_DEVICES
+#include "image_layout.hpp"  // gen::GenParams, bank::Scale
+#include "images.hpp"        // Image
 
 // A parameter bank (net_bank_t, include/mibminet.h): the images of its sets, immutable after
 // net_bank_create, and one device copy per device that has run a call on it.  A copy is the n_sets

@@ -26,14 +26,10 @@
 #include "bank_host.hpp"
 #include "forward_ep.hpp"
 #include "forward_win.hpp"
+#include "image_layout.hpp"  // bank::Scale
 
 namespace mib {
 namespace bank {
-
-// The input quantiser's scale of one set and RN(1 / scale), both from the host.
-struct Scale {
-  float qs, qy;
-};
 
 // Fused forward over E epochs of the source x (layout L: CT int8, F32 float32), logits [E][N].
 // sets: n_sets images of one geometry and one (RB, XR, CB); set_of: E set indices, or null (set 0);

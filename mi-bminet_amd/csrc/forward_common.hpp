@@ -1,5 +1,6 @@
-// forward_common.hpp — types, parameter images and helpers of the gfx950 forward kernel
-// (forward_wg.hpp).
+// forward_common.hpp — types and device helpers of the gfx950 forward kernel (forward_wg.hpp).  The
+// parameter images it reads (DevParams, SmallParams) and the constexpr helpers the host shares are
+// image_layout.hpp's.
 //
 // Requantisation y = clip(trunc((acc + off) / fac), -128, 127) is computed as
 // clip(int(float(acc + off) * r)) with r chosen on the host (requant_host.hpp: choose_reciprocal) and
@@ -12,27 +13,17 @@
 
 #include <type_traits>
 
-#include "net_consts.hpp"  // F2, N_OUT, FMAGIC_I
+#include "image_layout.hpp"  // v4i, DevParams, SmallParams, pbias, align16 and the rest of the layouts
+#include "net_consts.hpp"   // F2, N_OUT, FMAGIC_I
 
 namespace mib {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 
 constexpr int L2_TAPS = 64;
 constexpr int L3_TAPS = 16;
-constexpr int ND5_MAX = 96;     // dwords of the layer-4 output [F2][T64_ALIGN] (F2*T64_ALIGN <= 384)
 constexpr float FMAGIC_F = 12582912.0f; // 1.5 * 2^23
-// REORDER_BN pooling bias: the layer-2 MFMA chains start from a bias B (the bits of a
-// float MFMA srcC inline constant), so every conv value a lies at a + B with no wrap (|a| < 2^22),
-// and max(a, thr) - thr = sat_u32((a + B) - (thr + B)): one full-rate v_sub_u32 clamp per element
-// instead of a quarter-rate v_max_i32 (tools/vthru.hip: 2.45 vs 4.21 SIMD cycles).  Each chain
-// gets a constant of its own (filter slot 0: 1.0, slot 1: 2.0, the tail: 4.0): a constant shared
-// by two chains is hoisted into a 16-register tuple instead of riding in the instruction.
-// (layer 4 uses 0.5, -0.5 and -1.0: forward_wg.hpp, bias4)
-__host__ __device__ constexpr int pbias(int slot) { return slot == 0 ? 0x3F800000 : slot == 1 ? 0x40000000 : 0x40800000; }
-constexpr int PBIAS_TAIL = pbias(2);
 
 // Diagnostic phase stamps (tools/probe.hip builds with -DMIB_STAMPS; compiled out otherwise).
 #ifdef MIB_STAMPS
@@ -68,86 +59,6 @@ __device__ unsigned long long g_clk[2 * CLK_SLOTS];
 #define MIB_CLOCK_INIT
 #define MIB_CLOCK_FLUSH
 #endif
-
-__host__ __device__ constexpr int align16(int x) { return (x + 15) & ~15; }
-__host__ __device__ constexpr int cmax(int a, int b) { return a > b ? a : b; }
-__host__ __device__ constexpr int cmin(int a, int b) { return a < b ? a : b; }
-// smallest multiple of 4 >= x whose dword count is odd (conflict-free strided dword reads)
-__host__ __device__ constexpr int odd_dwords(int x) { return ((x + 3) / 4 % 2) ? (x + 3) / 4 * 4 : (x + 3) / 4 * 4 + 4; }
-
-// Parameters read into LDS by every workgroup.
-struct SmallParams {
-  v4i l4_bfrag[64];       // layer-4 B operand per lane (block diagonal, see host)
-  v4i l2_tpar[F2];        // layer-2 tail per filter: {PBIAS_TAIL + thr, off + 8 thr, bits of r, 0}
-                          // (thr = -(net_l2_offset >> 3); off + 8 thr = net_l2_offset & 7);
-                          // XR: {.., .., xdiv magic, shift word}
-  int l4_thr[F2];         // -(net_l4_offset >> 3), clamped to the conv range (images.hpp)
-  int l4_offm[F2];        // net_l4_offset + 8 thr
-  union {
-    float l4_r[F2];
-    unsigned l4_m[F2];    // XR: xdiv magic
-  };
-  // plain (non-REORDER_BN) layer-2/4 branches: per-element BN with offset >> 3 and factor >> 3 in
-  // the floor form (requant_host.hpp, choose_floor_form): MFMA C-init = per-filter magic bits + offset,
-  // reciprocal r and integer-valued c, so that fma(acc bits, r, c) = FMAGIC + floor(element).
-  // XR: C-init = offset >> 3, xdiv magic and shift word; l2_xs / l4_xs are also the shift words of
-  // the REORDER_BN builds' layer-2 / layer-4 requant (whose plain fields are unused)
-  int l2n_ci[F2];
-  union {
-    float l2n_r[F2];
-    unsigned l2n_m[F2];
-  };
-  union {
-    float l2n_c[F2];
-    int l2_xs[F2];
-  };
-  int l4n_ci[F2];
-  union {
-    float l4n_r[F2];
-    unsigned l4n_m[F2];
-  };
-  union {
-    float l4n_c[F2];
-    int l4_xs[F2];
-  };
-  int l5_w[N_OUT][ND5_MAX];  // [k][v] with row stride T64_ALIGN, zero padded
-  int l5_b[N_OUT];
-  float l3_r;
-  float l5_r;
-  float l3_c;             // -(1.5 * 2^23) * l3_r (layer 3's magic C-init requant)
-  int pad[1];
-};
-
-// Operand fragments and requantisation constants, built by the host from the net.h arrays.
-struct DevParams {
-  v4i l1_wfrag[2][64];      // layer-1 B operand per N-tile and lane
-  int l1_cinit[2][16];      // offset + FMAGIC_I per N-tile column (XR: offset)
-  union {
-    float l1_r[2][16];      // reciprocal per N-tile column
-    unsigned l1_m[2][16];   // XR: xdiv magic
-  };
-  union {
-    float l1_c[2][16];      // -(1.5 * 2^23) * r, exact
-    int l1_xs[2][16];       // XR: xdiv shift word
-  };
-  v4i l2_afrag[F2][3][64];  // layer-2 A operand (banded weights) per filter, K-step and lane
-  int l2_thrb[F2];          // pbias(f & 1) + thr, thr = -(net_l2_offset >> 3) clamped: full-tile threshold
-  int l2_offm[F2];          // net_l2_offset + 8 thr
-  union {
-    float l2_r[F2];
-    unsigned l2_m[F2];      // XR: xdiv magic (shift word: sp.l2_xs)
-  };
-  // layer-3 A operands per filter pair (wave) and lane, MFMA 16x16x64 with a block-diagonal K
-  // (forward_wg.hpp, layer3): tile 1 = 16 shifts x both filters' 32-slot bands, tile 2 = the same
-  // with shift g on row 4g and the other rows zero
-  v4i l3_a1[F2 / 2][64];
-  v4i l3_a2[F2 / 2][64];
-  // layer-2 tail A operand per filter pair (wave) and K-step: MFMA 16x16x64, 16 shifts x 192
-  // K-slots = the two filters' 96-slot bands side by side (K block diagonal, see forward_wg.hpp)
-  v4i l2t_afrag[F2 / 2][3][64];
-  SmallParams sp;
-  v4i l1_wfrag_ct[2][64];   // layer-1 B operand for the channel-major staging's K-slot order (stage_block)
-};
 
 // LO: lower clip bound, -128 (the C's __CLIP_R(x, 127), clip_balanced=False) or -127
 // (golden_model.py clip_balanced=True, functional.py:89-91)

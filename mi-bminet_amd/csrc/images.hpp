@@ -1,12 +1,14 @@
 // images.hpp — the two parameter images the kernels read, laid out from a parsed set and its
-// requant plan (params_host.hpp): DevParams for the compiled geometries (forward_wg.hpp) and
-// gen::GenParams for the run-time-dimension kernels (forward_gen.hpp, forward_win.hpp,
-// forward_ep.hpp).  Neither builder searches for a constant.
+// requant plan (params_host.hpp) in the layouts of image_layout.hpp: DevParams for the compiled
+// geometries (forward_wg.hpp) and gen::GenParams for the run-time-dimension kernels
+// (forward_gen.hpp, forward_win.hpp, forward_ep.hpp).  Neither builder searches for a constant.
+// HIP-free like params_host.hpp: included by device_state.hpp and bank_host.hpp, and built into the
+// stand-alone host programs (tests/host_arith_main.cpp, tests/bank_host_main.cpp).
 #pragma once
-#include <atomic>
 #include <memory>
 
-#include "forward_gen.hpp"
+#include "entry_host.hpp"  // gen::Layout
+#include "image_layout.hpp"
 #include "params_host.hpp"
 
 namespace mib {
@@ -25,6 +27,13 @@ Image make_image(std::shared_ptr<P> p) {
   im.bytes = sizeof(P);
   im.data = std::move(p);
   return im;
+}
+// FNV-1a over an image's bytes (mibminet_test_image_digest; the pinned digests of tests/support.py)
+inline uint64_t fnv1a(const Image& im) {
+  uint64_t h = 1469598103934665603ull;
+  const uint8_t* p = (const uint8_t*)im.data.get();
+  for (size_t i = 0; i < im.bytes; i++) h = (h ^ p[i]) * 1099511628211ull;
+  return h;
 }
 
 // ---- fragments both families read ------------------------------------------------------------
@@ -224,20 +233,17 @@ inline int gen_supported(const Dims& d) {
   return NET_OK;
 }
 
-// Requant: the plan's float forms at layers 1-4 where every one is proven (gp.xr = 0), exact integer
-// division (xdiv) at layers 1-4 otherwise (gp.xr = 1, the float fields zero); layer 5 always
-// divides exactly.  The xdiv constants are there either way.
-inline int build_genparams(const HostParams& hp, const Plan& pl, gen::GenParams& gp) {
-  const Dims& d = hp.d;
-  if (const int rc = gen_supported(d)) return rc;
-  std::memset(&gp, 0, sizeof(gp));
-  const int C = d.C, CA = d.C_ALIGN(), T8 = d.T8(), T64 = d.T64(), T64A = d.T64_ALIGN();
-  gp.C = C;
+// The geometry of a supported set, the part of the image that depends on its dimensions alone (and
+// all gen::carve_of takes): the layer-1 blocks, layer 2's tiles, the last wave's share of layer 1 and
+// the time-major trial stride.
+inline void gen_geometry(const Dims& d, gen::GenParams& gp) {
+  const int T8 = d.T8(), T64 = d.T64();
+  gp.C = d.C;
   gp.T = d.T;
   gp.N = d.N;
   gp.T8 = T8;
   gp.T64 = T64;
-  gp.T64A = T64A;
+  gp.T64A = d.T64_ALIGN();
   gp.NB1 = (d.T + 15) / 16;
   const int NB2 = (8 * T8 + 31) / 32;  // layer-2 column blocks of 32 outputs
   // full 32x32 tiles of 32 blocks; at most 16 blocks left go to 16x16x64 tail tiles (16 columns of
@@ -253,10 +259,21 @@ inline int build_genparams(const HostParams& hp, const Plan& pl, gen::GenParams&
   // time-major at one workgroup per CU: two fewer (same box: -0.9 ... -2.6 %; channel-major
   // measured +1.5 % and keeps K7, profiles/r06_ab_k7.txt)
   gp.K7T1 = std::max(0, gp.K7 - 2);
+  gp.xstride = (int)trial_stride(d);
+}
+
+// Requant: the plan's float forms at layers 1-4 where every one is proven (gp.xr = 0), exact integer
+// division (xdiv) at layers 1-4 otherwise (gp.xr = 1, the float fields zero); layer 5 always
+// divides exactly.  The xdiv constants are there either way.
+inline int build_genparams(const HostParams& hp, const Plan& pl, gen::GenParams& gp) {
+  const Dims& d = hp.d;
+  if (const int rc = gen_supported(d)) return rc;
+  std::memset(&gp, 0, sizeof(gp));
+  gen_geometry(d, gp);
+  const int C = d.C, CA = d.C_ALIGN(), T64 = d.T64(), T64A = d.T64_ALIGN();
   const bool rb = hp.reorder_bn, xr = pl.xr || !pl.l3_ok;
   gp.rb = rb ? 1 : 0;
   gp.lo = hp.clip_balanced ? -127 : -128;
-  gp.xstride = (int)(((size_t)C * d.T + 15) / 16 * 16);
   gp.xr = xr ? 1 : 0;
   // layer 1: lane (filter j, K group g) holds channels 16 c .. 16 c + 15 (zero past C) of chunk c:
   // time-major c = gen::l1_chunk(g, C), zero in K groups 1 and 3 when C <= 32 (their lanes re-read

@@ -6,8 +6,11 @@
 //   requant plan;
 // * entry_host.hpp: the entries' argument arithmetic (scale, strides, counts, the windows and epochs
 //   checks with the launch geometry they validate);
-// * bank_host.hpp: the HIP-free part of a parameter bank;
-// * images.hpp: the gfx950 operand fragments and both parameter images;
+// * image_layout.hpp: the layouts of both parameter images, the LDS carve and a bank's scale entry,
+//   shared with the kernels (HIP-free);
+// * images.hpp: the gfx950 operand fragments and both parameter images, laid out from the plan
+//   (HIP-free);
+// * bank_host.hpp: the HIP-free part of a parameter bank, the build of its images included;
 // * device_state.hpp: the loaded set, the per-device image cache and the scoped launch entry;
 // * test_hooks.hpp: include/mibminet_testing.h.
 // There is no CPU compute path: without a usable HIP device every entry point returns an error.
@@ -340,57 +343,7 @@ int epochs_async(const void* x, bool f32, size_t n_elems, size_t row_stride, con
 }
 
 // ---- parameter banks (forward_bank.hpp, bank_host.hpp) ---------------------------------------
-// One set of a bank: the blob through the loader's own path (parse_blob, build_set), its window
-// image kept.  hp comes back as build_set leaves it.
-int bank_set(const void* blob, size_t len, HostParams& hp, gen::GenParams& gp) {
-  if (const int rc = parse_blob(blob, len, hp)) return rc;
-  Image img, win;
-  if (const int rc = build_set(hp, g_force_general.load() != 0, &img, &win)) return rc;
-  if (!win.data) return NET_ERR_UNSUPPORTED;
-  gp = *(const gen::GenParams*)win.data.get();
-  return NET_OK;
-}
-
-// The image of a float set in the exact-division form (bank::force_exact), for a bank some other set
-// of which needs exact division.
-int bank_set_exact(const HostParams& hp, gen::GenParams& gp) {
-  Ranges rg;
-  if (const int rc = check_ranges(hp, rg)) return rc;
-  Plan pl = make_plan(hp, rg);
-  bank::force_exact(hp, pl);
-  return build_genparams(hp, pl, gp);
-}
-
-int bank_create(const void* const* blobs, const size_t* sizes, const float* scales, size_t n_sets, net_bank** out,
-                size_t* failed) {
-  if (out) *out = nullptr;
-  if (!blobs || !sizes || !out || n_sets == 0 || n_sets > NET_BANK_MAX_SETS) return NET_ERR_INVALID;
-  auto fail = [&](size_t i, int rc) {
-    if (failed) *failed = i;
-    return rc;
-  };
-  auto b = std::make_unique<net_bank>();
-  b->sets.resize(n_sets);
-  std::vector<HostParams> hps(n_sets);
-  bool any_xr = false, all_xr = true;
-  for (size_t i = 0; i < n_sets; i++) {
-    if (const int rc = bank_set(blobs[i], sizes[i], hps[i], b->sets[i])) return fail(i, rc);
-    if (!bank::agree(hps[0], hps[i])) return fail(i, NET_ERR_UNSUPPORTED);
-    if (scales) {
-      if (const int rc = check_scale(scales[i])) return fail(i, rc);
-      b->scales.push_back(bank::Scale{scales[i], recip_scale(scales[i])});
-    }
-    any_xr = any_xr || b->sets[i].xr;
-    all_xr = all_xr && b->sets[i].xr;
-  }
-  if (any_xr && !all_xr)
-    for (size_t i = 0; i < n_sets; i++)
-      if (!b->sets[i].xr)
-        if (const int rc = bank_set_exact(hps[i], b->sets[i])) return fail(i, rc);
-  *out = b.release();
-  return NET_OK;
-}
-
+// (a bank's images are built by bank::build, bank_host.hpp: net_bank_create below only allocates)
 void bank_destroy(net_bank* b) {
   if (!b) return;
   for (const auto& c : b->dev) {
@@ -845,9 +798,16 @@ int net_model_compute_epochs_f32(const float* x, size_t n_elems, size_t row_stri
   return epochs_async(x, true, n_elems, row_stride, channels, onsets, E, scale, y, n_bad, device, stream);
 }
 
+// The images of the sets (bank::build, bank_host.hpp) in a net_bank of their own.
 int net_bank_create(const void* const* blobs, const size_t* sizes, const float* scales, size_t n_sets,
                     net_bank_t** bank, size_t* failed) {
-  return bank_create(blobs, sizes, scales, n_sets, bank, failed);
+  if (bank) *bank = nullptr;
+  if (!blobs || !sizes || !bank || n_sets == 0 || n_sets > NET_BANK_MAX_SETS) return NET_ERR_INVALID;
+  auto b = std::make_unique<net_bank>();
+  if (const int rc = bank::build(blobs, sizes, scales, n_sets, g_force_general.load() != 0, b->sets, b->scales, failed))
+    return rc;
+  *bank = b.release();
+  return NET_OK;
 }
 
 int net_bank_info(const net_bank_t* bank, int32_t* info) {

@@ -1,5 +1,5 @@
-// net_consts.hpp — the constants shared by the device code (forward_common.hpp) and the HIP-free
-// host code (params_host.hpp).
+// net_consts.hpp — the constants shared by the device code (forward_common.hpp), the layouts
+// (image_layout.hpp) and the HIP-free host code (params_host.hpp).
 #pragma once
 
 namespace mib {

@@ -38,36 +38,55 @@ struct HostParams {
   int folded = 0;              // set at load: constant filters folded (fold_constant_filters)
 };
 
+// The dimensions of a header, a blob's and a net_arrays_t's alike: positive, T of at least one
+// layer-5 sample, and F2 = F1 D without trusting int to hold the product.  What the kernels support
+// of them is build_set's business (images.hpp).
+inline int check_dims(const Dims& d) {
+  if (d.C <= 0 || d.T < 64 || d.F1 <= 0 || d.D < 1 || d.F2 < 1 || d.N <= 0) return NET_ERR_BLOB;
+  return (int64_t)d.F2 == (int64_t)d.F1 * d.D ? NET_OK : NET_ERR_BLOB;
+}
+
 // ---- blob parsing ------------------------------------------------------------------------
+// Every array is sized from the header, so each read first tests that the bytes left cover it: a
+// header cannot make the reader allocate more than the blob holds.  pos <= n while ok.
 struct Reader {
   const uint8_t* p;
   size_t n, pos;
   bool ok = true;
   const uint8_t* take(size_t bytes) {
-    if (!ok || pos + bytes > n) { ok = false; return nullptr; }
+    if (!ok || bytes > n - pos) { ok = false; return nullptr; }
     const uint8_t* r = p + pos;
-    pos += bytes + ((4 - bytes % 4) % 4);
-    if (pos > n) { ok = false; return nullptr; }
+    pos += bytes;
+    const size_t pad = (4 - bytes % 4) % 4;
+    if (pad > n - pos) { ok = false; return nullptr; }
+    pos += pad;
     return r;
   }
+  int32_t one() {
+    int32_t v = 0;
+    if (const uint8_t* s = take(4)) std::memcpy(&v, s, 4);
+    return v;
+  }
   std::vector<int32_t> i32(size_t count) {
-    std::vector<int32_t> v(count);
+    if (count > (n - pos) / 4) ok = false;
     const uint8_t* s = take(4 * count);
+    std::vector<int32_t> v(s ? count : 0);
     if (s) std::memcpy(v.data(), s, 4 * count);
     return v;
   }
-  std::vector<int8_t> w(size_t count, int wbits) {
-    std::vector<int8_t> v(count);
+  // count = a b weights of wbits bits (a product past size_t covers nothing)
+  std::vector<int8_t> w(size_t a, size_t b, int wbits) {
+    const size_t count = b && a > SIZE_MAX / b ? SIZE_MAX : a * b;
+    const uint8_t* s = take(wbits == 8 ? count : count / 2 + count % 2);
+    std::vector<int8_t> v(s ? count : 0);
+    if (!s) return v;
     if (wbits == 8) {
-      const uint8_t* s = take(count);
-      if (s) std::memcpy(v.data(), s, count);
+      std::memcpy(v.data(), s, count);
     } else {
-      const uint8_t* s = take((count + 1) / 2);
-      if (s)
-        for (size_t i = 0; i < count; i++) {
-          int nib = (s[i / 2] >> (4 * (i & 1))) & 0xF;
-          v[i] = (int8_t)(nib >= 8 ? nib - 16 : nib);
-        }
+      for (size_t i = 0; i < count; i++) {
+        int nib = (s[i / 2] >> (4 * (i & 1))) & 0xF;
+        v[i] = (int8_t)(nib >= 8 ? nib - 16 : nib);
+      }
     }
     return v;
   }
@@ -105,32 +124,32 @@ inline int parse_blob(const void* blob, size_t len, HostParams& hp) {
   hp.reorder_bn = (flags & FLAG_REORDER_BN) != 0;
   hp.clip_balanced = (flags & FLAG_CLIP_BALANCED) != 0;
   if (d.wbits != 8 && d.wbits != 4) return NET_ERR_BLOB;
-  if (d.C <= 0 || d.T < 64 || d.F1 <= 0 || d.N <= 0 || d.F2 != d.F1 * d.D) return NET_ERR_BLOB;
+  if (const int rc = check_dims(d)) return rc;
   Reader r{b, len, (size_t)HEADER_SIZE};
-  const int F2 = d.F2;
+  const size_t F2 = (size_t)d.F2;
   hp.d = d;
   hp.l1_factor = r.i32(F2); hp.l1_offset = r.i32(F2);
-  hp.l1_weight_align = r.w((size_t)F2 * d.C_ALIGN(), d.wbits);
+  hp.l1_weight_align = r.w(F2, (size_t)d.C_ALIGN(), d.wbits);
   hp.l2_factor = r.i32(F2); hp.l2_offset = r.i32(F2);
-  hp.l2_weight_reverse = r.w((size_t)F2 * 64, d.wbits);
-  hp.l3_factor = r.i32(1)[0];
-  hp.l3_weight = r.w((size_t)F2 * 16, d.wbits);
+  hp.l2_weight_reverse = r.w(F2, 64, d.wbits);
+  hp.l3_factor = r.one();
+  hp.l3_weight = r.w(F2, 16, d.wbits);
   hp.l4_factor = r.i32(F2); hp.l4_offset = r.i32(F2);
-  hp.l4_weight = r.w((size_t)F2 * F2, d.wbits);
-  hp.l5_factor = r.i32(1)[0];
-  hp.l5_bias = r.w(d.N, 8);
-  hp.l5_weight = r.w((size_t)d.N * F2 * d.T64_ALIGN(), d.wbits);
+  hp.l4_weight = r.w(F2, F2, d.wbits);
+  hp.l5_factor = r.one();
+  hp.l5_bias = r.w((size_t)d.N, 1, 8);
+  hp.l5_weight = r.w((size_t)d.N, F2 * (size_t)d.T64_ALIGN(), d.wbits);  // F2 T64_ALIGN < 2^56
   if (!r.ok || r.pos != len) return NET_ERR_BLOB;
   return check_pads(hp);
 }
 
-// net_params_load_arrays: the blob header's checks (parse_blob), then the arrays it would carry
+// net_params_load_arrays: the blob header's checks (parse_blob, check_dims), then the arrays it would carry
 inline int parse_arrays(const net_arrays_t* a, HostParams& hp) {
   if (!a) return NET_ERR_INVALID;
   if (a->flags & ~(FLAG_REORDER_BN | FLAG_CLIP_BALANCED)) return NET_ERR_BLOB;
   Dims d;
   d.C = a->C; d.T = a->T; d.F1 = a->F1; d.F2 = a->F2; d.D = a->D; d.N = a->N; d.wbits = 8;
-  if (d.C <= 0 || d.T < 64 || d.F1 <= 0 || d.N <= 0 || d.F2 != d.F1 * d.D) return NET_ERR_BLOB;
+  if (const int rc = check_dims(d)) return rc;
   if ((size_t)d.C * d.T > ((size_t)1 << 30) || d.N > 4096 || d.F2 > 4096) return NET_ERR_UNSUPPORTED;
   if (!a->l1_factor || !a->l1_offset || !a->l1_weight_align || !a->l2_factor || !a->l2_offset ||
       !a->l2_weight_reverse || !a->l3_weight || !a->l4_factor || !a->l4_offset || !a->l4_weight || !a->l5_bias ||

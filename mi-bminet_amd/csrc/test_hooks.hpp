@@ -87,11 +87,7 @@ int mibminet_test_image_digest(uint64_t* digest) {
   if (!digest) return NET_ERR_INVALID;
   Snapshot s = snapshot();
   if (!s.host) return NET_ERR_NO_PARAMS;
-  uint64_t h = 1469598103934665603ull;  // FNV-1a over the image bytes
-  const Image& img = s.img[IMG_KERNELS];
-  const uint8_t* p = (const uint8_t*)img.data.get();
-  for (size_t i = 0; i < img.bytes; i++) h = (h ^ p[i]) * 1099511628211ull;
-  *digest = h;
+  *digest = fnv1a(s.img[IMG_KERNELS]);
   return NET_OK;
 }
 

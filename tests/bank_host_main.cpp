@@ -1,12 +1,16 @@
 // bank_host_main.cpp — the HIP-free part of a parameter bank as a stand-alone program (tests/
 // test_bank_host_sanitizers.py builds it with -fsanitize=address,undefined and runs it).  The blobs
-// named on the command line are one bank: each is parsed and range-checked as net_bank_create does,
-// the agreement check names the first set that disagrees with set 0, and every set's plan is forced
-// to the exact-division form, which must keep the xdiv constants and drop every float form.  Then
-// bank::range_of is swept: the ranges of the G workgroups must tile [0, E) in order, each holding
-// floor(E / G) or one more item.  Prints "bank <n> mismatch <i> xr <flags>" and "ranges <cases>";
-// exits 0 when every check held.
+// named on the command line are one bank, built by bank::build, the function net_bank_create calls:
+// the first set refused and its code are printed with, per set, whether it needs exact division
+// when loaded alone (build_set on that blob, so the flags exist for a refused bank too).  A bank that
+// is not mixed must hold, byte for byte, the window image each blob gets alone; in a mixed bank that
+// holds for the sets that need exact division, and every promoted set must have xr = 1, no float
+// form and no magic in a C-init, and the xdiv constants of its own plan.  Then bank::range_of is
+// swept: the ranges of the G workgroups must tile [0, E) in order, each holding floor(E / G) or one
+// more item.  Prints "bank <n> refused <i> rc <code> xr <flags>" and "ranges <cases>"; exits 0 when
+// every check held.
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 #include <iterator>
 #include <string>
@@ -25,38 +29,64 @@ static int g_bad = 0;
   } while (0)
 
 static void run_bank(int n, char** paths) {
-  std::vector<HostParams> hps((size_t)n);
-  std::vector<const HostParams*> ptrs;
+  const size_t ns = (size_t)n;
+  std::vector<std::vector<char>> blobs(ns);
+  std::vector<const void*> ptrs(ns);
+  std::vector<size_t> sizes(ns);
+  std::vector<float> scales(ns);
+  // each set alone, as net_params_load would take it
+  std::vector<HostParams> hps(ns);
+  std::vector<Image> wins(ns);
   std::string flags;
-  for (int i = 0; i < n; i++) {
+  for (size_t i = 0; i < ns; i++) {
     std::ifstream in(paths[i], std::ios::binary);
-    const std::vector<char> blob((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
-    HostParams& hp = hps[(size_t)i];
-    int rc = parse_blob(blob.data(), blob.size(), hp);
+    blobs[i].assign((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    ptrs[i] = blobs[i].data();
+    sizes[i] = blobs[i].size();
+    scales[i] = 1.0f + (float)i;
+    Image img;
+    int rc = parse_blob(ptrs[i], sizes[i], hps[i]);
+    if (rc == NET_OK) rc = build_set(hps[i], false, &img, &wins[i]);
+    CHECK(rc == NET_OK && wins[i].bytes == sizeof(gen::GenParams), "%s: rc %d", paths[i], rc);
+    if (rc != NET_OK) return;
+    flags += hps[i].xr ? '1' : '0';
+  }
+  std::vector<gen::GenParams> sets;
+  std::vector<bank::Scale> sc;
+  size_t failed = (size_t)-1;
+  const int rc = bank::build(ptrs.data(), sizes.data(), scales.data(), ns, false, sets, sc, &failed);
+  std::printf("bank %d refused %ld rc %d xr %s\n", n, rc ? (long)failed : -1L, rc, flags.c_str());
+  CHECK((rc == NET_OK) == (failed == (size_t)-1), "rc %d with failed %zu", rc, failed);
+  if (rc != NET_OK) return;
+  CHECK(sets.size() == ns && sc.size() == ns, "%zu sets, %zu scales", sets.size(), sc.size());
+  const bool mixed = flags.find('0') != std::string::npos && flags.find('1') != std::string::npos;
+  for (size_t i = 0; i < ns; i++) {
+    const gen::GenParams& g = sets[i];
+    CHECK(sc[i].qs == scales[i] && sc[i].qy == 1.0f / scales[i], "%s: scale %g, %g", paths[i], sc[i].qs, sc[i].qy);
+    if (!mixed || hps[i].xr) {
+      CHECK(std::memcmp(&g, wins[i].data.get(), sizeof(g)) == 0, "%s: not the image it gets alone", paths[i]);
+      continue;
+    }
+    // promoted: the exact-division form of a set whose float forms were all proven
+    const HostParams& hp = hps[i];
     Ranges rg;
-    if (rc == NET_OK) rc = check_ranges(hp, rg);
-    CHECK(rc == NET_OK, "%s: rc %d", paths[i], rc);
-    if (rc != NET_OK) continue;
-    ptrs.push_back(&hp);
-    const Plan was = make_plan(hp, rg);
-    Plan pl = was;
-    bank::force_exact(hp, pl);
-    flags += was.xr ? '1' : '0';
-    CHECK(pl.xr, "%s: not exact after force_exact", paths[i]);
+    CHECK(check_ranges(hp, rg) == NET_OK, "%s: ranges", paths[i]);
+    const Plan pl = make_plan(hp, rg);
+    CHECK(g.xr == 1, "%s: not exact after promotion", paths[i]);
+    CHECK(g.l3_r == 0.0f && g.l3_c == 0.0f, "%s: layer 3 keeps a float form", paths[i]);
+    CHECK(g.l3_m == pl.x3.m && g.l3_xs == pl.x3.xs && g.l5_m == pl.x5.m && g.l5_xs == pl.x5.xs,
+          "%s: lost an xdiv constant of layer 3 or 5", paths[i]);
     for (int f = 0; f < F2; f++) {
-      CHECK(pl.f1[f].r == 0.0f && pl.f1[f].c == 0.0f && pl.f2[f].r == 0.0f && pl.f2[f].mbits == 0 &&
-                pl.f4[f].r == 0.0f && pl.f4[f].mbits == 0,
+      CHECK(g.l1_r[f] == 0.0f && g.l1_c[f] == 0.0f && g.l2_r[f] == 0.0f && g.l2_c[f] == 0.0f && g.sg.l4_r[f] == 0.0f &&
+                g.sg.l4_c[f] == 0.0f,
             "%s: filter %d keeps a float form", paths[i], f);
-      CHECK(pl.ci1[f] == hp.l1_offset[f] && pl.ci2[f] == (hp.l2_offset[f] >> 3) && pl.ci4[f] == (hp.l4_offset[f] >> 3),
+      CHECK(g.l1_off[f] == hp.l1_offset[f] && g.l2_thr[f] == -(hp.l2_offset[f] >> 3) && g.sg.l4_ci[f] == 0,
             "%s: filter %d keeps a magic in its C-init", paths[i], f);
-      CHECK(pl.x1[f].m == was.x1[f].m && pl.x1[f].xs == was.x1[f].xs && pl.x2[f].m == was.x2[f].m &&
-                pl.x4[f].m == was.x4[f].m && pl.x3.m == was.x3.m && pl.x5.m == was.x5.m,
+      CHECK(g.l1_m[f] == pl.x1[f].m && g.l1_xs[f] == pl.x1[f].xs && g.l2_m[f] == pl.x2[f].m &&
+                g.l2_xs[f] == pl.x2[f].xs && g.sg.l4_m[f] == pl.x4[f].m && g.sg.l4_xs[f] == pl.x4[f].xs,
             "%s: filter %d lost an xdiv constant", paths[i], f);
     }
-    if (was.xr) CHECK(pl.xr_layer == was.xr_layer && pl.xr_filter == was.xr_filter, "%s: an exact plan changed", paths[i]);
   }
-  const long mm = (int)ptrs.size() == n ? bank::first_mismatch(ptrs.data(), ptrs.size()) : -2;
-  std::printf("bank %d mismatch %ld xr %s\n", n, mm, flags.c_str());
 }
 
 static void run_ranges() {

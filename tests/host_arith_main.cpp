@@ -1,15 +1,20 @@
 // host_arith_main.cpp — the loader's host arithmetic as a stand-alone program (tests/
-// test_host_sanitizers.py builds it with -fsanitize=address,undefined and runs it): parses the
-// blobs named on the command line and runs range check, folding and requant plan on each as
-// net_params_load does, then sweeps the requant searches over the factor classes and checks every
-// proven form against 64-bit integer division at both ends of every output step.  Prints one line
-// per blob ("set <file> rc xr layer filter folded") and exits 0 when every check held.
+// test_host_sanitizers.py builds it with -fsanitize=address,undefined and runs it): loads the blobs
+// named on the command line through the loader's own functions (parse_blob and build_set,
+// images.hpp), each normally and on the general path, and prints what net_params_info would report
+// with the FNV-1a digests of both images ("set <file> <normal|general> rc xr layer filter folded
+// kernels-image window-image").  Then the header's dimension cases on the first blob and on a
+// net_arrays_t of its arrays ("dims <cases>"), gen::carve_of over every geometry gen_supported admits
+// ("carve <cases> max <bytes>"), and the requant searches swept over the factor classes, every
+// proven form checked against 64-bit integer division at both ends of every output step.  Exits 0
+// when every check held.
 #include <cstdio>
 #include <fstream>
 #include <iterator>
 #include <string>
 #include <vector>
 
+#include "images.hpp"
 #include "params_host.hpp"
 #include "requant_host.hpp"
 
@@ -28,30 +33,93 @@ static int64_t floor_div(int64_t a, int64_t b) {
   return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q;
 }
 
-// what build_set (images.hpp) does with a parsed set, without the images
-static void run_set(const char* path) {
+static std::vector<char> read_file(const char* path) {
   std::ifstream in(path, std::ios::binary);
-  const std::vector<char> blob((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
-  HostParams hp;
-  int rc = parse_blob(blob.data(), blob.size(), hp);
-  Ranges rg;
-  if (rc == NET_OK) rc = check_ranges(hp, rg);
-  Plan pl;
-  int folded = 0;
-  if (rc == NET_OK) {
-    pl = make_plan(hp, rg);
-    if (pl.xr) {
-      HostParams fh = hp;
-      Ranges frg;
-      const int n = fold_constant_filters(fh, rg);
-      if (n > 0 && check_ranges(fh, frg) == NET_OK) {
-        pl = make_plan(fh, frg);
-        folded = n;
-      }
-    }
-    CHECK(pl.l3_ok, "%s: layer 3 has no float form", path);
+  return std::vector<char>((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+}
+
+// net_params_load on the blob, normally and under mibminet_test_force_general
+static void run_set(const char* path) {
+  const std::vector<char> blob = read_file(path);
+  for (const bool force : {false, true}) {
+    HostParams hp;
+    Image img, win;
+    int rc = parse_blob(blob.data(), blob.size(), hp);
+    if (rc == NET_OK) rc = build_set(hp, force, &img, &win);
+    const bool named = rc == NET_OK && !hp.general && hp.xr;  // net_params_info: info[1], info[2]
+    std::printf("set %s %s %d %d %d %d %d %016llx %016llx\n", path, force ? "general" : "normal", rc,
+                rc == NET_OK && hp.xr ? 1 : 0, named ? hp.xr_layer : 0, named ? hp.xr_filter : -1, hp.folded,
+                (unsigned long long)fnv1a(img), (unsigned long long)fnv1a(win));
   }
-  std::printf("set %s %d %d %d %d %d\n", path, rc, pl.xr ? 1 : 0, pl.xr ? pl.xr_layer : 0, pl.xr ? pl.xr_filter : -1, folded);
+}
+
+// A valid blob whose header claims other dimensions, and the same through a net_arrays_t: refused
+// with a code, by both parsers, before anything is sized from them.
+static void run_dims(const char* path) {
+  const std::vector<char> blob = read_file(path);
+  HostParams hp;
+  CHECK(parse_blob(blob.data(), blob.size(), hp) == NET_OK, "%s does not parse", path);
+  if (hp.l5_weight.empty()) return;
+  net_arrays_t a = {hp.d.C, hp.d.T, hp.d.F1, hp.d.F2, hp.d.D, hp.d.N,
+                    (hp.reorder_bn ? FLAG_REORDER_BN : 0) | (hp.clip_balanced ? FLAG_CLIP_BALANCED : 0),
+                    hp.l1_factor.data(), hp.l1_offset.data(), hp.l1_weight_align.data(), hp.l2_factor.data(),
+                    hp.l2_offset.data(), hp.l2_weight_reverse.data(), hp.l3_factor, hp.l3_weight.data(),
+                    hp.l4_factor.data(), hp.l4_offset.data(), hp.l4_weight.data(), hp.l5_factor, hp.l5_bias.data(),
+                    hp.l5_weight.data()};
+  HostParams out;
+  CHECK(parse_arrays(&a, out) == NET_OK, "%s: its arrays do not load", path);
+  // (F1, F2, D, the arrays' code).  The last is refused by size before the arrays are looked at
+  // (NET_ERR_UNSUPPORTED, F2 > 4096); as a blob its first array is longer than the blob.
+  const int cases[4][4] = {{hp.d.F1, -16, -1, NET_ERR_BLOB},
+                           {hp.d.F1, 0, 0, NET_ERR_BLOB},
+                           {65536, 0, 65536, NET_ERR_BLOB},
+                           {1 << 15, 1 << 30, 1 << 15, NET_ERR_UNSUPPORTED}};
+  int n = 0;
+  for (const auto& c : cases) {
+    std::vector<char> bad = blob;
+    const int32_t f1 = c[0], f2 = c[1], dd = c[2];  // header: magic, version, C, T, F1, F2, D
+    std::memcpy(&bad[8 + 4 * 3], &f1, 4);
+    std::memcpy(&bad[8 + 4 * 4], &f2, 4);
+    std::memcpy(&bad[8 + 4 * 5], &dd, 4);
+    HostParams b;
+    const int rb = parse_blob(bad.data(), bad.size(), b);
+    CHECK(rb == NET_ERR_BLOB, "blob F1 %d F2 %d D %d: rc %d", f1, f2, dd, rb);
+    net_arrays_t aa = a;
+    aa.F1 = f1; aa.F2 = f2; aa.D = dd;
+    const int ra = parse_arrays(&aa, b);
+    CHECK(ra == c[3], "arrays F1 %d F2 %d D %d: rc %d", f1, f2, dd, ra);
+    n++;
+  }
+  std::printf("dims %d\n", n);
+}
+
+// gen::carve_of over every geometry gen_supported admits and the four layouts: inside the LDS, its
+// areas in order, the staged trial (if any) behind them.  The dimensions are gen_geometry's.
+static void run_carve() {
+  static gen::GenParams g;
+  long long cases = 0;
+  int most = 0;
+  Dims d;
+  d.F1 = d.F2 = F2;
+  d.D = 1;
+  for (d.C = 1; d.C <= 64; d.C++)
+    for (d.T = 64; d.T <= gen::TMAX; d.T++) {
+      d.N = 1;
+      CHECK(gen_supported(d) == NET_OK, "C %d T %d refused", d.C, d.T);
+      gen_geometry(d, g);
+      for (int N = 1; N <= gen::NMAX; N++)
+        for (int layout = 0; layout < 4; layout++) {
+          const gen::Carve c = gen::carve_of(g.C, g.T, N, g.T8, g.T64A, g.NB1, g.MT, g.NTT, layout);
+          CHECK(c.bytes <= gen::LDS_MAX, "C %d T %d N %d layout %d: %d bytes", d.C, d.T, N, layout, c.bytes);
+          CHECK(0 < c.y2 && c.y2 < c.y3 && c.y3 < c.y4 && c.y4 < c.sg && c.sg < c.w5 && c.w5 < c.stg && c.stg <= c.bytes,
+                "C %d T %d N %d layout %d: areas out of order", d.C, d.T, N, layout);
+          CHECK(c.raw < 0 || c.raw >= c.stg, "C %d T %d N %d layout %d: raw %d before stg %d", d.C, d.T, N, layout, c.raw,
+                c.stg);
+          most = std::max(most, c.bytes);
+          cases++;
+        }
+    }
+  std::printf("carve %lld max %d\n", cases, most);
 }
 
 // both ends of every step interval of trunc(v / fac) = k (k0 <= k <= k1) inside |v| <= vmax
@@ -127,6 +195,8 @@ static int sweep() {
 
 int main(int argc, char** argv) {
   for (int i = 1; i < argc; i++) run_set(argv[i]);
+  if (argc > 1) run_dims(argv[1]);
+  run_carve();
   sweep();
   if (g_bad) std::printf("%d checks failed\n", g_bad);
   return g_bad ? 1 : 0;

@@ -102,6 +102,9 @@ def test_arrays_round_trip_and_load_like_the_blob(tmp_path, kw):
     # the blob's checks: non-zero pads and unknown flags are refused
     a.flags = 4
     assert lib.load().net_params_load_arrays(ctypes.byref(a)) == lib.NET_ERR_BLOB
+    # a negative D with the F2 = F1 D that matches it: refused before any array is sized from F2
+    a.flags, a.F2, a.D = ps.flags, -16, -1
+    assert lib.load().net_params_load_arrays(ctypes.byref(a)) == lib.NET_ERR_BLOB
     assert lib.load().net_params_load_arrays(None) == lib.NET_ERR_INVALID
     lib.params_unload()
 

@@ -1,7 +1,10 @@
 """Parameter blob (weight ABI) round trips and validation — host logic, CPU only."""
+import struct
+
 import numpy as np
 import pytest
 
+from mibminet import lib
 from mibminet.params import ParamSet, appendix_b_net, pack_trials, trial_stride_bytes, _pack_int4, _unpack_int4
 
 
@@ -77,3 +80,17 @@ def test_pack_trials_layout():
     assert p.shape == (2, trial_stride_bytes(3, 70)) and p.shape[1] % 16 == 0
     assert p[1, 5 * 3 + 2] == x[1, 2, 5]
     assert np.all(p[:, 210:] == 0)
+
+
+@pytest.mark.parametrize("F1,F2,D", [(16, -16, -1), (16, 0, 0), (65536, 0, 65536), (2 ** 15, 2 ** 30, 2 ** 15)])
+def test_header_dimensions_are_refused_with_a_code(F1, F2, D):
+    """A valid blob whose header claims a negative or zero D or F2, an F1 D past int32, or arrays far
+    longer than the blob: NET_ERR_BLOB from the library (csrc/params_host.hpp, check_dims and
+    Reader), not an exception through the C ABI or a 4 GB allocation.  The header is "MIBMINET",
+    then version, C, T, F1, F2, D as uint32."""
+    blob = bytearray(ParamSet.synthetic(seed=42).to_blob())
+    assert struct.unpack_from("<3i", blob, 20) == (16, 16, 1)
+    struct.pack_into("<3i", blob, 20, F1, F2, D)
+    with pytest.raises(lib.NetError) as e:
+        lib.params_load_blob(bytes(blob))
+    assert e.value.code == lib.NET_ERR_BLOB
