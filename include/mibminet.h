@@ -441,6 +441,83 @@ size_t net_bank_windows_starts(const size_t* lengths, size_t R, int64_t* starts)
 size_t net_bank_windows_lists(const net_bank_t* bank, const size_t* lengths, const int32_t* sets, size_t R,
                               size_t hop, int32_t* blk_set, size_t n_blk, int64_t* onsets, size_t cap, size_t* first);
 
+/* ---- live streams: chunks pushed into a layer-1 ring, windows as they end --------------------
+ * A stream group is S live sessions of one bank's geometry on one device.  Session i is decoded by
+ * its own set of the bank, and all sessions advance by the same n samples per push.  The group owns
+ * a device-resident ring of layer-1 outputs per session: a push runs layer 1 on the n new samples
+ * only and returns the logits of exactly those windows of the global grid o = j*hop (j = 0, 1, ...)
+ * whose last sample arrived in it.  Over any sequence of pushes the rows of session i, concatenated,
+ * are byte-identical to what net_model_compute_windows_bank returns for the concatenation of its
+ * chunks under its set ("Live streams").
+ * The ring holds cap = net_streams_ring_samples(bank, max_push) = 16*ceil((T + max_push)/16)
+ * samples per session, sample t at position t mod cap.  A push of n samples at position p0
+ * overwrites the positions of samples p0-cap .. p0+n-1-cap, and the windows it completes reach back
+ * to sample p0-T+1; that sample survives iff cap >= T+n-1, which holds for every n <= max_push.
+ * ALL PUSHES AND RESTARTS OF ONE GROUP MUST BE ORDERED WITH RESPECT TO ONE ANOTHER (one HIP stream,
+ * or events between streams), and none of them may run concurrently in two host threads: each reads
+ * what the one before it wrote.  A push is not capturable into a HIP graph: the position its
+ * arguments are computed from lives on the host. */
+typedef struct net_streams net_streams_t;
+
+/* Host only, no device, no group.  _ring_samples: cap as above; 0 for a NULL bank or max_push
+ * outside 1 .. 65,536.  _push_windows: the windows per session that a push of n samples at position
+ * pos returns, net_windows_count(pos + n, hop) - net_windows_count(pos, hop) for the bank's T; 0 for a
+ * NULL bank, hop == 0, or when pos + n overflows. */
+size_t net_streams_ring_samples(const net_bank_t* bank, size_t max_push);
+size_t net_streams_push_windows(const net_bank_t* bank, size_t hop, size_t pos, size_t n);
+
+/* sets: HOST array of S set indices, NULL = set 0 for every session.  Any hop >= 1 is allowed
+ * (hop > T and hop > max_push included).  Checks, NET_ERR_INVALID before any device call: a NULL
+ * bank or out, S == 0, hop == 0, max_push outside 1 .. 65,536, a sets[i] outside the bank,
+ * S*max_push > INT32_MAX - 65,535, a bad device.  Then the bank is uploaded to `device` if it is not
+ * there, and one allocation is made and zeroed: the rings (32*cap bytes per session) followed by
+ * the sessions' origins (int64) and sets (int32).  The position is 0 and every origin 0.  The bank
+ * must outlive the group.  The loaded set, net_params_info and the image cache are untouched. */
+int net_streams_create(const net_bank_t* bank, const int32_t* sets, size_t S, size_t hop, size_t max_push,
+                       int device, net_streams_t** out);
+
+/* Synchronises the group's device, then frees the group.  NULL is allowed. */
+void net_streams_destroy(net_streams_t* st);
+
+/* info[0..5] = S, hop, max_push, cap, the position (samples pushed per session so far), the windows
+ * returned per session so far. */
+int net_streams_info(const net_streams_t* st, int64_t* info);
+
+/* The host's record of session i: its origin (the position at its last restart, 0 before any) and
+ * its set.  NET_ERR_INVALID for a NULL group or pointer or i >= S. */
+int net_streams_origin(const net_streams_t* st, size_t i, int64_t* origin, int32_t* set);
+
+/* One push: n new samples of every session.  x: DEVICE pointer to the S chunks, contiguous, any byte
+ * alignment: layout 0 = [S][n][C] int8, 1 = [S][C][n] int8; the float entry [S][C][n] float32,
+ * 4-byte aligned, session i quantised with the bank's scale of its set exactly as
+ * net_quantize_input_f32 does.  With pos the position before the call and
+ * k = net_streams_push_windows(bank, hop, pos, n), y is DEVICE [S][k][N] int8, 4-byte aligned: row
+ * (i, j) is global window W0 + j, W0 = net_windows_count(pos, hop) for the bank's T, whose onset is
+ * (W0 + j)*hop.  A window is answered iff its onset >= the session's origin; otherwise no ring or
+ * parameter address is formed from it, its row is N zeros, and *n_bad (DEVICE, 4-byte aligned, or
+ * NULL; the caller zeroes it) is incremented once.  An answered row is byte-identical to what
+ * net_model_compute_batch_ct returns for that window of the session's samples with its set loaded.
+ * k == 0 enqueues layer 1 only and writes nothing to y; otherwise two kernels go on `stream`.  No
+ * host sync, no allocation.  The position advances on the host when the push is enqueued.
+ * Checks, all before anything is enqueued and before the position moves: a NULL group,
+ * NET_ERR_INVALID; n == 0, NET_OK and nothing done; then NET_ERR_INVALID for n > max_push, a layout
+ * other than 0 or 1, a NULL x, a misaligned float x, the float entry on a bank without scales, a
+ * position that would pass INT64_MAX, with k > 0 a NULL or misaligned y, a misaligned n_bad; then
+ * NET_ERR_UNSUPPORTED for a `stream` that is capturing (a replay would not advance the position the
+ * arguments were computed from).  A refused push leaves the group exactly as it was. */
+int net_streams_push(net_streams_t* st, const int8_t* x, int layout, size_t n, int8_t* y, int32_t* n_bad,
+                     void* stream);
+int net_streams_push_f32(net_streams_t* st, const float* x, size_t n, int8_t* y, int32_t* n_bad, void* stream);
+
+/* A session that reconnects, or a new user who takes the slot: from the pushes enqueued after it,
+ * session i is decoded by `set` and its origin is the current position.  Samples from before the
+ * origin are never read by an answered window (they went through layer 1 under the old set).  The
+ * window grid stays the global one, so the session's first answered window starts up to hop - 1
+ * samples after its origin.  One one-thread kernel on `stream`, its two values passed by argument:
+ * no host copy, no sync.  NET_ERR_INVALID for a NULL group, i >= S or a set outside the bank;
+ * NET_ERR_UNSUPPORTED for a capturing stream. */
+int net_streams_restart(net_streams_t* st, size_t i, int32_t set, void* stream);
+
 /* Several devices from one host thread (static split, no collectives): shard i is
  * x[i] / y[i] / B[i] on devices[i] (DEVICE pointers of that device).  Every shard is enqueued
  * before any is waited for, so the devices run concurrently.  streams == NULL: each device's null

@@ -101,6 +101,14 @@ typedef struct net_bank net_bank_t;
 int mibminet_test_bank_copy(const net_bank_t* bank, size_t set, void* buf, size_t cap, size_t* bytes);
 int mibminet_test_bank_device_copies(const net_bank_t* bank);
 
+/* Live streams (net_streams_create, include/mibminet.h): the layer-1 ring of session i, its sixteen
+ * rows of 2 * cap bytes (cap = net_streams_info's info[3]; filter f's output of sample t at bytes
+ * t mod cap and t mod cap + cap of row f), copied to the HOST buffer out of 32 * cap bytes after the
+ * group's device has been synchronised.  It tells a wrong ring from a wrong window.
+ * NET_ERR_INVALID for a NULL group or buffer or a session past the last. */
+typedef struct net_streams net_streams_t;
+int mibminet_test_streams_ring(const net_streams_t* st, size_t i, void* out);
+
 #ifdef __cplusplus
 }
 #endif

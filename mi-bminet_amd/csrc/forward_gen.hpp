@@ -206,20 +206,27 @@ __device__ __forceinline__ L1C l1_consts(const GenParams* __restrict__ gp, int l
   return L1C{L == TM ? gp->l1_b[lane] : gp->l1_bn[lane], gp->l1_off[j], gp->l1_xs[j], gp->l1_m[j], gp->l1_r[j], gp->l1_c[j]};
 }
 
-// One layer-1 block: the fragment `raw` of samples 16 blk .. +15 (l1_fetch; transposed through
-// the wave's staging area stg unless time-major) -> bytes 16 blk .. +15 of the sixteen filters'
-// rows, `row` being that of the lane's filter lane & 15 (g = lane >> 4).  last: the block holds
-// samples >= lim, which are stored as zeros.
+// The arithmetic of one layer-1 block: the fragment `raw` of 16 samples (l1_fetch; transposed
+// through the wave's staging area stg unless time-major) -> y[r], the output of filter lane & 15 at
+// sample 4 (lane >> 4) + r of the block, before the saturating pack.
+template <int L, bool XR, bool CB>
+__device__ __forceinline__ void l1_outputs(v4i raw, int8_t* stg, const L1C& k, int lane, int (&y)[4]) {
+  const v4i a = L == TM ? raw : wg::stage_block<TrK>(raw, stg, lane);
+  const v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, k.wf, (v4i){k.off, k.off, k.off, k.off}, 0, 0, 0);
+#pragma unroll
+  for (int r = 0; r < 4; r++) y[r] = rq1<XR, CB>(acc[r], k.m, k.xs, k.r, k.c);
+}
+
+// One layer-1 block: the fragment `raw` of samples 16 blk .. +15 (l1_outputs) -> bytes 16 blk ..
+// +15 of the sixteen filters' rows, `row` being that of the lane's filter lane & 15
+// (g = lane >> 4).  last: the block holds samples >= lim, which are stored as zeros.
 template <int L, bool XR, bool CB>
 __device__ __forceinline__ void l1_block(v4i raw, int8_t* stg, const L1C& k, int blk, bool last, int lim, int8_t* row,
                                          int g, int lane) {
-  const v4i a = L == TM ? raw : wg::stage_block<TrK>(raw, stg, lane);
-  const v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, k.wf, (v4i){k.off, k.off, k.off, k.off}, 0, 0, 0);
+  int y[4];
+  l1_outputs<L, XR, CB>(raw, stg, k, lane, y);
   // lane column j = filter j, rows 4 g + r = samples 16 blk + 4 g + r
   const int t0 = 16 * blk + 4 * g;
-  int y[4];
-#pragma unroll
-  for (int r = 0; r < 4; r++) y[r] = rq1<XR, CB>(acc[r], k.m, k.xs, k.r, k.c);
   if (last) {
 #pragma unroll
     for (int r = 0; r < 4; r++) y[r] = t0 + r < lim ? y[r] : 0;

@@ -1,0 +1,206 @@
+// forward_stream.hpp — live streams (gfx950): net_streams_push[_f32], include/mibminet.h.  A stream
+// group is S sessions of one bank's geometry, each decoded by its own set of the bank, all advancing
+// by the same n samples per push.  Layer 1 is pointwise in time (forward_win.hpp), so its output is
+// state that persists between calls: a push runs layer 1 on the n new samples of every session
+// (k_layer1_ring) and layers 2-5 on the windows of the global grid o = j hop whose last sample
+// arrived in it (k_forward_ring), reading each window's sixteen rows out of the session's ring.
+//
+// The ring.  Per session sixteen rows of 2 cap bytes (cap a multiple of 16, stream_host.hpp).  The
+// output of absolute sample t for filter f is stored twice, at t mod cap and t mod cap + cap, so a
+// window (T <= cap) is one contiguous run of T bytes from o mod cap, wherever the seam lies, and
+// win::copy_rows reads it as it reads a workspace: almost every window wraps (cap - T is about
+// max_push), so the seam must cost the reader nothing; the doubled stores are 32 n bytes per session
+// and push against the 16 T a window reads.  A push keeps every sample its windows read
+// (cap >= T + n - 1, stream_host.hpp).
+//
+// Per session the ring is followed, at the end of the group's one allocation, by origin[s] (int64:
+// the first sample a window of the session may read) and set[s] (int32).  k_stream_restart changes
+// both, stream-ordered; the push kernels read them with scalar loads.
+#pragma once
+#include "forward_bank.hpp"
+
+namespace mib {
+namespace stream {
+
+using bank::Range64;
+using bank::range_of;
+using bank::Scale;
+
+// Layer 1 of the new samples.  Items are (session s, 16-sample block b of its chunk), session-major
+// (item = s nb + b); wave g of gridDim.x NW1 takes the contiguous items range_of(g, gridDim.x NW1, S nb)
+// with a current set per wave, as bank::k_layer1_rec_bank does.  x: the S chunks, contiguous, in
+// layout L ([n][C] int8, [C][n] int8, [C][n] float32) at any byte alignment (float32: 4); the view is
+// one session's chunk, the row stride of the channel-major layouts n.  A set index is compared
+// unsigned before any address is formed from it; a session whose index is outside the bank stores
+// nothing.  Stores: sample 16 b + 4 g + r < n of the chunk goes to position (p0 + 16 b + 4 g + r)
+// mod cap of the lane's row and to that + cap.  Samples >= n of a partial last block are not
+// stored: their positions hold live older samples.  Where p0 is a multiple of 4 a lane's four
+// positions do not cross the seam (cap is a multiple of 4) and, when all four samples exist, leave
+// as two dwords; otherwise as bytes.
+template <int L, bool XR, bool CB>
+__global__ __launch_bounds__(win::NT1) void k_layer1_ring(const gen::GenParams* __restrict__ sets, int n_sets,
+                                                          const int* __restrict__ set_of,
+                                                          const Scale* __restrict__ scales,
+                                                          const int8_t* __restrict__ x, int8_t* __restrict__ ring,
+                                                          int items, int nb, int n, int p0, int cap) {
+  __shared__ v4i stg_v[win::NW1 * 64];  // channel-major transpose staging, 1 KB per wave
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int8_t* stg = (int8_t*)stg_v + 1024 * wave;
+  const int C = sets->C;  // every set's
+  const unsigned chunk = (L == gen::F32 ? 4u : 1u) * (unsigned)C * (unsigned)n;  // <= 2^24
+  const int g = lane >> 4;
+  const Range64 rg = range_of(blockIdx.x * win::NW1 + (unsigned)wave, gridDim.x * win::NW1, (unsigned long long)items);
+  const int end = (int)rg.hi;
+  gen::L1C k{};
+  float qs = 0.0f, qy = 0.0f;
+  int cur = -1;
+  for (int it = (int)rg.lo; it < end; it++) {  // wave-uniform
+    const int s = it / nb, b = it - s * nb;
+    const int set = set_of[s];
+    if ((unsigned)set >= (unsigned)n_sets) continue;
+    if (set != cur) {
+      cur = set;
+      k = gen::l1_consts<L>(sets + set, lane);
+      if constexpr (L == gen::F32) {
+        const Scale q = scales[set];
+        qs = q.qs;
+        qy = q.qy;
+      }
+    }
+    const gen::View v = gen::make_view(x + (size_t)s * chunk, chunk);
+    int y[4];
+    gen::l1_outputs<L, XR, CB>(gen::l1_fetch<L>(v, b, C, n, lane, qs, qy), stg, k, lane, y);
+    const unsigned w = gen::sat4(y[0], y[1], y[2], y[3]);
+    int8_t* row = ring + ((size_t)s * 16 + (size_t)(lane & 15)) * (size_t)(2 * cap);
+    const int t0 = 16 * b + 4 * g;  // the lane's first sample of the chunk
+    int q = p0 + t0;                // < 2 cap: p0 < cap, t0 < n <= cap
+    q = q >= cap ? q - cap : q;
+    if ((p0 & 3) == 0 && t0 + 3 < n) {
+      *(unsigned*)(row + q) = w;
+      *(unsigned*)(row + q + cap) = w;
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        if (t0 + r < n) {
+          const int qr = q + r >= cap ? q + r - cap : q + r;
+          const int8_t byte = (int8_t)(w >> (8 * r));
+          row[qr] = byte;
+          row[qr + cap] = byte;
+        }
+      }
+    }
+  }
+}
+
+// Where the bank loop finds item i = s k + j of a push: window j of session s, the window of the
+// global grid at onset o = first + j hop (64 bits).  open() reads origin[s] and set[s] (wave-uniform:
+// two scalar loads); the set is compared unsigned against n_sets before any address is formed from
+// it, and the item is valid iff o >= origin[s] and the set is in range.  Its rows are win::copy_rows
+// on the view of session s's ring from o mod cap, row stride 2 cap: o mod cap = (first mod cap +
+// j hop) mod cap in 32 bits with one conditional subtraction, the onsets of one push lying less than
+// n <= cap apart.  T is held or read per window as win::Rows does (HT).  gp is the current set's,
+// changed by the loop.
+template <bool HT>
+struct RingRows {
+  const int8_t* ring;
+  const long long* origin;
+  const int* set_of;
+  const gen::GenParams* gp;
+  long long first, hop;
+  int k, first_mod, cap, n_sets, T, NB1, y1s, tid;
+  int8_t* y1;
+  struct Item {
+    int session, at;  // the window's session and its first byte in the session's rows
+    bool valid;
+    int s;            // the window's set, meaningful if valid
+  };
+  __device__ __forceinline__ Item open(int i, bool more) const {
+    if (!more) return Item{0, 0, false, 0};
+    const int session = i / k, j = i - session * k;
+    const long long d = (long long)j * hop;  // < n
+    const int st = set_of[session];
+    const bool valid = first + d >= origin[session] && (unsigned)st < (unsigned)n_sets;
+    const int at = first_mod + (int)d;  // < 2 cap
+    return Item{session, at >= cap ? at - cap : at, valid, st};
+  }
+  __device__ __forceinline__ void rows(const Item& it) const {
+    const int t = HT ? T : gp->T;
+    if (it.valid)
+      win::copy_rows(win::window_view(ring + (size_t)it.session * (size_t)(32 * cap), it.at, t, 2 * cap), y1, y1s, t, NB1,
+                     2 * cap, tid, gen::NT - 64);
+  }
+};
+
+// bank::k_forward_y1_bank's loop over the W = S k windows of a push, logits [S][k][N]: the
+// contiguous ranges (session-major items: a range changes sets when it changes sessions), item
+// i - 1 finished on its own set before a switch with its two barriers, an invalid window keeps the
+// current set, the zero pads written once.  The loop is a copy, as that kernel's is of
+// bank::k_forward_ep_bank's.
+template <bool RB, bool XR, bool CB>
+__global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_forward_ring(
+    const gen::GenParams* __restrict__ sets, int n_sets, const int8_t* __restrict__ ring,
+    const long long* __restrict__ origin, const int* __restrict__ set_of, int8_t* __restrict__ out,
+    int* __restrict__ n_bad, int W, int k, long long first, long long hop, int first_mod, int cap) {
+  using namespace gen;
+  extern __shared__ v4i smem_v[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // the geometry is every set's: set 0 stands for it until the first switch
+  const Lds m = lds_of(sets, (int8_t*)smem_v, 3);
+  const int N = sets->N;
+  v4i* z = (v4i*)m.y1;  // the zero pads (gen::setup); the first switch's barriers publish them
+  for (int i = tid; i < m.cv.sg / 16; i += NT) z[i] = (v4i){0, 0, 0, 0};
+  RingRows<RB || XR> src{ring, origin, set_of, sets,      first, hop, k,  first_mod,
+                         cap,  n_sets, sets->T, sets->NB1, m.cv.y1s, tid, m.y1};
+  L2C k2;
+  const Range64 rg = range_of(blockIdx.x, gridDim.x, (unsigned long long)W);
+  const int end = (int)rg.hi;
+  int cur = -1;   // the set in registers and LDS
+  int prev = -1;  // gen::item_loop's: i valid, -2 - i invalid, -1 none
+  for (int i = (int)rg.lo;; i++) {
+    const bool more = i < end;  // uniform over the workgroup
+    const auto it = src.open(i, more);
+    const int need = it.valid ? it.s : max(cur, 0);  // an invalid window stays where the workgroup is
+    if (more && need != cur) {
+      // window i - 1 ends on its own set before any of that set's state goes
+      if (wave == NW - 1) finish_prev<RB, XR, CB, true>(src.gp, m, out, n_bad, prev, N, lane);
+      prev = -1;
+      __syncthreads();
+      cur = need;
+      src.gp = sets + cur;
+      // the reload's addresses are derived here, per switch, from an opaque copy of the thread
+      // index (bank::k_forward_ep_bank)
+      int t;
+      asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
+      set_l2c(src.gp, k2, wave, t & 63);
+      set_lds(src.gp, m, t);
+      __syncthreads();
+    }
+    const GenParams* __restrict__ gp = src.gp;
+    if (wave < NW - 1) {
+      if (more) src.rows(it);
+    } else {
+      finish_prev<RB, XR, CB, true>(gp, m, out, n_bad, prev, N, lane);
+    }
+    if (!more) break;
+    __syncthreads();  // A
+    layer2<RB, XR, CB>(gp, m.y1, m.cv.y1s, m.y2, m.cv.y2s, k2, wave, lane);
+    wg::wave_sync_lds();  // layer 3 of filter f reads only y2 row f, written by this wave
+    __builtin_amdgcn_s_setprio(wg::PRIO_L3);
+    layer3<XR, CB>(gp, m.sg, m.y2, m.cv.y2s, m.y3, wave, lane);
+    __builtin_amdgcn_s_setprio(0);
+    __syncthreads();  // B
+    prev = it.valid ? i : -2 - i;
+  }
+}
+
+// net_streams_restart: from the pushes enqueued after it session i is decoded by `set`, and no
+// window that starts before sample `pos` is answered.  One thread, its values by argument.
+__global__ void k_stream_restart(long long* __restrict__ origin, int* __restrict__ set_of, int i, long long pos, int set) {
+  origin[i] = pos;
+  set_of[i] = set;
+}
+
+}  // namespace stream
+}  // namespace mib

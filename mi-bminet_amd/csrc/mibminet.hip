@@ -11,6 +11,7 @@
 // * images.hpp: the gfx950 operand fragments and both parameter images, laid out from the plan
 //   (HIP-free);
 // * bank_host.hpp: the HIP-free part of a parameter bank, the build of its images included;
+// * stream_host.hpp: the HIP-free part of a stream group: ring size, per-push arithmetic, checks;
 // * device_state.hpp: the loaded set, the per-device image cache and the scoped launch entry;
 // * test_hooks.hpp: include/mibminet_testing.h.
 // There is no CPU compute path: without a usable HIP device every entry point returns an error.
@@ -35,11 +36,28 @@
 #include "forward_win.hpp"
 #include "forward_ep.hpp"
 #include "forward_bank.hpp"
+#include "forward_stream.hpp"
+#include "stream_host.hpp"
 #include "quantize.hpp"
 #include "classify.hpp"
 #include "device_state.hpp"
 
 using namespace mib;
+
+// A stream group (net_streams_t, include/mibminet.h): S live sessions of one bank's geometry on one
+// device.  mem is the group's one allocation (stream::alloc_of): the layer-1 rings, then the
+// sessions' origins and sets, of which origin and set are the host's mirrors.  pos and emitted
+// advance on the host when a push is enqueued.
+struct net_streams {
+  const net_bank* bank = nullptr;
+  int device = 0;
+  size_t S = 0, hop = 0, max_push = 0, cap = 0;
+  uint64_t pos = 0, emitted = 0;
+  void* mem = nullptr;
+  stream::Alloc at{};
+  std::vector<int64_t> origin;
+  std::vector<int32_t> set;
+};
 
 // test hook (mibminet_test_xdiv_gpu): xdiv against C division in 64 bits over e0 .. e0 + count - 1;
 // each thread writes its own mismatch count (plain stores, summed on the host)
@@ -419,6 +437,117 @@ int bank_windows_async(const net_bank* b, const void* x, int arg_layout, bool f3
   });
 }
 
+// ---- live streams (forward_stream.hpp, stream_host.hpp) --------------------------------------
+// A launch on a capturing stream would be replayed with the position its arguments were computed
+// from; a status that cannot be read counts as capturing.
+bool capturing(hipStream_t st) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+}
+
+int streams_create(const net_bank* b, const int32_t* sets, size_t S, size_t hop, size_t max_push, int device,
+                   net_streams** out) {
+  if (out) *out = nullptr;
+  if (const int rc = stream::check_create(b != nullptr, b ? b->sets.size() : 0, sets, S, hop, max_push, device,
+                                          out != nullptr))
+    return rc;
+  auto g = std::make_unique<net_streams>();
+  g->bank = b;
+  g->device = device;
+  g->S = S;
+  g->hop = hop;
+  g->max_push = max_push;
+  g->cap = stream::ring_samples((size_t)b->sets[0].T, max_push);
+  g->at = stream::alloc_of(S, g->cap);
+  g->origin.assign(S, 0);
+  g->set.assign(S, 0);
+  if (sets) g->set.assign(sets, sets + S);
+  DeviceScope sc(device, *b);  // uploads the bank if this device has no copy yet
+  if (sc.rc) return sc.rc;
+  hipError_t e = hipMalloc(&g->mem, g->at.bytes);
+  if (e != hipSuccess) return hip_err(e);
+  e = hipMemset(g->mem, 0, g->at.bytes);
+  if (e == hipSuccess && sets)
+    e = hipMemcpy((char*)g->mem + g->at.set, g->set.data(), 4 * S, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();  // the null stream's memset precedes every stream's push
+  if (e != hipSuccess) {
+    (void)hipFree(g->mem);
+    return hip_err(e);
+  }
+  *out = g.release();
+  return NET_OK;
+}
+
+void streams_destroy(net_streams* g) {
+  if (!g) return;
+  {
+    DeviceState& ds = g_devs[g->device];
+    std::lock_guard<std::mutex> lk(ds.mu);
+    DeviceGuard guard(g->device);
+    if (guard.err == hipSuccess) (void)hipDeviceSynchronize();  // no push still uses the rings
+    (void)hipFree(g->mem);
+  }
+  delete g;
+}
+
+// Both push entries: every check (stream::check_push, then the stream's capture status) comes before
+// the first launch and before pos moves.
+int streams_push(net_streams* g, const void* x, int arg_layout, bool f32, size_t n, int8_t* y, int32_t* n_bad,
+                 void* stream) {
+  if (!g) return NET_ERR_INVALID;
+  const net_bank& b = *g->bank;
+  const gen::GenParams& hg = b.sets[0];
+  stream::Push p;
+  if (const int rc = stream::check_push((size_t)hg.T, g->S, g->hop, g->max_push, g->cap, g->pos, x, arg_layout, f32,
+                                        !b.scales.empty(), n, y, n_bad, p))
+    return rc;
+  if (n == 0) return NET_OK;
+  DeviceScope sc(g->device, b);
+  if (sc.rc) return sc.rc;
+  const hipStream_t st = (hipStream_t)stream;
+  if (capturing(st)) return NET_ERR_UNSUPPORTED;
+  const auto* sets = (const gen::GenParams*)sc.image;
+  const auto* scales = f32 ? (const bank::Scale*)(sets + b.sets.size()) : nullptr;
+  const int n_sets = (int)b.sets.size();
+  int8_t* ring = (int8_t*)g->mem;
+  const long long* origin = (const long long*)(ring + g->at.origin);
+  const int* set_of = (const int*)(ring + g->at.set);
+  const int rc = with_layout(f32 ? (int)gen::F32 : arg_layout, [&](auto lc) {
+    return with_flags(hg, [&](auto rb, auto xr, auto cb) {
+      constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
+      // 8 workgroups of 4 waves fill a CU (launch_windows)
+      const size_t wgs = (p.l1_items + win::NW1 - 1) / win::NW1;
+      hipLaunchKernelGGL((stream::k_layer1_ring<decltype(lc)::value, XR, CB>), dim3((unsigned)capped_grid(sc.ds, wgs, 8)),
+                         dim3(win::NT1), 0, st, sets, n_sets, set_of, scales, (const int8_t*)x, ring, (int)p.l1_items,
+                         (int)p.blocks, (int)n, p.p0, (int)g->cap);
+      if (const int rc = hip_err(hipGetLastError())) return rc;
+      if (p.k == 0) return (int)NET_OK;
+      return launch_items(sc.ds, stream::k_forward_ring<RB, XR, CB>, windows_lds(hg), p.items, st, sets, n_sets,
+                          (const int8_t*)ring, origin, set_of, y, (int*)n_bad, (int)p.items, (int)p.k, p.first, p.hop,
+                          p.first_mod, (int)g->cap);
+    });
+  });
+  if (rc) return rc;
+  g->pos += n;
+  g->emitted += p.k;
+  return NET_OK;
+}
+
+int streams_restart(net_streams* g, size_t i, int32_t set, void* stream) {
+  if (!g || i >= g->S || set < 0 || (size_t)set >= g->bank->sets.size()) return NET_ERR_INVALID;
+  DeviceScope sc(g->device, *g->bank);
+  if (sc.rc) return sc.rc;
+  const hipStream_t st = (hipStream_t)stream;
+  if (capturing(st)) return NET_ERR_UNSUPPORTED;  // a replay would move the origin to a stale position
+  char* mem = (char*)g->mem;
+  hipLaunchKernelGGL(stream::k_stream_restart, dim3(1), dim3(1), 0, st, (long long*)(mem + g->at.origin),
+                     (int*)(mem + g->at.set), (int)i, (long long)g->pos, (int)set);
+  if (const int rc = hip_err(hipGetLastError())) return rc;
+  g->origin[i] = (int64_t)g->pos;
+  g->set[i] = set;
+  return NET_OK;
+}
+
 // Runs one reference-layout single-trial stage on the single-trial device.
 // stage 0 = whole model (input [T][C_ALIGN]); 1..5 = net_layerN; 6 = flip.
 int run_single(int stage, const int8_t* in, int8_t* out) {
@@ -737,6 +866,48 @@ int net_model_compute_batch(const int8_t* x, int8_t* y, size_t B, int device) { 
 
 int net_model_compute_batch_ct_sync(const int8_t* x, int8_t* y, size_t B, int device) {
   return batch_sync(x, y, B, device, 1);
+}
+
+size_t net_streams_ring_samples(const net_bank_t* bank, size_t max_push) {
+  return bank ? stream::ring_samples((size_t)bank->sets[0].T, max_push) : 0;
+}
+
+size_t net_streams_push_windows(const net_bank_t* bank, size_t hop, size_t pos, size_t n) {
+  return bank ? stream::push_windows((size_t)bank->sets[0].T, hop, (uint64_t)pos, n) : 0;
+}
+
+int net_streams_create(const net_bank_t* bank, const int32_t* sets, size_t S, size_t hop, size_t max_push, int device,
+                       net_streams_t** out) {
+  return streams_create(bank, sets, S, hop, max_push, device, out);
+}
+
+void net_streams_destroy(net_streams_t* st) { streams_destroy(st); }
+
+int net_streams_info(const net_streams_t* st, int64_t* info) {
+  if (!st || !info) return NET_ERR_INVALID;
+  info[0] = (int64_t)st->S; info[1] = (int64_t)std::min(st->hop, (size_t)INT64_MAX); info[2] = (int64_t)st->max_push;
+  info[3] = (int64_t)st->cap; info[4] = (int64_t)st->pos; info[5] = (int64_t)st->emitted;
+  return NET_OK;
+}
+
+int net_streams_origin(const net_streams_t* st, size_t i, int64_t* origin, int32_t* set) {
+  if (!st || i >= st->S || !origin || !set) return NET_ERR_INVALID;
+  *origin = st->origin[i];
+  *set = st->set[i];
+  return NET_OK;
+}
+
+int net_streams_push(net_streams_t* st, const int8_t* x, int layout, size_t n, int8_t* y, int32_t* n_bad,
+                     void* stream) {
+  return streams_push(st, x, layout, false, n, y, n_bad, stream);
+}
+
+int net_streams_push_f32(net_streams_t* st, const float* x, size_t n, int8_t* y, int32_t* n_bad, void* stream) {
+  return streams_push(st, x, 1, true, n, y, n_bad, stream);
+}
+
+int net_streams_restart(net_streams_t* st, size_t i, int32_t set, void* stream) {
+  return streams_restart(st, i, set, stream);
 }
 
 int net_model_compute_batch_multi(int ndev, const int* devices, const int8_t* const* x, int8_t* const* y,

@@ -155,4 +155,15 @@ int mibminet_test_bank_device_copies(const net_bank_t* bank) {
   return (int)bank->dev.size();
 }
 
+int mibminet_test_streams_ring(const net_streams_t* st, size_t i, void* out) {
+  if (!st || i >= st->S || !out) return NET_ERR_INVALID;
+  DeviceState& ds = g_devs[st->device];
+  std::lock_guard<std::mutex> lk(ds.mu);
+  DeviceGuard guard(st->device);
+  if (guard.err != hipSuccess) return hip_err(guard.err);
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, (const char*)st->mem + i * st->at.ring, st->at.ring, hipMemcpyDeviceToHost);
+  return hip_err(e);
+}
+
 }  // extern "C"

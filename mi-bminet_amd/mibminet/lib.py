@@ -74,6 +74,15 @@ PROTOTYPES = {
     "net_model_compute_windows_bank_f32": "int (ptr, ptr, size_t, ptr, ptr, size_t, ptr, ptr, ptr, size_t, int, ptr)",
     "net_bank_windows_starts": "size_t (ptr, size_t, ptr)",
     "net_bank_windows_lists": "size_t (ptr, ptr, ptr, size_t, size_t, ptr, size_t, ptr, size_t, ptr)",
+    "net_streams_ring_samples": "size_t (ptr, size_t)",
+    "net_streams_push_windows": "size_t (ptr, size_t, size_t, size_t)",
+    "net_streams_create": "int (ptr, ptr, size_t, size_t, size_t, int, ptr)",
+    "net_streams_destroy": "void (ptr)",
+    "net_streams_info": "int (ptr, ptr)",
+    "net_streams_origin": "int (ptr, size_t, ptr, ptr)",
+    "net_streams_push": "int (ptr, ptr, int, size_t, ptr, ptr, ptr)",
+    "net_streams_push_f32": "int (ptr, ptr, size_t, ptr, ptr, ptr)",
+    "net_streams_restart": "int (ptr, size_t, int32_t, ptr)",
     "net_model_compute_batch_multi": "int (int, ptr, ptr, ptr, ptr, ptr)",
     "net_model_compute_batch_multi_ct": "int (int, ptr, ptr, ptr, ptr, ptr)",
     "net_quantize_input_f32": "int (ptr, ptr, size_t, int, int, float, int, ptr)",
@@ -102,6 +111,7 @@ PROTOTYPES = {
     "mibminet_test_folded_filters": "int (ptr)",
     "mibminet_test_bank_copy": "int (ptr, size_t, ptr, size_t, ptr)",
     "mibminet_test_bank_device_copies": "int (ptr)",
+    "mibminet_test_streams_ring": "int (ptr, size_t, ptr)",
 }
 EXPORTED_SYMBOLS = tuple(n for n in PROTOTYPES if n.startswith("net_"))
 NET_PATH_FLOAT, NET_PATH_EXACT, NET_PATH_GENERAL = 0, 1, 2
@@ -991,6 +1001,120 @@ def forward_windows_multi_bank_torch(bank, recordings, sets, hop: int, layout: s
             out.append(forward_windows_bank_torch(bank, xc, torch.from_numpy(blk_set).to(xc.device),
                                                   torch.from_numpy(onsets), layout=layout, stream=s, check=False))
         return _stitch(net, tensors[0], out), first
+
+
+class Streams:
+    """net_streams_create: ``len(sets)`` live sessions of ``bank``'s geometry on ``device``, session i
+    decoded by set ``sets[i]`` (``sets`` an int: that many sessions under set 0), windows at every
+    ``hop``-th sample of the global grid, at most ``max_push`` samples per session and push.  The group
+    keeps a device-resident ring of layer-1 outputs per session; ``push`` runs layer 1 on the new
+    samples only and returns the windows that end in them.  All pushes and restarts of a group must
+    be ordered with respect to one another (one stream, or events).  The bank must outlive the group;
+    ``close()`` (or leaving the ``with`` block) synchronises the device and frees it."""
+
+    def __init__(self, bank, sets, hop: int, max_push: int, device: int = 0):
+        self._h = None
+        self.bank = _require_bank(bank)
+        ss = [0] * sets if isinstance(sets, int) else [int(v) for v in sets]
+        if hop < 1 or max_push < 1 or not ss:
+            raise ValueError("at least one session, hop and max_push at least 1")
+        arr = (ctypes.c_int32 * len(ss))(*ss)
+        h = ctypes.c_void_p()
+        _check(load().net_streams_create(bank.handle, arr, len(ss), hop, max_push, device, ctypes.byref(h)),
+               "net_streams_create")
+        self._h = h.value
+        self.S, self.hop, self.max_push, self.device = len(ss), hop, max_push, device
+        self.cap = self.info()[3]
+
+    @property
+    def handle(self) -> int:
+        if self._h is None:
+            raise ValueError("the stream group is closed")
+        return self._h
+
+    def info(self) -> list:
+        """net_streams_info: [S, hop, max_push, cap, position, windows returned per session so far]."""
+        arr = (ctypes.c_int64 * 6)()
+        _check(load().net_streams_info(self.handle, arr), "net_streams_info")
+        return list(arr)
+
+    def origin(self, i: int) -> tuple:
+        """net_streams_origin: (origin, set) of session ``i``."""
+        o, s = ctypes.c_int64(0), ctypes.c_int32(0)
+        _check(load().net_streams_origin(self.handle, i, ctypes.byref(o), ctypes.byref(s)), "net_streams_origin")
+        return o.value, s.value
+
+    def windows(self, n: int) -> int:
+        """net_streams_push_windows: the windows per session the next push of ``n`` samples returns."""
+        return int(load().net_streams_push_windows(self.bank.handle, self.hop, self.info()[4], n))
+
+    def _push(self, x, dtype: str, code, n: int, stream, out):
+        torch = _torch()
+        k, N = self.windows(n), self.bank.dims.N
+        s, _ = _launch(x, stream)
+        with torch.cuda.stream(s):  # the counter's zeroing precedes the launch on its stream
+            nbad = torch.zeros((1,), dtype=torch.int32, device=x.device)
+        if out is None:
+            out = torch.empty((self.S, k, N), dtype=torch.int8, device=x.device)
+        else:
+            _check_tensor(out, "out", ("int8",), (self.S, k, N))
+        name = "net_streams_push" + ("_f32" if dtype == "float32" else "")
+        _check(getattr(load(), name)(self.handle, x.data_ptr(), *code, n, out.data_ptr() if k else None, nbad.data_ptr(),
+                                     s.cuda_stream), name)
+        return out, nbad
+
+    def push(self, x, layout: str = "ct", stream=None, out=None):
+        """net_streams_push: ``x`` is a CUDA/HIP int8 tensor of every session's new samples, "ct" =
+        [S][C][n] or "tc" = [S][n][C], any byte alignment.  Returns (logits [S][k][N] int8, n_bad): row
+        (i, j) is the j-th window of the global grid that ends in this push, what forward_ct_torch
+        returns for that window of session i's samples with its set loaded; the rows of windows that
+        start before a session's origin are zero and counted in ``n_bad``, a device int32 tensor of one
+        element (no host sync here).  ``out``: an int8 device tensor [S][k][N] to write instead."""
+        code = _layout_code(layout)
+        C = self.bank.dims.C
+        _check_tensor(x, "x", ("int8",), (self.S, C, "n") if layout == "ct" else (self.S, "n", C))
+        return self._push(x, "int8", (code,), int(x.shape[2 if layout == "ct" else 1]), stream, out)
+
+    def push_f32(self, x, stream=None, out=None):
+        """net_streams_push_f32: ``x`` is a CUDA/HIP float32 tensor [S][C][n]; session i is quantised
+        with the bank's scale of its set.  Returns what push returns."""
+        if not self.bank.has_scales:
+            raise ValueError("a float32 source needs a bank created with scales")
+        _check_tensor(x, "x", ("float32",), (self.S, self.bank.dims.C, "n"))
+        return self._push(x, "float32", (), int(x.shape[2]), stream, out)
+
+    def restart(self, i: int, set: int, stream=None) -> None:
+        """net_streams_restart: from the next push session ``i`` is decoded by ``set`` and answers no
+        window that starts before the current position.  ``stream``: a torch stream (default: the
+        current one of the group's device)."""
+        torch = _torch()
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        _check(load().net_streams_restart(self.handle, i, set, s.cuda_stream), "net_streams_restart")
+
+    def close(self) -> None:
+        if self._h is not None:
+            load().net_streams_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover - interpreter shutdown
+            pass
+
+
+def streams_ring(streams, i: int) -> np.ndarray:
+    """Test hook (mibminet_test_streams_ring): the layer-1 ring of session ``i`` of a Streams group,
+    [16][2 cap] int8, read after synchronising its device."""
+    out = np.empty((16, 2 * streams.cap), np.int8)
+    _check(load().mibminet_test_streams_ring(streams.handle, i, out.ctypes.data), "mibminet_test_streams_ring")
+    return out
 
 
 def quantize_input_torch(x, scale: float, stream=None):

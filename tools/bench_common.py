@@ -1,4 +1,4 @@
-"""What bench_windows.py, bench_windows_at.py, bench_epochs.py, bench_bank.py and bench_windows_bank.py share: the alternating HIP-event
+"""What bench_windows.py, bench_windows_at.py, bench_epochs.py, bench_bank.py, bench_windows_bank.py and bench_streams.py share: the alternating HIP-event
 timing loop and its summaries, the command line, and the loop that runs the cases, writes one JSON
 line per case and turns mismatches into the exit status.  No tool of its own."""
 import argparse
@@ -40,17 +40,18 @@ def min_max(v):
     return [round(min(v), 4), round(max(v), 4)]
 
 
-def main(doc, cases, run_case, count, prefix, failures):
+def main(doc, cases, run_case, count, prefix, failures, reps=7, warmup=2):
     """The tools' command line and case loop.  ``count`` names the tool's size option ("windows",
     "epochs"); ``run_case(name, count, reps, warmup, variant)`` returns a case's result, which goes
     as one JSON line to stdout and to <out-dir>/<prefix>_<name>[_<variant>].json; the process exits
-    with 1 if ``failures(result)`` is non-zero for any case."""
+    with 1 if ``failures(result)`` is non-zero for any case.  ``reps`` and ``warmup`` are the defaults of
+    those options."""
     tool = os.path.basename(sys.argv[0])
     ap = argparse.ArgumentParser(description=doc, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--cases", default=",".join(cases))
     ap.add_argument("--" + count, type=int, default=65536)
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=reps)
+    ap.add_argument("--warmup", type=int, default=warmup)
     ap.add_argument("--variant", default="canonical", choices=("canonical", "plain_bn"),
                     help="plain_bn: a set without REORDER_BN (the plain-BN kernels); the file name then carries it")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
