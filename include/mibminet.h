@@ -455,8 +455,9 @@ size_t net_bank_windows_lists(const net_bank_t* bank, const size_t* lengths, con
  * to sample p0-T+1; that sample survives iff cap >= T+n-1, which holds for every n <= max_push.
  * ALL PUSHES AND RESTARTS OF ONE GROUP MUST BE ORDERED WITH RESPECT TO ONE ANOTHER (one HIP stream,
  * or events between streams), and none of them may run concurrently in two host threads: each reads
- * what the one before it wrote.  A push is not capturable into a HIP graph: the position its
- * arguments are computed from lives on the host. */
+ * what the one before it wrote.  A push of such a group is not capturable into a HIP graph: the
+ * position its arguments are computed from lives on the host.  Sessions that advance at their own
+ * pace, and a push that is capturable, are an each-group's (net_streams_create_each, below). */
 typedef struct net_streams net_streams_t;
 
 /* Host only, no device, no group.  _ring_samples: cap as above; 0 for a NULL bank or max_push
@@ -517,6 +518,80 @@ int net_streams_push_f32(net_streams_t* st, const float* x, size_t n, int8_t* y,
  * no host copy, no sync.  NET_ERR_INVALID for a NULL group, i >= S or a set outside the bank;
  * NET_ERR_UNSUPPORTED for a capturing stream. */
 int net_streams_restart(net_streams_t* st, size_t i, int32_t set, void* stream);
+
+/* ---- live streams, each session at its own pace ------------------------------------------------
+ * An each-group is a stream group whose sessions each have their own position pos[s], an int64 in
+ * DEVICE memory: the samples session s was given since the group was created or the session last
+ * restarted.  One push hands session s cnt_in[s] new samples, 0 <= cnt_in[s] <= n_max <= max_push
+ * (0: the session skips the tick), and session s gets the windows of ITS OWN grid o = j*hop
+ * (j = 0, 1, ..., counted in its own samples) whose last sample lies in pos[s] .. pos[s]+cnt_in[s]-1.
+ * The contract is the uniform group's, per session: over any sequence of pushes the rows session s
+ * received, concatenated, are byte-identical to what net_model_compute_windows_bank returns for the
+ * concatenation of the chunks it was given since its origin, under its set.  The ring, cap and the
+ * survival argument above are unchanged; pos[s] mod cap differs per session.
+ * The counts are a device array and the positions live on the device, so a push reads nothing from
+ * the host: the same enqueue is valid again and again, AND A PUSH IS CAPTURABLE INTO A HIP GRAPH
+ * (below).  The ordering rule is the uniform group's: all pushes, restarts and position copies of
+ * one group ordered with respect to one another, none concurrently in two host threads.
+ *
+ * _create_each: the arguments, checks, single allocation and opaque type of net_streams_create; the
+ * allocation additionally holds, after the sets, one 16-byte plan record per session (at a multiple
+ * of 16) and the positions (int64[S]), all zero.  An each-group refuses net_streams_push[_f32] with
+ * NET_ERR_INVALID, and a uniform group refuses the entries below the same way.  net_streams_destroy
+ * serves both kinds.  On an each-group net_streams_info returns S, hop, max_push, cap, THE PUSHES
+ * ENQUEUED SO FAR and -1 (info[4] counts enqueues on the host, not the replays of a captured graph),
+ * and net_streams_origin the host's record of the set and origin -1. */
+int net_streams_create_each(const net_bank_t* bank, const int32_t* sets, size_t S, size_t hop, size_t max_push,
+                            int device, net_streams_t** out);
+
+/* Host only.  kmax = ceil(n_max / hop): the most windows any session can complete in a push of at
+ * most n_max samples, the rows per session of y below.  0 for hop == 0 or n_max outside 1 .. 65,536. */
+size_t net_streams_each_rows(size_t hop, size_t n_max);
+
+/* One push.  x: DEVICE memory in fixed slots of n_max samples per session, so no address depends on
+ * a count: layout 0 = [S][n_max][C] int8, the first cnt_in[s] samples of slot s used; 1 =
+ * [S][C][n_max] int8, row stride n_max, the first cnt_in[s] samples of each row used; the float
+ * entry [S][C][n_max] float32, 4-byte aligned, session s quantised with the bank's scale of its set.
+ * Int8 x at any byte alignment.  The rest of a slot is read (it must be mapped) and ignored.
+ * cnt_in: DEVICE int32[S], 4-byte aligned.
+ * y: DEVICE [S][kmax][N] int8, 4-byte aligned, kmax = net_streams_each_rows(hop, n_max).  Rows
+ * j < cnt_out[s] of session s are written: row j is window win0[s] + j of the session's grid, byte-
+ * identical to what net_model_compute_batch_ct returns for that window of the session's samples
+ * with its set loaded.  Rows j >= cnt_out[s] are not touched.
+ * cnt_out: DEVICE int32[S], 4-byte aligned, required: the windows session s completed in this push.
+ * win0: DEVICE int64[S], 8-byte aligned, or NULL: the index on the session's grid of its row 0 (the
+ * onset is win0[s]*hop); written for every session, whatever its count.
+ * A count outside 0 .. n_max is the caller's error and harmless: it is compared unsigned before any
+ * address or loop bound is formed from it, the session stores nothing and its position does not
+ * move, cnt_out[s] = -1 and *n_bad (DEVICE, 4-byte aligned, or NULL; the caller zeroes it) is
+ * incremented once.  So is a count that would take the position past INT64_MAX - 65,536.
+ * Three kernels go on `stream`: one thread per session plans the push (validates the count, writes
+ * the session's record, cnt_out and win0, advances pos[s]), layer 1 of the new samples goes into the
+ * rings, layers 2-5 run on the completed windows; the last two read only the records.  No host sync,
+ * no allocation, no host-side state a replay would miss: THE ENTRY MAY BE CALLED ON A CAPTURING
+ * STREAM after one eager call on the device (which may pass zeros and all counts 0; it uploads the
+ * bank if create has not and asks the runtime for the kernels' occupancy).  A replay reads x and
+ * cnt_in as they then are, writes y, cnt_out, win0 and n_bad again and advances the positions again.
+ * Checks, all before anything is enqueued: a NULL group or a uniform group, NET_ERR_INVALID; then
+ * NET_ERR_INVALID for n_max outside 1 .. max_push; a layout other than 0 or 1; a NULL x, cnt_in, y
+ * or cnt_out; a misaligned y, cnt_in, cnt_out, win0, n_bad or float x; the float entry on a bank
+ * without scales.  A refused push leaves the group as it was.  A HIP error of a launch (NET_ERR_HIP
+ * and below) is no refusal: the three launches go out one after another, so if the second or third
+ * fails the plan has already run and the positions have moved past samples whose layer 1 or windows
+ * never ran.  Treat such a group as lost: destroy it, or restart every session. */
+int net_streams_push_each(net_streams_t* st, const int8_t* x, int layout, const int32_t* cnt_in, size_t n_max,
+                          int8_t* y, int32_t* cnt_out, int64_t* win0, int32_t* n_bad, void* stream);
+int net_streams_push_each_f32(net_streams_t* st, const float* x, const int32_t* cnt_in, size_t n_max, int8_t* y,
+                              int32_t* cnt_out, int64_t* win0, int32_t* n_bad, void* stream);
+
+/* A stream-ordered copy of an each-group's positions to pos_out (DEVICE int64[S], 8-byte aligned).
+ * NET_ERR_INVALID for a NULL group, a uniform group, a NULL or misaligned pos_out.
+ *
+ * net_streams_restart on an each-group: the same one-thread kernel sets pos[i] = 0 and the session's
+ * set.  A window of the new run starts at o >= 0 of the new count and reads samples o .. o+T-1 <
+ * pos[i], all written after the restart, so stale ring contents are never read and an each-group has
+ * no unanswered window.  A capturing stream is refused, as for a uniform group. */
+int net_streams_positions(net_streams_t* st, int64_t* pos_out, void* stream);
 
 /* Several devices from one host thread (static split, no collectives): shard i is
  * x[i] / y[i] / B[i] on devices[i] (DEVICE pointers of that device).  Every shard is enqueued

@@ -16,8 +16,16 @@
 // Per session the ring is followed, at the end of the group's one allocation, by origin[s] (int64:
 // the first sample a window of the session may read) and set[s] (int32).  k_stream_restart changes
 // both, stream-ordered; the push kernels read them with scalar loads.
+//
+// Each-groups (net_streams_push_each[_f32]): every session has its own position pos[s] in device
+// memory and its own count per push.  k_stream_plan turns count and position into one record per
+// session (plan_each, stream_host.hpp) and advances the position; k_layer1_ring_each and
+// k_forward_ring_each are the two kernels above with n, p0, k and the first window's ring position
+// read per session from that record, and from nothing else: the same three launches are valid on
+// every replay of a captured graph.
 #pragma once
 #include "forward_bank.hpp"
+#include "stream_host.hpp"  // EachRec, plan_each: shared with the host
 
 namespace mib {
 namespace stream {
@@ -91,6 +99,93 @@ __global__ __launch_bounds__(win::NT1) void k_layer1_ring(const gen::GenParams* 
       }
     }
   }
+}
+
+// An each-group's layer 1 (net_streams_push_each).  A SIBLING OF k_layer1_ring, kept in step with it
+// by hand: the same body with n and p0 per session, read from the session's plan record (wave-
+// uniform: one scalar load; k_stream_plan validated the record, so n <= n_max and p0 < cap).  A
+// body shared by both changed the code generated for k_layer1_ring (tools/asm_cmp.py), so it is a
+// copy.  Items are (s, b) with b < nb = ceil(n_max / 16), session-major; a wave skips the blocks
+// b >= ceil(n[s] / 16).  The view is the session's fixed slot of n_max samples, the row stride of
+// the channel-major layouts n_max; samples >= n[s] are read inside the slot and not stored.
+template <int L, bool XR, bool CB>
+__global__ __launch_bounds__(win::NT1) void k_layer1_ring_each(const gen::GenParams* __restrict__ sets, int n_sets,
+                                                               const int* __restrict__ set_of,
+                                                               const Scale* __restrict__ scales,
+                                                               const int8_t* __restrict__ x, int8_t* __restrict__ ring,
+                                                               const EachRec* __restrict__ plan, int items, int nb,
+                                                               int n_max, int cap) {
+  __shared__ v4i stg_v[win::NW1 * 64];  // channel-major transpose staging, 1 KB per wave
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int8_t* stg = (int8_t*)stg_v + 1024 * wave;
+  const int C = sets->C;  // every set's
+  const unsigned slot = (L == gen::F32 ? 4u : 1u) * (unsigned)C * (unsigned)n_max;  // <= 2^24
+  const int g = lane >> 4;
+  const Range64 rg = range_of(blockIdx.x * win::NW1 + (unsigned)wave, gridDim.x * win::NW1, (unsigned long long)items);
+  const int end = (int)rg.hi;
+  gen::L1C k{};
+  float qs = 0.0f, qy = 0.0f;
+  int cur = -1;
+  for (int it = (int)rg.lo; it < end; it++) {  // wave-uniform
+    const int s = it / nb, b = it - s * nb;
+    const EachRec rec = plan[s];
+    const int n = rec.n, p0 = rec.p0;
+    if (16 * b >= n) continue;
+    const int set = set_of[s];
+    if ((unsigned)set >= (unsigned)n_sets) continue;
+    if (set != cur) {
+      cur = set;
+      k = gen::l1_consts<L>(sets + set, lane);
+      if constexpr (L == gen::F32) {
+        const Scale q = scales[set];
+        qs = q.qs;
+        qy = q.qy;
+      }
+    }
+    const gen::View v = gen::make_view(x + (size_t)s * slot, slot);
+    int y[4];
+    gen::l1_outputs<L, XR, CB>(gen::l1_fetch<L>(v, b, C, n_max, lane, qs, qy), stg, k, lane, y);
+    const unsigned w = gen::sat4(y[0], y[1], y[2], y[3]);
+    int8_t* row = ring + ((size_t)s * 16 + (size_t)(lane & 15)) * (size_t)(2 * cap);
+    const int t0 = 16 * b + 4 * g;  // the lane's first sample of the slot
+    int q = p0 + t0;                // < 2 cap: p0 < cap, t0 < n <= cap
+    q = q >= cap ? q - cap : q;
+    if ((p0 & 3) == 0 && t0 + 3 < n) {
+      *(unsigned*)(row + q) = w;
+      *(unsigned*)(row + q + cap) = w;
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        if (t0 + r < n) {
+          const int qr = q + r >= cap ? q + r - cap : q + r;
+          const int8_t byte = (int8_t)(w >> (8 * r));
+          row[qr] = byte;
+          row[qr + cap] = byte;
+        }
+      }
+    }
+  }
+}
+
+// The first kernel of an each-group's push: one thread per session.  It reads cnt_in[s] and pos[s],
+// writes the session's record (plan_each, stream_host.hpp: the count is validated there, unsigned,
+// before anything is formed from it; the 64-bit divisions happen here, once per session and push),
+// cnt_out[s] (the windows completed, -1 for a refused count), win0[s] and *n_bad, and advances
+// pos[s].  The two kernels after it read only the records, never cnt_in or pos: the advance cannot
+// race with them, and a refused count (n = k = 0) reaches no address.
+__global__ void k_stream_plan(const int* __restrict__ cnt_in, long long* __restrict__ pos, EachRec* __restrict__ plan,
+                              int* __restrict__ cnt_out, long long* __restrict__ win0, int* __restrict__ n_bad, int S,
+                              int T, unsigned long long hop, int cap, int n_max) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+  const long long p = pos[s];
+  const EachPlan e = plan_each((unsigned)T, hop, (unsigned)cap, p, cnt_in[s], (unsigned)n_max);
+  plan[s] = e.rec;
+  cnt_out[s] = e.ok ? e.rec.k : -1;
+  if (win0) win0[s] = e.W0;
+  if (!e.ok && n_bad) atomicAdd(n_bad, 1);
+  pos[s] = p + e.rec.n;
 }
 
 // Where the bank loop finds item i = s k + j of a push: window j of session s, the window of the
@@ -195,8 +290,106 @@ __global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
   }
 }
 
+// Where the loop finds item i = s kmax + j of an each-group's push: window j of those session s
+// completes in it.  open() reads the session's record and set[s] (wave-uniform: scalar loads).  The
+// item exists iff j < k[s] (and the set is in the bank, which create and restart see to): its rows
+// start at ring position (at0 + j hop) mod cap, one conditional subtraction (at0 < cap and
+// j hop < n[s] <= cap).  An item that does not exist is no invalid window: the loop skips it and
+// nothing is written.
+template <bool HT>
+struct EachRows {
+  const int8_t* ring;
+  const EachRec* plan;
+  const int* set_of;
+  const gen::GenParams* gp;
+  int kmax, hop, cap, n_sets, T, NB1, y1s, tid;
+  int8_t* y1;
+  struct Item {
+    int session, at;
+    bool valid;  // the item exists
+    int s;       // its set, meaningful if valid
+  };
+  __device__ __forceinline__ Item open(int i, bool more) const {
+    if (!more) return Item{0, 0, false, 0};
+    const int session = i / kmax, j = i - session * kmax;
+    const EachRec r = plan[session];
+    const int st = set_of[session];
+    const bool valid = j < r.k && (unsigned)st < (unsigned)n_sets;
+    const int at = r.at0 + j * hop;  // j hop < n_max + hop <= 2^17; < 2 cap where the item exists
+    return Item{session, at >= cap ? at - cap : at, valid, st};
+  }
+  __device__ __forceinline__ void rows(const Item& it) const {
+    const int t = HT ? T : gp->T;
+    win::copy_rows(win::window_view(ring + (size_t)it.session * (size_t)(32 * cap), it.at, t, 2 * cap), y1, y1s, t, NB1,
+                   2 * cap, tid, gen::NT - 64);
+  }
+};
+
+// k_forward_ring's loop over the S kmax items of an each-group's push, logits [S][kmax][N]: row
+// s kmax + j is written iff the item exists.  A sibling, not a shared body: here an item may be
+// absent, which the loop passes over before any barrier (the records are uniform over the
+// workgroup), leaving `prev` as it is, so the last item that did exist is still finished, on its own
+// set, at the next switch or on the pass past the last item.  Every item that is not skipped is
+// valid, so prev is i or -1 and n_bad is never counted here.
+template <bool RB, bool XR, bool CB>
+__global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_forward_ring_each(
+    const gen::GenParams* __restrict__ sets, int n_sets, const int8_t* __restrict__ ring,
+    const EachRec* __restrict__ plan, const int* __restrict__ set_of, int8_t* __restrict__ out, int W, int kmax, int hop,
+    int cap) {
+  using namespace gen;
+  extern __shared__ v4i smem_v[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const Lds m = lds_of(sets, (int8_t*)smem_v, 3);
+  const int N = sets->N;
+  v4i* z = (v4i*)m.y1;  // the zero pads (gen::setup); the first switch's barriers publish them
+  for (int i = tid; i < m.cv.sg / 16; i += NT) z[i] = (v4i){0, 0, 0, 0};
+  EachRows<RB || XR> src{ring, plan, set_of, sets, kmax, hop, cap, n_sets, sets->T, sets->NB1, m.cv.y1s, tid, m.y1};
+  L2C k2;
+  const Range64 rg = range_of(blockIdx.x, gridDim.x, (unsigned long long)W);
+  const int end = (int)rg.hi;
+  int cur = -1;   // the set in registers and LDS
+  int prev = -1;  // the item whose layers 4-5 are owed, -1 none
+  for (int i = (int)rg.lo;; i++) {
+    const bool more = i < end;  // uniform over the workgroup
+    const auto it = src.open(i, more);
+    if (more && !it.valid) continue;  // uniform over the workgroup: an absent item
+    if (more && it.s != cur) {
+      // the last item ends on its own set before any of that set's state goes
+      if (wave == NW - 1) finish_prev<RB, XR, CB, true>(src.gp, m, out, nullptr, prev, N, lane);
+      prev = -1;
+      __syncthreads();
+      cur = it.s;
+      src.gp = sets + cur;
+      // the reload's addresses are derived here, per switch, from an opaque copy of the thread
+      // index (bank::k_forward_ep_bank)
+      int t;
+      asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
+      set_l2c(src.gp, k2, wave, t & 63);
+      set_lds(src.gp, m, t);
+      __syncthreads();
+    }
+    const GenParams* __restrict__ gp = src.gp;
+    if (wave < NW - 1) {
+      if (more) src.rows(it);
+    } else {
+      finish_prev<RB, XR, CB, true>(gp, m, out, nullptr, prev, N, lane);
+    }
+    if (!more) break;
+    __syncthreads();  // A
+    layer2<RB, XR, CB>(gp, m.y1, m.cv.y1s, m.y2, m.cv.y2s, k2, wave, lane);
+    wg::wave_sync_lds();  // layer 3 of filter f reads only y2 row f, written by this wave
+    __builtin_amdgcn_s_setprio(wg::PRIO_L3);
+    layer3<XR, CB>(gp, m.sg, m.y2, m.cv.y2s, m.y3, wave, lane);
+    __builtin_amdgcn_s_setprio(0);
+    __syncthreads();  // B
+    prev = i;
+  }
+}
+
 // net_streams_restart: from the pushes enqueued after it session i is decoded by `set`, and no
-// window that starts before sample `pos` is answered.  One thread, its values by argument.
+// window that starts before sample `pos` is answered.  One thread, its values by argument.  An
+// each-group passes its positions and pos = 0: the session's count starts again.
 __global__ void k_stream_restart(long long* __restrict__ origin, int* __restrict__ set_of, int i, long long pos, int set) {
   origin[i] = pos;
   set_of[i] = set;

@@ -11,7 +11,8 @@
 // * images.hpp: the gfx950 operand fragments and both parameter images, laid out from the plan
 //   (HIP-free);
 // * bank_host.hpp: the HIP-free part of a parameter bank, the build of its images included;
-// * stream_host.hpp: the HIP-free part of a stream group: ring size, per-push arithmetic, checks;
+// * stream_host.hpp: the HIP-free part of a stream group: ring size, per-push arithmetic, checks,
+//   and an each-group's per-session plan, shared with its plan kernel;
 // * device_state.hpp: the loaded set, the per-device image cache and the scoped launch entry;
 // * test_hooks.hpp: include/mibminet_testing.h.
 // There is no CPU compute path: without a usable HIP device every entry point returns an error.
@@ -47,7 +48,9 @@ using namespace mib;
 // A stream group (net_streams_t, include/mibminet.h): S live sessions of one bank's geometry on one
 // device.  mem is the group's one allocation (stream::alloc_of): the layer-1 rings, then the
 // sessions' origins and sets, of which origin and set are the host's mirrors.  pos and emitted
-// advance on the host when a push is enqueued.
+// advance on the host when a push is enqueued.  An each-group (net_streams_create_each) keeps a
+// position per session on the device behind them (stream::alloc_each); its pos counts the pushes
+// enqueued.
 struct net_streams {
   const net_bank* bank = nullptr;
   int device = 0;
@@ -55,6 +58,8 @@ struct net_streams {
   uint64_t pos = 0, emitted = 0;
   void* mem = nullptr;
   stream::Alloc at{};
+  bool each = false;
+  size_t plan_at = 0, pos_at = 0;  // an each-group's records and positions in mem
   std::vector<int64_t> origin;
   std::vector<int32_t> set;
 };
@@ -446,7 +451,7 @@ bool capturing(hipStream_t st) {
 }
 
 int streams_create(const net_bank* b, const int32_t* sets, size_t S, size_t hop, size_t max_push, int device,
-                   net_streams** out) {
+                   net_streams** out, bool each = false) {
   if (out) *out = nullptr;
   if (const int rc = stream::check_create(b != nullptr, b ? b->sets.size() : 0, sets, S, hop, max_push, device,
                                           out != nullptr))
@@ -459,14 +464,22 @@ int streams_create(const net_bank* b, const int32_t* sets, size_t S, size_t hop,
   g->max_push = max_push;
   g->cap = stream::ring_samples((size_t)b->sets[0].T, max_push);
   g->at = stream::alloc_of(S, g->cap);
-  g->origin.assign(S, 0);
+  size_t bytes = g->at.bytes;
+  if (each) {
+    const stream::AllocEach a = stream::alloc_each(S, g->cap);
+    g->each = true;
+    g->plan_at = a.plan;
+    g->pos_at = a.pos;
+    bytes = a.bytes;
+  }
+  g->origin.assign(S, each ? -1 : 0);
   g->set.assign(S, 0);
   if (sets) g->set.assign(sets, sets + S);
   DeviceScope sc(device, *b);  // uploads the bank if this device has no copy yet
   if (sc.rc) return sc.rc;
-  hipError_t e = hipMalloc(&g->mem, g->at.bytes);
+  hipError_t e = hipMalloc(&g->mem, bytes);
   if (e != hipSuccess) return hip_err(e);
-  e = hipMemset(g->mem, 0, g->at.bytes);
+  e = hipMemset(g->mem, 0, bytes);
   if (e == hipSuccess && sets)
     e = hipMemcpy((char*)g->mem + g->at.set, g->set.data(), 4 * S, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipDeviceSynchronize();  // the null stream's memset precedes every stream's push
@@ -494,7 +507,7 @@ void streams_destroy(net_streams* g) {
 // the first launch and before pos moves.
 int streams_push(net_streams* g, const void* x, int arg_layout, bool f32, size_t n, int8_t* y, int32_t* n_bad,
                  void* stream) {
-  if (!g) return NET_ERR_INVALID;
+  if (!g || g->each) return NET_ERR_INVALID;
   const net_bank& b = *g->bank;
   const gen::GenParams& hg = b.sets[0];
   stream::Push p;
@@ -540,12 +553,67 @@ int streams_restart(net_streams* g, size_t i, int32_t set, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   if (capturing(st)) return NET_ERR_UNSUPPORTED;  // a replay would move the origin to a stale position
   char* mem = (char*)g->mem;
-  hipLaunchKernelGGL(stream::k_stream_restart, dim3(1), dim3(1), 0, st, (long long*)(mem + g->at.origin),
-                     (int*)(mem + g->at.set), (int)i, (long long)g->pos, (int)set);
+  // an each-group: the session's position goes back to 0 (its origin stays -1: there is none)
+  hipLaunchKernelGGL(stream::k_stream_restart, dim3(1), dim3(1), 0, st,
+                     (long long*)(mem + (g->each ? g->pos_at : g->at.origin)), (int*)(mem + g->at.set), (int)i,
+                     g->each ? 0ll : (long long)g->pos, (int)set);
   if (const int rc = hip_err(hipGetLastError())) return rc;
-  g->origin[i] = (int64_t)g->pos;
+  if (!g->each) g->origin[i] = (int64_t)g->pos;
   g->set[i] = set;
   return NET_OK;
+}
+
+// Both push entries of an each-group: every check comes before the first launch.  A launch that
+// fails after the plan's leaves the positions advanced (include/mibminet.h says so); nothing here
+// depends on what earlier pushes did (the positions are on the device), so the three launches are
+// the same on every call with the same arguments and may be captured; pos counts the enqueues.
+int streams_push_each(net_streams* g, const void* x, int arg_layout, bool f32, const int32_t* cnt_in, size_t n_max,
+                      int8_t* y, int32_t* cnt_out, int64_t* win0, int32_t* n_bad, void* stream) {
+  if (!g || !g->each) return NET_ERR_INVALID;
+  const net_bank& b = *g->bank;
+  const gen::GenParams& hg = b.sets[0];
+  stream::PushEach p;
+  if (const int rc = stream::check_push_each(g->S, g->hop, g->max_push, x, arg_layout, f32, !b.scales.empty(), cnt_in,
+                                             n_max, y, cnt_out, win0, n_bad, p))
+    return rc;
+  DeviceScope sc(g->device, b);
+  if (sc.rc) return sc.rc;
+  const hipStream_t st = (hipStream_t)stream;
+  const auto* sets = (const gen::GenParams*)sc.image;
+  const auto* scales = f32 ? (const bank::Scale*)(sets + b.sets.size()) : nullptr;
+  const int n_sets = (int)b.sets.size();
+  int8_t* ring = (int8_t*)g->mem;
+  const int* set_of = (const int*)(ring + g->at.set);
+  auto* plan = (stream::EachRec*)(ring + g->plan_at);
+  hipLaunchKernelGGL(stream::k_stream_plan, dim3((unsigned)((g->S + 255) / 256)), dim3(256), 0, st, (const int*)cnt_in,
+                     (long long*)(ring + g->pos_at), plan, (int*)cnt_out, (long long*)win0, (int*)n_bad, (int)g->S, hg.T,
+                     (unsigned long long)g->hop, (int)g->cap, (int)n_max);
+  if (const int rc = hip_err(hipGetLastError())) return rc;
+  const int rc = with_layout(f32 ? (int)gen::F32 : arg_layout, [&](auto lc) {
+    return with_flags(hg, [&](auto rb, auto xr, auto cb) {
+      constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
+      const size_t wgs = (p.l1_items + win::NW1 - 1) / win::NW1;
+      hipLaunchKernelGGL((stream::k_layer1_ring_each<decltype(lc)::value, XR, CB>),
+                         dim3((unsigned)capped_grid(sc.ds, wgs, 8)), dim3(win::NT1), 0, st, sets, n_sets, set_of, scales,
+                         (const int8_t*)x, ring, (const stream::EachRec*)plan, (int)p.l1_items, (int)p.blocks, (int)n_max,
+                         (int)g->cap);
+      if (const int rc = hip_err(hipGetLastError())) return rc;
+      return launch_items(sc.ds, stream::k_forward_ring_each<RB, XR, CB>, windows_lds(hg), p.items, st, sets, n_sets,
+                          (const int8_t*)ring, (const stream::EachRec*)plan, set_of, y, (int)p.items, (int)p.kmax, p.hop,
+                          (int)g->cap);
+    });
+  });
+  if (rc) return rc;
+  g->pos++;
+  return NET_OK;
+}
+
+int streams_positions(net_streams* g, int64_t* pos_out, void* stream) {
+  if (!g || !g->each || !pos_out || ((uintptr_t)pos_out & 7) != 0) return NET_ERR_INVALID;
+  DeviceScope sc(g->device, *g->bank);
+  if (sc.rc) return sc.rc;
+  return hip_err(hipMemcpyAsync(pos_out, (const char*)g->mem + g->pos_at, 8 * g->S, hipMemcpyDeviceToDevice,
+                                (hipStream_t)stream));
 }
 
 // Runs one reference-layout single-trial stage on the single-trial device.
@@ -886,7 +954,7 @@ void net_streams_destroy(net_streams_t* st) { streams_destroy(st); }
 int net_streams_info(const net_streams_t* st, int64_t* info) {
   if (!st || !info) return NET_ERR_INVALID;
   info[0] = (int64_t)st->S; info[1] = (int64_t)std::min(st->hop, (size_t)INT64_MAX); info[2] = (int64_t)st->max_push;
-  info[3] = (int64_t)st->cap; info[4] = (int64_t)st->pos; info[5] = (int64_t)st->emitted;
+  info[3] = (int64_t)st->cap; info[4] = (int64_t)st->pos; info[5] = st->each ? -1 : (int64_t)st->emitted;
   return NET_OK;
 }
 
@@ -908,6 +976,27 @@ int net_streams_push_f32(net_streams_t* st, const float* x, size_t n, int8_t* y,
 
 int net_streams_restart(net_streams_t* st, size_t i, int32_t set, void* stream) {
   return streams_restart(st, i, set, stream);
+}
+
+int net_streams_create_each(const net_bank_t* bank, const int32_t* sets, size_t S, size_t hop, size_t max_push,
+                            int device, net_streams_t** out) {
+  return streams_create(bank, sets, S, hop, max_push, device, out, true);
+}
+
+size_t net_streams_each_rows(size_t hop, size_t n_max) { return stream::each_rows(hop, n_max); }
+
+int net_streams_push_each(net_streams_t* st, const int8_t* x, int layout, const int32_t* cnt_in, size_t n_max, int8_t* y,
+                          int32_t* cnt_out, int64_t* win0, int32_t* n_bad, void* stream) {
+  return streams_push_each(st, x, layout, false, cnt_in, n_max, y, cnt_out, win0, n_bad, stream);
+}
+
+int net_streams_push_each_f32(net_streams_t* st, const float* x, const int32_t* cnt_in, size_t n_max, int8_t* y,
+                              int32_t* cnt_out, int64_t* win0, int32_t* n_bad, void* stream) {
+  return streams_push_each(st, x, 1, true, cnt_in, n_max, y, cnt_out, win0, n_bad, stream);
+}
+
+int net_streams_positions(net_streams_t* st, int64_t* pos_out, void* stream) {
+  return streams_positions(st, pos_out, stream);
 }
 
 int net_model_compute_batch_multi(int ndev, const int* devices, const int8_t* const* x, int8_t* const* y,

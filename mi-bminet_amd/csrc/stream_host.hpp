@@ -1,9 +1,11 @@
 // stream_host.hpp — the HIP-free part of a stream group (net_streams_create, include/mibminet.h):
 // the size of a session's layer-1 ring, the arithmetic of one push (which windows of the global grid
 // o = j hop end in it, where they and the new samples lie in the ring, how many items the two
-// kernels take) and the argument checks of create and push.  HIP-free like entry_host.hpp, whose
-// windows_count it uses: included by mibminet.hip and a stand-alone host program
-// (tests/stream_host_main.cpp).
+// kernels take) and the argument checks of create and push; for an each-group, whose sessions have
+// a position each, the per-session plan of a push (plan_each, shared with the plan kernel of
+// forward_stream.hpp), the rows of its logits, its allocation and its checks.  HIP-free like
+// entry_host.hpp, whose windows_count it uses: included by mibminet.hip, forward_stream.hpp and two
+// stand-alone host programs (tests/stream_host_main.cpp, tests/stream_each_host_main.cpp).
 //
 // The ring.  A session's ring holds the layer-1 output of its last cap samples, sample t at position
 // t mod cap (and again at t mod cap + cap, forward_stream.hpp).  A push of n samples at position p0
@@ -16,7 +18,8 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "entry_host.hpp"  // windows_count, MAX_DEVICES
+#include "entry_host.hpp"    // windows_count, MAX_DEVICES
+#include "image_layout.hpp"  // MIB_HD
 
 namespace mib {
 namespace stream {
@@ -105,6 +108,104 @@ inline int check_push(size_t T, size_t S, size_t hop, size_t max_push, size_t ca
   g.blocks = (n + 15) / 16;
   g.l1_items = S * g.blocks;  // <= S max_push <= MAX_ITEMS
   g.items = S * k;            // k <= n
+  return NET_OK;
+}
+
+// ---- each-groups: a position per session, on the device ---------------------------------------
+// An each-group (net_streams_create_each) keeps pos[s] (int64, the samples session s was given since
+// creation or its last restart) in device memory, and a push hands session s cnt[s] <= n_max samples
+// of its own.  What the kernels need of a session and push is one record, computed by one thread of
+// k_stream_plan (forward_stream.hpp) with plan_each below; the host tests run the same function
+// (tests/stream_each_host_main.cpp), as image_layout.hpp and bank_host.hpp's range_of are shared.
+
+// the most windows a session can complete in a push of at most n_max samples: ceil(n_max / hop).
+// (The windows that end in n consecutive samples end hop apart.)  0: hop == 0 or n_max outside
+// 1 .. MAX_PUSH.
+inline size_t each_rows(size_t hop, size_t n_max) {
+  if (hop == 0 || n_max < 1 || n_max > MAX_PUSH) return 0;
+  return n_max / hop + (n_max % hop != 0);
+}
+
+// a position may not pass this: every onset and pos + n stay int64 without a check on the host
+constexpr long long EACH_POS_LIMIT = INT64_MAX - 65536;
+
+// One session's record of one push, as the layer-1 and the window kernel read it (16 bytes, one
+// scalar load): n samples go to ring positions p0, p0 + 1, ... mod cap; k windows are completed, the
+// first read from ring position at0, the next ones hop further each.
+struct EachRec {
+  int n, p0, k, at0;
+};
+struct EachPlan {
+  EachRec rec;
+  long long W0;  // the index on the session's grid of its first window of this push
+  bool ok;       // false: the count was refused (n = k = 0, nothing stored, the position stays)
+};
+
+// windows_count (entry_host.hpp) for a device caller; hop >= 1
+MIB_HD inline unsigned long long each_count(unsigned long long T, unsigned long long L, unsigned long long hop) {
+  return L < T ? 0 : (L - T) / hop + 1;
+}
+
+// The plan of a session at position pos (0 <= pos <= EACH_POS_LIMIT) that is handed cnt samples of
+// a push of at most n_max (<= max_push <= cap - T).  cnt is compared unsigned before anything is
+// formed from it; a count outside 0 .. n_max, or one that would take the position past
+// EACH_POS_LIMIT, is refused.  k <= ceil(cnt / hop) <= each_rows(hop, n_max); W0 hop + T <= pos + cnt
+// where k > 0, so the onset fits; with k == 0 at0 is 0 (unused, and W0 hop may not fit).
+MIB_HD inline EachPlan plan_each(unsigned T, unsigned long long hop, unsigned cap, long long pos, int cnt,
+                                 unsigned n_max) {
+  EachPlan e;
+  const unsigned long long p = (unsigned long long)pos;
+  e.W0 = (long long)each_count(T, p, hop);
+  e.ok = (unsigned)cnt <= n_max && pos <= EACH_POS_LIMIT - (long long)(unsigned)cnt;
+  e.rec.p0 = (int)(p % cap);
+  e.rec.n = e.ok ? cnt : 0;
+  e.rec.k = (int)(each_count(T, p + (unsigned)e.rec.n, hop) - (unsigned long long)e.W0);
+  e.rec.at0 = e.rec.k ? (int)((unsigned long long)e.W0 * hop % cap) : 0;
+  return e;
+}
+
+// bytes of an each-group's one allocation: a uniform group's (the origins stay zero and unread),
+// then the records EachRec[S] at a multiple of 16 and the positions int64[S]
+struct AllocEach {
+  Alloc base;
+  size_t plan, pos, bytes;
+};
+inline AllocEach alloc_each(size_t S, size_t cap) {
+  AllocEach a;
+  a.base = alloc_of(S, cap);
+  a.plan = (a.base.bytes + 15) / 16 * 16;
+  a.pos = a.plan + sizeof(EachRec) * S;
+  a.bytes = a.pos + 8 * S;
+  return a;
+}
+
+// What one push of an each-group hands to the kernels.
+struct PushEach {
+  size_t kmax;      // rows of y per session: each_rows(hop, n_max)
+  int hop;          // the hop as the kernel takes it (j hop < n_max + hop for every j < kmax)
+  size_t blocks;    // 16-sample blocks of a session's slot
+  size_t l1_items;  // S blocks
+  size_t items;     // S kmax
+};
+
+// The checks of net_streams_push_each[_f32] in their documented order (the group itself, NULL or
+// uniform, is the caller's first check).  kmax <= n_max <= max_push, so both item counts are at most
+// S max_push <= MAX_ITEMS (check_create).
+inline int check_push_each(size_t S, size_t hop, size_t max_push, const void* x, int layout, bool f32, bool have_scales,
+                           const void* cnt_in, size_t n_max, const void* y, const void* cnt_out, const void* win0,
+                           const void* n_bad, PushEach& g) {
+  if (n_max < 1 || n_max > max_push) return NET_ERR_INVALID;
+  if (!f32 && layout != 0 && layout != 1) return NET_ERR_INVALID;
+  if (!x || !cnt_in || !y || !cnt_out) return NET_ERR_INVALID;
+  if (((uintptr_t)y & 3) != 0 || ((uintptr_t)cnt_in & 3) != 0 || ((uintptr_t)cnt_out & 3) != 0 ||
+      ((uintptr_t)win0 & 7) != 0 || ((uintptr_t)n_bad & 3) != 0 || (f32 && ((uintptr_t)x & 3) != 0))
+    return NET_ERR_INVALID;
+  if (f32 && !have_scales) return NET_ERR_INVALID;
+  g.kmax = each_rows(hop, n_max);
+  g.hop = (int)std::min(hop, MAX_PUSH);  // hop > n_max: kmax = 1 and j hop = 0
+  g.blocks = (n_max + 15) / 16;
+  g.l1_items = S * g.blocks;
+  g.items = S * g.kmax;
   return NET_OK;
 }
 

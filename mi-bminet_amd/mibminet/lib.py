@@ -83,6 +83,11 @@ PROTOTYPES = {
     "net_streams_push": "int (ptr, ptr, int, size_t, ptr, ptr, ptr)",
     "net_streams_push_f32": "int (ptr, ptr, size_t, ptr, ptr, ptr)",
     "net_streams_restart": "int (ptr, size_t, int32_t, ptr)",
+    "net_streams_create_each": "int (ptr, ptr, size_t, size_t, size_t, int, ptr)",
+    "net_streams_each_rows": "size_t (size_t, size_t)",
+    "net_streams_push_each": "int (ptr, ptr, int, ptr, size_t, ptr, ptr, ptr, ptr, ptr)",
+    "net_streams_push_each_f32": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr, ptr, ptr)",
+    "net_streams_positions": "int (ptr, ptr, ptr)",
     "net_model_compute_batch_multi": "int (int, ptr, ptr, ptr, ptr, ptr)",
     "net_model_compute_batch_multi_ct": "int (int, ptr, ptr, ptr, ptr, ptr)",
     "net_quantize_input_f32": "int (ptr, ptr, size_t, int, int, float, int, ptr)",
@@ -1109,9 +1114,129 @@ class Streams:
             pass
 
 
+class StreamsEach:
+    """net_streams_create_each: a stream group whose sessions advance at their own pace.  Every
+    session has its own position in device memory, a push hands session i ``counts[i]`` samples
+    (0 .. n_max, 0: it skips the tick) and returns the windows of the session's own grid that end in
+    them.  A push reads nothing from the host, so after one eager push it may be captured into a
+    graph and replayed with ``x`` and ``counts`` rewritten in place.  A class of its own beside
+    Streams: its push takes and returns other things.  The ordering rule (all pushes, restarts and
+    position copies of a group ordered with respect to one another), the bank's lifetime and
+    ``close()`` are Streams'."""
+
+    def __init__(self, bank, sets, hop: int, max_push: int, device: int = 0):
+        self._h = None
+        self.bank = _require_bank(bank)
+        ss = [0] * sets if isinstance(sets, int) else [int(v) for v in sets]
+        if hop < 1 or max_push < 1 or not ss:
+            raise ValueError("at least one session, hop and max_push at least 1")
+        arr = (ctypes.c_int32 * len(ss))(*ss)
+        h = ctypes.c_void_p()
+        _check(load().net_streams_create_each(bank.handle, arr, len(ss), hop, max_push, device, ctypes.byref(h)),
+               "net_streams_create_each")
+        self._h = h.value
+        self.S, self.hop, self.max_push, self.device = len(ss), hop, max_push, device
+        self.cap = self.info()[3]
+
+    @property
+    def handle(self) -> int:
+        if self._h is None:
+            raise ValueError("the stream group is closed")
+        return self._h
+
+    def info(self) -> list:
+        """net_streams_info: [S, hop, max_push, cap, pushes enqueued so far, -1]."""
+        arr = (ctypes.c_int64 * 6)()
+        _check(load().net_streams_info(self.handle, arr), "net_streams_info")
+        return list(arr)
+
+    def origin(self, i: int) -> tuple:
+        """net_streams_origin: (-1, the set of session ``i``): an each-group keeps no origin."""
+        o, s = ctypes.c_int64(0), ctypes.c_int32(0)
+        _check(load().net_streams_origin(self.handle, i, ctypes.byref(o), ctypes.byref(s)), "net_streams_origin")
+        return o.value, s.value
+
+    def rows(self, n_max: int) -> int:
+        """net_streams_each_rows: kmax, the rows per session of a push of at most ``n_max`` samples."""
+        return int(load().net_streams_each_rows(self.hop, n_max))
+
+    def positions(self, stream=None):
+        """net_streams_positions: the sessions' positions, an int64 device tensor [S] (no host sync)."""
+        torch = _torch()
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        with torch.cuda.stream(s):
+            out = torch.empty((self.S,), dtype=torch.int64, device=f"cuda:{self.device}")
+        _check(load().net_streams_positions(self.handle, out.data_ptr(), s.cuda_stream), "net_streams_positions")
+        return out
+
+    def _push(self, x, dtype: str, code, n_max: int, counts, stream, out):
+        torch = _torch()
+        _check_tensor(counts, "counts", ("int32",), (self.S,))
+        if counts.device != x.device:
+            raise ValueError("counts must be on x's device")
+        kmax, N = self.rows(n_max), self.bank.dims.N
+        s, _ = _launch(x, stream)
+        with torch.cuda.stream(s):  # the counter's zeroing precedes the launch on its stream
+            nbad = torch.zeros((1,), dtype=torch.int32, device=x.device)
+            cnt_out = torch.empty((self.S,), dtype=torch.int32, device=x.device)
+            if out is None:
+                out = torch.empty((self.S, kmax, N), dtype=torch.int8, device=x.device)
+        _check_tensor(out, "out", ("int8",), (self.S, kmax, N))
+        name = "net_streams_push_each" + ("_f32" if dtype == "float32" else "")
+        _check(getattr(load(), name)(self.handle, x.data_ptr(), *code, counts.data_ptr(), n_max, out.data_ptr(),
+                                     cnt_out.data_ptr(), None, nbad.data_ptr(), s.cuda_stream), name)
+        return out, cnt_out, nbad
+
+    def push(self, x, counts, layout: str = "ct", stream=None, out=None):
+        """net_streams_push_each: ``x`` is a CUDA/HIP int8 tensor of fixed slots, "ct" = [S][C][n_max]
+        or "tc" = [S][n_max][C], any byte alignment; ``counts`` an int32 device tensor [S], the samples
+        of each slot that are new.  Returns (logits [S][kmax][N] int8, cnt_out [S] int32, n_bad [1]
+        int32), all device tensors, no host sync: rows j < cnt_out[i] of session i are its windows that
+        end in this push, what forward_ct_torch returns for them with its set loaded; the other rows
+        are not written.  A count outside 0 .. n_max gives cnt_out[i] = -1, moves nothing and is counted
+        in n_bad.  ``out``: an int8 device tensor [S][kmax][N] to write instead."""
+        code = _layout_code(layout)
+        C = self.bank.dims.C
+        _check_tensor(x, "x", ("int8",), (self.S, C, "n") if layout == "ct" else (self.S, "n", C))
+        return self._push(x, "int8", (code,), int(x.shape[2 if layout == "ct" else 1]), counts, stream, out)
+
+    def push_f32(self, x, counts, stream=None, out=None):
+        """net_streams_push_each_f32: ``x`` is a CUDA/HIP float32 tensor [S][C][n_max]; session i is
+        quantised with the bank's scale of its set.  Returns what push returns."""
+        if not self.bank.has_scales:
+            raise ValueError("a float32 source needs a bank created with scales")
+        _check_tensor(x, "x", ("float32",), (self.S, self.bank.dims.C, "n"))
+        return self._push(x, "float32", (), int(x.shape[2]), counts, stream, out)
+
+    def restart(self, i: int, set: int, stream=None) -> None:
+        """net_streams_restart on an each-group: session ``i`` starts again at position 0 under
+        ``set``; its grid starts at its next sample.  ``stream``: a torch stream (default: the current
+        one of the group's device)."""
+        torch = _torch()
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        _check(load().net_streams_restart(self.handle, i, set, s.cuda_stream), "net_streams_restart")
+
+    def close(self) -> None:
+        if self._h is not None:
+            load().net_streams_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover - interpreter shutdown
+            pass
+
+
 def streams_ring(streams, i: int) -> np.ndarray:
-    """Test hook (mibminet_test_streams_ring): the layer-1 ring of session ``i`` of a Streams group,
-    [16][2 cap] int8, read after synchronising its device."""
+    """Test hook (mibminet_test_streams_ring): the layer-1 ring of session ``i`` of a Streams or
+    StreamsEach group, [16][2 cap] int8, read after synchronising its device."""
     out = np.empty((16, 2 * streams.cap), np.int8)
     _check(load().mibminet_test_streams_ring(streams.handle, i, out.ctypes.data), "mibminet_test_streams_ring")
     return out

@@ -18,9 +18,32 @@ Then a, b and l alternate within every warm-up round and every timed repeat; the
 over --reps ticks are reported.  The only gate is a < b on the medians.  One JSON line per case goes
 to <out-dir>/streams_<name>.json and to stdout.  There is no CPU path.
 
-  python tools/bench_streams.py [--cases mmmi_64,bci_1024,bci_1024_shuffled] [--limit S] [--reps 1000]
-                                [--warmup 50] [--variant canonical|plain_bn] [--out-dir profiles]
+Sessions at their own pace (net_streams_push_each), in the same process and on the same sessions as
+bci_1024 (1,024 of 22 x 1125 under 16 sets, grouped, hop 8):
+  each_equal   every count 16 = n_max.  (e) net_streams_push_each against (u) net_streams_push of a
+               uniform group on the same samples: the reference is the uniform push, and e / u is
+               what the plan launch and the record loads cost.  Verified first: over six ticks every
+               row of (e) equals (u)'s.
+  each_ragged  counts drawn uniformly from 0 .. 32 = n_max (mean 16).  (e) against (b) the chunking
+               recipe, the only way to serve ragged sessions before: one net_model_compute_windows_bank
+               call on the sessions' kept samples followed by their new ones (session i from the onset
+               of its first window that ends in the tick, nothing for a session that completes none),
+               laid at multiples of 16 samples, the array and its lists prepared outside the timed
+               region, which flatters (b).  Verified first: every completed row of (e) equals (b)'s.
+In both, (e) is also captured into a graph once and replayed, (g).  Two timing rounds of their own:
+e alternating with its reference, no replay anywhere near them, gives e / reference; then e
+alternating with g gives g / e (that round's e is reported as *_beside_graph).  Per candidate two
+times are kept apart: the device's (HIP events around the call) and the host's (a clock around the
+enqueue alone, the queue drained before it).  No gate on these times: nothing here had been
+measured before.
+
+  python tools/bench_streams.py [--cases mmmi_64,bci_1024,bci_1024_shuffled,each_equal,each_ragged]
+                                [--limit S] [--reps 1000] [--warmup 50] [--variant canonical|plain_bn]
+                                [--out-dir profiles]
 """
+import statistics
+import time
+
 from bench_common import main, medians, min_max, time_alternating
 
 HOP = 8
@@ -30,9 +53,15 @@ CASES = {  # name: (sessions, sets, C, T, N, n, sets shuffled over the sessions)
     "bci_1024": (1024, 16, 22, 1125, 4, 16, False),
     "bci_1024_shuffled": (1024, 16, 22, 1125, 4, 16, True),
 }
+EACH_CASES = {  # name: (sessions, sets, C, T, N, n_max, counts drawn from 0 .. n_max): net_streams_push_each
+    "each_equal": (1024, 16, 22, 1125, 4, 16, False),
+    "each_ragged": (1024, 16, 22, 1125, 4, 32, True),
+}
 
 
 def run_case(name, limit, reps, warmup, variant, seed=2026):
+    if name in EACH_CASES:
+        return run_each(name, limit, reps, warmup, variant, seed)
     import numpy as np
     import torch
 
@@ -125,5 +154,166 @@ def run_case(name, limit, reps, warmup, variant, seed=2026):
     return res
 
 
+def host_ms(fns, reps, torch):
+    """{key: [the host's milliseconds per call]} of the candidates, enqueue only, in turn within every
+    repeat: the queue is drained before each call."""
+    out = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            out[k].append((time.perf_counter() - t0) * 1e3)
+    torch.cuda.synchronize()
+    return out
+
+
+def run_each(name, limit, reps, warmup, variant, seed=2026):
+    import numpy as np
+    import torch
+
+    from mibminet import lib
+    from mibminet.params import ParamSet
+
+    S, n_sets, C, T, N, n_max, ragged = EACH_CASES[name]
+    S = min(S, limit)
+    n_sets = min(n_sets, S)
+    sets = [ParamSet.synthetic(seed=seed + s, C=C, T=T, N=N, reorder_bn=variant != "plain_bn") for s in range(n_sets)]
+    bank = lib.Bank(sets)
+    set_of = [int(v) for v in np.sort(np.arange(S) * n_sets // S)]
+    each = lib.StreamsEach(bank, set_of, HOP, n_max)
+    uni = None if ragged else lib.Streams(bank, set_of, HOP, n_max)
+    kmax = each.rows(n_max)
+    rng = np.random.default_rng(seed)
+    lead = T % HOP
+    # ticks until every session has its first window: at the mean count n_max / 2, plus the spread
+    fill = -(-(T - lead) // (n_max // 2)) + 30 if ragged else -(-(T - lead) // n_max) + 2
+    ticks = fill + VERIFY
+    total = lead + ticks * n_max
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    x = torch.randint(-128, 128, (S, C, total), dtype=torch.int8, device="cuda", generator=g)
+    xh = x.cpu().numpy()
+    A = lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    xs = torch.zeros((S, C, n_max), dtype=torch.int8, device="cuda")
+    cin = torch.zeros((S,), dtype=torch.int32, device="cuda")
+    cout = torch.zeros((S,), dtype=torch.int32, device="cuda")
+    ye = torch.zeros((S, kmax, N), dtype=torch.int8, device="cuda")
+    yu = torch.zeros((S, n_max // HOP, N), dtype=torch.int8, device="cuda")
+    nbad = torch.zeros((1,), dtype=torch.int32, device="cuda")
+
+    def e():
+        rc = A.net_streams_push_each(each.handle, xs.data_ptr(), 1, cin.data_ptr(), n_max, ye.data_ptr(), cout.data_ptr(), None,
+                                     nbad.data_ptr(), stream)
+        assert rc == 0, rc
+
+    def u():
+        rc = A.net_streams_push(uni.handle, xs.data_ptr(), 1, n_max, yu.data_ptr(), nbad.data_ptr(), stream)
+        assert rc == 0, rc
+
+    # fill the rings (every session at its own pace in the ragged case), then VERIFY ticks against the reference
+    pos = np.zeros(S, np.int64)
+    mis = rows_checked = 0
+    recipe = None
+    for t in range(ticks):
+        first_tick = t == 0 and lead > 0
+        m = lead if first_tick else n_max
+        if ragged and t > 0:
+            cnt = rng.integers(0, n_max + 1, size=S).astype(np.int32)
+        else:
+            cnt = np.full(S, m, np.int32)
+        slot = np.zeros((S, C, n_max), np.int8)
+        for s in range(S):
+            slot[s, :, : cnt[s]] = xh[s, :, pos[s]: pos[s] + cnt[s]]
+        xs.copy_(torch.from_numpy(slot))
+        cin.copy_(torch.from_numpy(cnt))
+        e()
+        if uni is not None:
+            if first_tick:
+                uni.push(x[:, :, :lead].contiguous())
+            else:
+                u()
+        new = pos + cnt
+        if t >= fill:
+            torch.cuda.synchronize()
+            k = np.array([lib.load().net_streams_push_windows(bank.handle, HOP, int(p), int(c)) for p, c in zip(pos, cnt)])
+            assert cout.cpu().tolist() == k.tolist()
+            if uni is not None:
+                assert (k == n_max // HOP).all()
+                mis += int((ye[:, : n_max // HOP] != yu).any(dim=2).sum().item())
+                rows_checked += int(k.sum())
+            else:
+                # the recipe: session s from the onset of its first completed window to its last new sample
+                W0 = np.where(pos >= T, (pos - T) // HOP + 1, 0)
+                lens = np.where(k > 0, new - W0 * HOP, 0)
+                starts, Lx, blk_set, onsets, first = lib.bank_windows_lists(bank, lens.tolist(), set_of, HOP)
+                assert (np.diff(first) == k).all() and Lx * max(16, C) < 2**31
+                xb = np.zeros((C, Lx), np.int8)
+                for s in np.flatnonzero(k > 0):
+                    xb[:, starts[s]: starts[s] + lens[s]] = xh[s, :, W0[s] * HOP: new[s]]
+                wsb = lib.windows_workspace(Lx)
+                recipe = (torch.from_numpy(xb).cuda(), Lx, torch.from_numpy(blk_set).cuda(), torch.from_numpy(onsets).cuda(),
+                          int(first[-1]), torch.empty((wsb,), dtype=torch.int8, device="cuda"), wsb,
+                          torch.empty((int(first[-1]), N), dtype=torch.int8, device="cuda"))
+                b_call(A, bank, recipe, nbad, stream)
+                torch.cuda.synchronize()
+                yb, yeh = recipe[7].cpu().numpy(), ye.cpu().numpy()
+                for s in np.flatnonzero(k > 0):
+                    mis += int((yeh[s, : k[s]] != yb[first[s]: first[s + 1]]).any(axis=1).sum())
+                rows_checked += int(k.sum())
+        pos = new
+    assert int(nbad.item()) == 0
+
+    # (g): the same enqueue captured once; its replays advance the positions as eager calls do
+    graph = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(graph, stream=side):
+            rc = A.net_streams_push_each(each.handle, xs.data_ptr(), 1, cin.data_ptr(), n_max, ye.data_ptr(), cout.data_ptr(),
+                                         None, nbad.data_ptr(), side.cuda_stream)
+            assert rc == 0, rc
+    # two rounds, so that a replay never sits between the eager call and its reference: e against the
+    # reference, then e against g (its e is reported as device_ms_push_each_beside_graph)
+    ref = "u" if uni is not None else "b"
+    ref_fn = u if uni is not None else lambda: b_call(A, bank, recipe, nbad, stream)
+    ms = time_alternating({"e": e, ref: ref_fn}, reps, warmup)
+    ms.update(time_alternating({"e2": e, "g": graph.replay}, reps, warmup))
+    med = medians(ms)
+    host = host_ms({"e": e, ref: ref_fn}, reps, torch)
+    host.update(host_ms({"e2": e, "g": graph.replay}, reps, torch))
+    info = bank.info()
+    res = {"name": name, "sessions": S, "sets": n_sets, "C": C, "T": T, "N": N, "hop": HOP, "n_max": n_max,
+           "counts": "uniform 0 .. n_max" if ragged else "all n_max", "mean_count": round(float(cnt.mean()), 2),
+           "rows_per_session": kmax, "windows_last_tick": int(k.sum()), "variant": variant, "exact_division": bool(info[4]),
+           "verified_ticks": VERIFY, "rows_verified": rows_checked, "mismatched_rows": mis, "reps": reps, "warmup": warmup,
+           "reference": "net_streams_push (uniform group)" if uni is not None else "chunking recipe, net_model_compute_windows_bank",
+           "device": torch.cuda.get_device_name(0),
+           "device_ms_push_each": round(med["e"], 4), "device_ms_reference": round(med[ref], 4),
+           "device_ms_push_each_beside_graph": round(med["e2"], 4), "device_ms_push_each_graph": round(med["g"], 4),
+           "host_ms_push_each": round(statistics.median(host["e"]), 4),
+           "host_ms_push_each_beside_graph": round(statistics.median(host["e2"]), 4),
+           "host_ms_push_each_graph": round(statistics.median(host["g"]), 4),
+           "host_ms_reference": round(statistics.median(host[ref]), 4),
+           "device_ms_push_each_min_max": min_max(ms["e"]), "device_ms_push_each_graph_min_max": min_max(ms["g"]),
+           "device_ms_reference_min_max": min_max(ms[ref]),
+           "push_each_over_reference": round(med["e"] / med[ref], 4), "graph_over_eager": round(med["g"] / med["e2"], 4),
+           "pass": mis == 0 and rows_checked > 0}
+    del graph
+    each.close()
+    if uni is not None:
+        uni.close()
+    bank.close()
+    return res
+
+
+def b_call(A, bank, recipe, nbad, stream):
+    xb, Lx, bsd, ond, W, ws, wsb, yb = recipe
+    rc = A.net_model_compute_windows_bank(bank.handle, xb.data_ptr(), 1, Lx, bsd.data_ptr(), ond.data_ptr(), W, yb.data_ptr(),
+                                          nbad.data_ptr(), ws.data_ptr(), wsb, 0, stream)
+    assert rc == 0, rc
+
+
+
 if __name__ == "__main__":
-    main(__doc__, CASES, run_case, "limit", "streams", lambda res: res["mismatched_rows"], reps=1000, warmup=50)
+    main(__doc__, {**CASES, **EACH_CASES}, run_case, "limit", "streams", lambda res: res["mismatched_rows"], reps=1000, warmup=50)
