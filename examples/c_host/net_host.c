@@ -16,6 +16,12 @@
  *   net_host bench <params.blob> [B=65536] [steps=50]
  *       Times `steps` back-to-back net_model_compute_batch_async launches over B resident
  *       random trials with HIP events and prints one line of trials/s.
+ *   net_host widen <params.blob> [R=64] [n=16]
+ *       A wider montage: widens the set to R source rows with net_blob_widen (channel c reads row
+ *       (37 c + 5) mod R, which needs an R that 37 does not divide into repeats: any power of two),
+ *       runs n random trials u[R][T] through the widened set and the gathered rows u[channels]
+ *       through the original one (net_model_compute_batch_ct both times), and compares the logits.
+ *       Exit 0 when every trial matches.
  *
  * Built with -DMIB_NET_H against a generated net.h / net.c (the reference's weight globals,
  * gen_net_header.py; net_host_b22 / net_host_g19 in the Makefile), <params.blob> may be "-": the
@@ -209,13 +215,87 @@ static int bench(const char* blob, long B, int steps) {
     return 0;
 }
 
+/* logits of n channel-major trials [n][C][T] (host) under the blob: load, upload, run, download */
+static int run_ct(const void* blob, size_t len, const int8_t* x, long n, int8_t* y) {
+    int rc = net_params_load(blob, len);
+    if (rc) {
+        fprintf(stderr, "net_params_load: %s\n", net_error_string(rc));
+        return 1;
+    }
+    int32_t d[7];
+    net_params_dims(d);
+    const size_t xb = (size_t)n * d[0] * d[1], yb = (size_t)n * d[4];
+    int8_t *dx = NULL, *dy = NULL;
+    HIP_OK(hipMalloc((void**)&dx, xb));
+    HIP_OK(hipMalloc((void**)&dy, yb));
+    HIP_OK(hipMemcpy(dx, x, xb, hipMemcpyHostToDevice));
+    rc = net_model_compute_batch_ct(dx, dy, (size_t)n, 0, NULL);
+    if (rc) {
+        fprintf(stderr, "net_model_compute_batch_ct: %s\n", net_error_string(rc));
+        return 1;
+    }
+    HIP_OK(hipMemcpy(y, dy, yb, hipMemcpyDeviceToHost));  /* null stream: after the launch */
+    hipFree(dx);
+    hipFree(dy);
+    return 0;
+}
+
+static int widen(const char* path, int R, long n) {
+    size_t len = 0, wlen = 0;
+    void* blob = read_file(path, &len);
+    if (!blob) return 1;
+    int32_t d[7];
+    int rc = net_params_load(blob, len);
+    if (rc || n < 1) {
+        fprintf(stderr, "net_params_load: %s\n", net_error_string(rc));
+        return 1;
+    }
+    net_params_dims(d);
+    const int C = d[0], T = d[1], N = d[4];
+    int32_t ch[64];
+    for (int c = 0; c < C && c < 64; c++) ch[c] = (37 * c + 5) % (R > 0 ? R : 1);
+    /* the size first, then the blob; a bad R or a repeated row is refused here */
+    rc = net_blob_widen(blob, len, R, ch, NULL, 0, &wlen);
+    void* wide = rc ? NULL : malloc(wlen);
+    if (!rc) rc = net_blob_widen(blob, len, R, ch, wide, wlen, &wlen);
+    if (rc) {
+        fprintf(stderr, "net_blob_widen: %s\n", net_error_string(rc));
+        return 1;
+    }
+    int8_t* u = malloc((size_t)n * R * T);       /* what the cap delivers: every electrode */
+    int8_t* g = malloc((size_t)n * C * T);       /* the gathered rows, as a caller built them before */
+    int8_t* yw = malloc((size_t)n * N);
+    int8_t* yg = malloc((size_t)n * N);
+    uint32_t s = 2026u;
+    for (size_t i = 0; i < (size_t)n * R * T; i++) {
+        s = s * 1664525u + 1013904223u;
+        u[i] = (int8_t)(s >> 24);
+    }
+    for (long b = 0; b < n; b++)
+        for (int c = 0; c < C; c++) memcpy(g + ((size_t)b * C + c) * T, u + ((size_t)b * R + ch[c]) * T, (size_t)T);
+    if (run_ct(blob, len, g, n, yg) || run_ct(wide, wlen, u, n, yw)) return 1;
+    int32_t info[5];
+    net_params_info(info);
+    long bad = 0;
+    for (long b = 0; b < n; b++) bad += memcmp(yw + (size_t)b * N, yg + (size_t)b * N, (size_t)N) != 0;
+    printf("widened %d -> %d rows (%zu -> %zu bytes, path %d): %ld of %ld trials differ from the gathered input\n", C, R,
+           len, wlen, info[0], bad, n);
+    free(u); free(g); free(yw); free(yg); free(wide); free(blob);
+    if (bad) return 1;
+    printf("ok\n");
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 3 && !strcmp(argv[1], "widen"))
+        return widen(argv[2], argc > 3 ? atoi(argv[3]) : 64, argc > 4 ? atol(argv[4]) : 16);
     if (argc >= 6 && !strcmp(argv[1], "check")) return check(argv[2], argv[3], argv[4], atol(argv[5]));
     if (argc >= 3 && !strcmp(argv[1], "bench"))
         return bench(argv[2], argc > 3 ? atol(argv[3]) : 65536, argc > 4 ? atoi(argv[4]) : 50);
     fprintf(stderr,
             "usage: %s check <params.blob> <x.bin> <want.bin> <n>\n"
-            "       %s bench <params.blob> [B] [steps]\n",
-            argv[0], argv[0]);
+            "       %s bench <params.blob> [B] [steps]\n"
+            "       %s widen <params.blob> [R] [n]\n",
+            argv[0], argv[0], argv[0]);
     return 2;
 }

@@ -123,6 +123,29 @@ int net_params_load(const void* blob, size_t len);
 #define NET_PATH_GENERAL 2
 int net_params_info(int32_t* info);
 
+/* Host only: the blob over R source rows, for input that carries every electrode of the cap.  The
+ * output is the input blob with C := R and l1_weight_align as [F2][R_ALIGN]: column channels[c] of
+ * the new array is column c of the old one, every other column is zero (int8 and packed int4
+ * alike); every other field is byte-identical.  channels: HOST, the blob's C entries.  Layer 1 is a
+ * dense contraction over its channel slots whatever C is, so for every int8 input u[R][T] the
+ * widened set gives on u, at every layer, what the original gives on u[channels]: the same int32
+ * accumulators, zeros adding nothing.  The reachable ranges are therefore the same: the widened
+ * blob loads iff the original does, with the same code, and takes the same requant path
+ * (net_params_info's info[4], exact division or not).  A compiled geometry (22 x 1125, 64 x 1000,
+ * 64 x 480) becomes a general-path one once R != C; 64 -> 64 with a permutation stays compiled.
+ * Sets of different C widened to one R agree on C for net_bank_create (T, N and the variant still
+ * have to), so subjects with different electrode selections share one bank and one stream group;
+ * net_bank_info then reports R as C.  Widen once at set-up, then feed the [n][R] frames to the
+ * _f32_tm entries ("Frames as the amplifier delivers them").
+ * out: HOST, cap bytes, not overlapping the blob; *out_len (if non-NULL) is set to the size the
+ * output needs whenever the arguments pass; out == NULL asks for the size only.  Returns
+ * NET_ERR_BLOB as net_params_load's parser returns it (first); then NET_ERR_INVALID for R outside
+ * 1 .. 64, a NULL channels, an entry outside 0 .. R-1 or a duplicate entry (two columns would add,
+ * and the sum may leave int8); then NET_ERR_INVALID for a cap too small, *out_len set.  Whether the
+ * kernels take the set is net_params_load's business, here as for any blob. */
+int net_blob_widen(const void* blob, size_t len, int R, const int32_t* channels, void* out, size_t cap,
+                   size_t* out_len);
+
 /* The reference's generated globals (edge-eegnet_wolf/data/gen_net_header.py:78-224, written by
  * python_utils/header_file.py as src/cl/net/net.{h,c}), by pointer, in their own layouts: a C host
  * that links the reference's net.c loads them with net_params_load_arrays and needs no blob file
@@ -249,6 +272,16 @@ int net_model_compute_windows(const int8_t* x, int layout, size_t L, size_t hop,
 int net_model_compute_windows_f32(const float* x, size_t L, size_t hop, float scale, int8_t* y, void* ws,
                                   size_t ws_bytes, int device, void* stream);
 
+/* The same for a float32 time-major recording [L][C] (sample-major frames, element (t, c) at float
+ * index t*C + c; 4-byte aligned): the arguments, checks, check order, return codes and capture rules
+ * of net_model_compute_windows_f32, only the shape of x differs.  This is the contract of every
+ * _f32_tm entry below, each against its _f32 sibling: y, and where there is one the workspace or the
+ * rings, are byte-identical to what the sibling writes for the transposed array, and therefore to
+ * what the int8 time-major entry (layout 0) writes for net_quantize_input_f32's quantisation of the
+ * same samples.  No transpose pass and no staging: a lane reads 64 contiguous bytes of one frame. */
+int net_model_compute_windows_f32_tm(const float* x, size_t L, size_t hop, float scale, int8_t* y, void* ws,
+                                     size_t ws_bytes, int device, void* stream);
+
 /* ---- windows at given onsets: dense irregular windows, many recordings in one call -----------
  * The same two kernels with the window starts read from a device list: window i covers samples
  * onsets[i] .. onsets[i] + T - 1 of the recording and is valid iff 0 <= onsets[i] <= L - T.
@@ -256,8 +289,9 @@ int net_model_compute_windows_f32(const float* x, size_t L, size_t hop, float sc
  * irregular hops, and the sliding windows of several recordings laid end to end along time (no
  * window crossing a boundary: net_windows_multi_onsets) share it exactly as the regular windows
  * do: ws[f][t] does not depend on which recording sample t belongs to.  Prefer
- * net_model_compute_epochs for sparse onsets (W*T << L: layer 1 here covers all L samples), channel
- * subsets and strided sources ("Windows at given onsets").
+ * net_model_compute_epochs for sparse onsets (W*T << L: layer 1 here covers all L samples) and
+ * strided sources ("Windows at given onsets"); a channel subset of up to 64 source
+ * rows is served here by a set widened over those rows (net_blob_widen).
  * x, layout, L, ws, ws_bytes, scale, device and stream are those of net_model_compute_windows
  * [_f32], and ws holds the same after the call.  onsets (W int64, 8-byte aligned, duplicates and
  * any order allowed), y ([W][N] int8, 4-byte aligned) and n_bad (one int32, 4-byte aligned, or
@@ -277,6 +311,10 @@ int net_model_compute_windows_at(const int8_t* x, int layout, size_t L, const in
                                  int8_t* y, int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream);
 int net_model_compute_windows_at_f32(const float* x, size_t L, const int64_t* onsets, size_t W, float scale,
                                      int8_t* y, int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream);
+/* net_model_compute_windows_at_f32 on a float32 time-major recording [L][C]
+ * (net_model_compute_windows_f32_tm). */
+int net_model_compute_windows_at_f32_tm(const float* x, size_t L, const int64_t* onsets, size_t W, float scale,
+                                        int8_t* y, int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream);
 
 /* Host only: the onset list of the sliding windows of R recordings laid end to end along time.
  * Recording r has lengths[r] samples and starts at sample s_r = lengths[0] + .. + lengths[r - 1];
@@ -348,7 +386,8 @@ typedef struct net_bank net_bank_t;
 int net_bank_create(const void* const* blobs, const size_t* sizes, const float* scales, size_t n_sets,
                     net_bank_t** bank, size_t* failed);
 
-/* info[0..6] = n_sets, C, T, N, exact_division (0/1), has_scales (0/1), bytes per set on the device. */
+/* info[0..6] = n_sets, C, T, N, exact_division (0/1), has_scales (0/1), bytes per set on the device.
+ * C is the sets' as loaded: for sets widened by net_blob_widen it is R, the source rows. */
 int net_bank_info(const net_bank_t* bank, int32_t* info);
 
 /* Synchronises every device that holds a copy of the bank, frees the copies and the bank.  NULL is
@@ -427,6 +466,11 @@ int net_model_compute_windows_bank(const net_bank_t* bank, const int8_t* x, int 
 int net_model_compute_windows_bank_f32(const net_bank_t* bank, const float* x, size_t L,
                                        const int32_t* blk_set, const int64_t* onsets, size_t W, int8_t* y,
                                        int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream);
+/* net_model_compute_windows_bank_f32 on a float32 time-major array [L][C]
+ * (net_model_compute_windows_f32_tm): block b's samples are quantised with blk_set[b]'s scale. */
+int net_model_compute_windows_bank_f32_tm(const net_bank_t* bank, const float* x, size_t L,
+                                          const int32_t* blk_set, const int64_t* onsets, size_t W, int8_t* y,
+                                          int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream);
 
 /* Host only: the layout above.  starts[0..R-1] (HOST, may be NULL); returns L, 0 on overflow of
  * int64 or R == 0. */
@@ -509,6 +553,9 @@ int net_streams_origin(const net_streams_t* st, size_t i, int64_t* origin, int32
 int net_streams_push(net_streams_t* st, const int8_t* x, int layout, size_t n, int8_t* y, int32_t* n_bad,
                      void* stream);
 int net_streams_push_f32(net_streams_t* st, const float* x, size_t n, int8_t* y, int32_t* n_bad, void* stream);
+/* net_streams_push_f32 on [S][n][C] float32 chunks, frames as an amplifier delivers them
+ * (net_model_compute_windows_f32_tm): the same rings and rows, no transpose before the push. */
+int net_streams_push_f32_tm(net_streams_t* st, const float* x, size_t n, int8_t* y, int32_t* n_bad, void* stream);
 
 /* A session that reconnects, or a new user who takes the slot: from the pushes enqueued after it,
  * session i is decoded by `set` and its origin is the current position.  Samples from before the
@@ -583,6 +630,10 @@ int net_streams_push_each(net_streams_t* st, const int8_t* x, int layout, const 
                           int8_t* y, int32_t* cnt_out, int64_t* win0, int32_t* n_bad, void* stream);
 int net_streams_push_each_f32(net_streams_t* st, const float* x, const int32_t* cnt_in, size_t n_max, int8_t* y,
                               int32_t* cnt_out, int64_t* win0, int32_t* n_bad, void* stream);
+/* net_streams_push_each_f32 on [S][n_max][C] float32 fixed slots, the first cnt_in[s] frames of slot
+ * s used (net_model_compute_windows_f32_tm).  Capturable into a HIP graph as its sibling is. */
+int net_streams_push_each_f32_tm(net_streams_t* st, const float* x, const int32_t* cnt_in, size_t n_max, int8_t* y,
+                                 int32_t* cnt_out, int64_t* win0, int32_t* n_bad, void* stream);
 
 /* A stream-ordered copy of an each-group's positions to pos_out (DEVICE int64[S], 8-byte aligned).
  * NET_ERR_INVALID for a NULL group, a uniform group, a NULL or misaligned pos_out.

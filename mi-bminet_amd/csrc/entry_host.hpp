@@ -18,7 +18,15 @@ namespace mib {
 constexpr int MAX_DEVICES = 64;
 
 namespace gen {
-enum Layout { TM = 0, CT = 1, F32 = 2 };
+// TM [t][c] int8, CT [c][t] int8, F32 [c][t] float32, F32TM [t][c] float32 (element (t, c) at float
+// index t C + c: frames as an amplifier delivers them).  3 is the carve's "no staging" code
+// (image_layout.hpp, carve_of), no layout.
+enum Layout { TM = 0, CT = 1, F32 = 2, F32TM = 4 };
+constexpr bool is_float(int layout) { return layout == F32 || layout == F32TM; }
+constexpr bool is_time_major(int layout) { return layout == TM || layout == F32TM; }
+constexpr unsigned elem_bytes(int layout) { return is_float(layout) ? 4u : 1u; }
+// the layout of a float32 entry: channel-major unless its caller names F32TM
+constexpr int float_layout(int arg_layout) { return arg_layout == F32TM ? (int)F32TM : (int)F32; }
 }  // namespace gen
 
 namespace ep {
@@ -82,7 +90,8 @@ inline size_t windows_multi(size_t T, const size_t* lengths, size_t R, size_t ho
 
 // The argument checks the windows entries share (the loaded set's and a bank's), in their
 // documented order, for a network of C channels and T samples.  arg_layout: the int8 entries' layout
-// argument (0 time-major, 1 channel-major); f32: a float32 entry (channel-major).  at: false, the
+// argument (0 time-major, 1 channel-major); f32: a float32 entry (channel-major; time-major for the
+// _f32_tm entries, which pass gen::F32TM as arg_layout: gen::float_layout).  at: false, the
 // windows at every hop-th sample (onsets, W_at and n_bad unused); true, the W_at windows at the
 // device list onsets (hop unused).  nw1: the 16-sample blocks a layer-1 workgroup takes per step
 // (win::NW1).  On NET_OK what the launches take: the gen::Layout, W and the geometry of L.
@@ -98,10 +107,10 @@ inline int check_windows(int C, int T, const void* x, int arg_layout, bool f32, 
                          const int64_t* onsets, size_t W_at, const int8_t* y, const int32_t* n_bad, const void* ws,
                          size_t ws_bytes, int device, int nw1, WindowsGeom& g) {
   if ((!at && hop == 0) || (!f32 && arg_layout != 0 && arg_layout != 1)) return NET_ERR_INVALID;
-  const int layout = f32 ? (int)gen::F32 : arg_layout;  // gen::Layout
+  const int layout = f32 ? gen::float_layout(arg_layout) : arg_layout;  // gen::Layout
   const size_t W = at ? W_at : windows_count((size_t)T, L, hop);
   if (W && (!x || !y || !ws || (at && !onsets))) return NET_ERR_INVALID;
-  if (((uintptr_t)y & 3) != 0 || (layout == 2 && ((uintptr_t)x & 3) != 0)) return NET_ERR_INVALID;
+  if (((uintptr_t)y & 3) != 0 || (gen::is_float(layout) && ((uintptr_t)x & 3) != 0)) return NET_ERR_INVALID;
   if (at && (((uintptr_t)n_bad & 3) != 0 || ((uintptr_t)onsets & 7) != 0)) return NET_ERR_INVALID;
   if (L > SIZE_MAX / 32) return NET_ERR_INVALID;  // (far past the offset limit below; 16 rs cannot wrap)
   const size_t rs = windows_row_stride(L);
@@ -111,7 +120,7 @@ inline int check_windows(int C, int T, const void* x, int arg_layout, bool f32, 
   // window indices are int in the kernel: w + gridDim.x (grid <= 2 per CU) must not wrap
   if (W > (size_t)INT32_MAX - 65535) return NET_ERR_INVALID;
   // the recording and the workspace are each one buffer view with 32-bit offsets
-  const size_t per = std::max((size_t)16, (size_t)C * (layout == 2 ? sizeof(float) : 1));
+  const size_t per = std::max((size_t)16, (size_t)C * gen::elem_bytes(layout));
   if (L > (((size_t)1 << 31) - 1) / per) return NET_ERR_INVALID;
   g.layout = layout;
   g.W = W;

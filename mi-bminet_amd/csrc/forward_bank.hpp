@@ -141,7 +141,7 @@ __global__ __launch_bounds__(win::NT1) void k_layer1_rec_bank(const gen::GenPara
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int8_t* stg = (int8_t*)stg_v + 1024 * wave;
   const int C = sets->C;  // every set's
-  const gen::View v = gen::make_view(x, (L == gen::F32 ? 4u : 1u) * (unsigned)C * (unsigned)Lr);
+  const gen::View v = gen::make_view(x, gen::elem_bytes(L) * (unsigned)C * (unsigned)Lr);
   const int NB = (Lr + 15) / 16;
   int8_t* row = ws + (size_t)(lane & 15) * (size_t)rs;
   const Range64 rg = range_of(blockIdx.x * win::NW1 + (unsigned)wave, gridDim.x * win::NW1, (unsigned long long)NB);
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(win::NT1) void k_layer1_rec_bank(const gen::GenPara
     if (s != cur) {
       cur = s;
       k = gen::l1_consts<L>(sets + s, lane);
-      if constexpr (L == gen::F32) {
+      if constexpr (gen::is_float(L)) {
         const Scale q = scales[s];
         qs = q.qs;
         qy = q.qy;

@@ -103,7 +103,8 @@ __device__ __forceinline__ View trial_view(const int8_t* x, long long b, int C, 
 }
 
 // The A fragment of layer-1 block blk (samples 16 blk .. +15), before staging: time-major, lane
-// (j, g) holds channels 16 c .. +15 (c = l1_chunk(g, C)) of sample 16 blk + j; channel-major,
+// (j, g) holds channels 16 c .. +15 (c = l1_chunk(g, C)) of sample 16 blk + j (int8, or float32
+// quantised here: F32TM, the layer-1 kernels of the windows and streams only); channel-major,
 // lane c holds samples 16 blk .. +15 of channel c.  K-slots past C meet zero weights, so what those lanes read does not
 // matter: the loads are unconditional (no per-lane branch between one block's loads and the next
 // block's), and channel-major rows past C re-read row C - 1.  T: the row stride of the
@@ -120,6 +121,13 @@ __device__ __forceinline__ v4i l1_fetch(const View& v, int blk, int C, int T, in
     return load16u(v.r, d + (ub + j) * uC + 16u * (unsigned)l1_chunk((int)g, C));
   } else if constexpr (L == CT) {
     return load16u(v.r, d + (unsigned)min(lane, C - 1) * uT + ub);
+  } else if constexpr (L == F32TM) {
+    // TM's fragment in floats: the 64 bytes of channels 16 c .. +15 of sample 16 blk + j, quantised
+    // here (delta = 0: the view is 4-byte aligned).  A slot past C holds the next sample's float or a
+    // zero past the view, a finite int8 once quantised (NaN and the infinities too), and meets a
+    // zero weight.
+    const unsigned j = lane & 15, g = lane >> 4;
+    return load16f(v.r, 4u * ((ub + j) * uC + 16u * (unsigned)l1_chunk((int)g, C)), qs, qy);
   } else {
     return load16f(v.r, 4u * ((unsigned)min(lane, C - 1) * uT + ub), qs, qy);
   }
@@ -199,11 +207,12 @@ struct L1C {  // a lane's layer-1 constants (filter lane & 15)
   unsigned m;
   float r, c;
 };
-// layout L's: time-major fragments take the K order of l1_chunk, the others the natural one
+// layout L's: time-major fragments (int8 or float32) take the K order of l1_chunk, the others the
+// natural one
 template <int L>
 __device__ __forceinline__ L1C l1_consts(const GenParams* __restrict__ gp, int lane) {
   const int j = lane & 15;
-  return L1C{L == TM ? gp->l1_b[lane] : gp->l1_bn[lane], gp->l1_off[j], gp->l1_xs[j], gp->l1_m[j], gp->l1_r[j], gp->l1_c[j]};
+  return L1C{is_time_major(L) ? gp->l1_b[lane] : gp->l1_bn[lane], gp->l1_off[j], gp->l1_xs[j], gp->l1_m[j], gp->l1_r[j], gp->l1_c[j]};
 }
 
 // The arithmetic of one layer-1 block: the fragment `raw` of 16 samples (l1_fetch; transposed
@@ -211,7 +220,7 @@ __device__ __forceinline__ L1C l1_consts(const GenParams* __restrict__ gp, int l
 // sample 4 (lane >> 4) + r of the block, before the saturating pack.
 template <int L, bool XR, bool CB>
 __device__ __forceinline__ void l1_outputs(v4i raw, int8_t* stg, const L1C& k, int lane, int (&y)[4]) {
-  const v4i a = L == TM ? raw : wg::stage_block<TrK>(raw, stg, lane);
+  const v4i a = is_time_major(L) ? raw : wg::stage_block<TrK>(raw, stg, lane);
   const v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, k.wf, (v4i){k.off, k.off, k.off, k.off}, 0, 0, 0);
 #pragma unroll
   for (int r = 0; r < 4; r++) y[r] = rq1<XR, CB>(acc[r], k.m, k.xs, k.r, k.c);

@@ -1,4 +1,4 @@
-// forward_stream.hpp — live streams (gfx950): net_streams_push[_f32], include/mibminet.h.  A stream
+// forward_stream.hpp — live streams (gfx950): net_streams_push[_f32[_tm]], include/mibminet.h.  A stream
 // group is S sessions of one bank's geometry, each decoded by its own set of the bank, all advancing
 // by the same n samples per push.  Layer 1 is pointwise in time (forward_win.hpp), so its output is
 // state that persists between calls: a push runs layer 1 on the n new samples of every session
@@ -37,8 +37,9 @@ using bank::Scale;
 // Layer 1 of the new samples.  Items are (session s, 16-sample block b of its chunk), session-major
 // (item = s nb + b); wave g of gridDim.x NW1 takes the contiguous items range_of(g, gridDim.x NW1, S nb)
 // with a current set per wave, as bank::k_layer1_rec_bank does.  x: the S chunks, contiguous, in
-// layout L ([n][C] int8, [C][n] int8, [C][n] float32) at any byte alignment (float32: 4); the view is
-// one session's chunk, the row stride of the channel-major layouts n.  A set index is compared
+// layout L ([n][C] int8, [C][n] int8, [C][n] float32, [n][C] float32) at any byte alignment (float32:
+// 4); the view is one session's chunk, the row stride of the channel-major layouts n (so a time-major
+// fragment's K-slots past C read the session's own next sample, or zeros past its last).  A set index is compared
 // unsigned before any address is formed from it; a session whose index is outside the bank stores
 // nothing.  Stores: sample 16 b + 4 g + r < n of the chunk goes to position (p0 + 16 b + 4 g + r)
 // mod cap of the lane's row and to that + cap.  Samples >= n of a partial last block are not
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(win::NT1) void k_layer1_ring(const gen::GenParams* 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int8_t* stg = (int8_t*)stg_v + 1024 * wave;
   const int C = sets->C;  // every set's
-  const unsigned chunk = (L == gen::F32 ? 4u : 1u) * (unsigned)C * (unsigned)n;  // <= 2^24
+  const unsigned chunk = gen::elem_bytes(L) * (unsigned)C * (unsigned)n;  // <= 2^24
   const int g = lane >> 4;
   const Range64 rg = range_of(blockIdx.x * win::NW1 + (unsigned)wave, gridDim.x * win::NW1, (unsigned long long)items);
   const int end = (int)rg.hi;
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(win::NT1) void k_layer1_ring(const gen::GenParams* 
     if (set != cur) {
       cur = set;
       k = gen::l1_consts<L>(sets + set, lane);
-      if constexpr (L == gen::F32) {
+      if constexpr (gen::is_float(L)) {
         const Scale q = scales[set];
         qs = q.qs;
         qy = q.qy;
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(win::NT1) void k_layer1_ring_each(const gen::GenPar
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int8_t* stg = (int8_t*)stg_v + 1024 * wave;
   const int C = sets->C;  // every set's
-  const unsigned slot = (L == gen::F32 ? 4u : 1u) * (unsigned)C * (unsigned)n_max;  // <= 2^24
+  const unsigned slot = gen::elem_bytes(L) * (unsigned)C * (unsigned)n_max;  // <= 2^24
   const int g = lane >> 4;
   const Range64 rg = range_of(blockIdx.x * win::NW1 + (unsigned)wave, gridDim.x * win::NW1, (unsigned long long)items);
   const int end = (int)rg.hi;
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(win::NT1) void k_layer1_ring_each(const gen::GenPar
     if (set != cur) {
       cur = set;
       k = gen::l1_consts<L>(sets + set, lane);
-      if constexpr (L == gen::F32) {
+      if constexpr (gen::is_float(L)) {
         const Scale q = scales[set];
         qs = q.qs;
         qy = q.qy;

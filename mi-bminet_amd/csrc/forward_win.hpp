@@ -28,8 +28,8 @@ constexpr int NT1 = 64 * NW1;
 
 // Layer 1 of recording blocks blk = 16 samples (gen::l1_fetch with the recording length Lr as the
 // row stride of the channel-major layouts, gen::l1_block), one wave per block, grid-strided.
-// x: the recording in layout L (gen::Layout: [Lr][C] int8, [C][Lr] int8, [C][Lr] float32), any
-// byte alignment (float32: 4); the view's bound keeps every load inside the recording (a partial
+// x: the recording in layout L (gen::Layout: [Lr][C] int8, [C][Lr] int8, [C][Lr] float32, [Lr][C]
+// float32), any byte alignment (float32: 4); the view's bound keeps every load inside the recording (a partial
 // last block reads zeros or the next row, and its samples >= Lr are stored as zeros inside the
 // row stride).  ws: [F1][rs], rs >= 16 ceil(Lr / 16).
 template <int L, bool XR, bool CB>
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(NT1) void k_layer1_rec(const gen::GenParams* __rest
   const int C = gp->C;
   const gen::L1C k = gen::l1_consts<L>(gp, lane);
   // the whole recording as one "trial"
-  const gen::View v = gen::make_view(x, (L == gen::F32 ? 4u : 1u) * (unsigned)C * (unsigned)Lr);
+  const gen::View v = gen::make_view(x, gen::elem_bytes(L) * (unsigned)C * (unsigned)Lr);
   const int NB = (Lr + 15) / 16;
   int8_t* row = ws + (size_t)(lane & 15) * (size_t)rs;
   for (int blk = (int)blockIdx.x * NW1 + wave; blk < NB; blk += (int)gridDim.x * NW1)  // wave-uniform

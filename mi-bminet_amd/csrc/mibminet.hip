@@ -140,9 +140,13 @@ int with_flags(const gen::GenParams& g, F&& f) {
 }
 
 // The same for a run-time layout (0 time-major int8, 1 channel-major int8, 2 channel-major
-// float32): calls f with the gen::Layout as a std::integral_constant.
-template <class F>
+// float32): calls f with the gen::Layout as a std::integral_constant.  L1: a layer-1 kernel of the
+// windows or streams, which also takes gen::F32TM (time-major float32); the batched kernels do not.
+template <bool L1 = false, class F>
 int with_layout(int layout, F&& f) {
+  if constexpr (L1) {
+    if (layout == gen::F32TM) return f(std::integral_constant<int, gen::F32TM>{});
+  }
   if (layout == 2) return f(std::integral_constant<int, gen::F32>{});
   return layout == 1 ? f(std::integral_constant<int, gen::CT>{}) : f(std::integral_constant<int, gen::TM>{});
 }
@@ -282,7 +286,7 @@ int launch_windows(DeviceState& ds, const gen::GenParams& hg, const void* p, con
                    const int64_t* onsets = nullptr, int32_t* n_bad = nullptr) {
   const int lds = windows_lds(hg);
   const gen::GenParams* gp = (const gen::GenParams*)p;
-  return with_layout(g.layout, [&](auto lc) {
+  return with_layout<true>(g.layout, [&](auto lc) {
     return with_flags(hg, [&](auto rb, auto xr, auto cb) {
       constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
       // 8 workgroups of 4 waves fill a CU
@@ -314,7 +318,7 @@ int windows_async(const void* x, int arg_layout, bool f32, size_t L, bool at, si
   if (const int rc = check_windows(d.C, d.T, x, arg_layout, f32, L, at, hop, onsets, W_at, y, n_bad, ws, ws_bytes, device,
                                    win::NW1, g))
     return rc;
-  if (g.layout == 2)
+  if (gen::is_float(g.layout))
     if (const int rc = check_scale(qs)) return rc;
   const Image& win = s.img[IMG_WINDOWS];
   if (!win.data) return NET_ERR_UNSUPPORTED;
@@ -427,7 +431,7 @@ int bank_windows_async(const net_bank* b, const void* x, int arg_layout, bool f3
   const auto* scales = f32 ? (const bank::Scale*)(sets + b->sets.size()) : nullptr;
   const int n_sets = (int)b->sets.size();
   const hipStream_t st = (hipStream_t)stream;
-  return with_layout(g.layout, [&](auto lc) {
+  return with_layout<true>(g.layout, [&](auto lc) {
     return with_flags(hg, [&](auto rb, auto xr, auto cb) {
       constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
       // 8 workgroups of 4 waves fill a CU (launch_windows)
@@ -525,7 +529,7 @@ int streams_push(net_streams* g, const void* x, int arg_layout, bool f32, size_t
   int8_t* ring = (int8_t*)g->mem;
   const long long* origin = (const long long*)(ring + g->at.origin);
   const int* set_of = (const int*)(ring + g->at.set);
-  const int rc = with_layout(f32 ? (int)gen::F32 : arg_layout, [&](auto lc) {
+  const int rc = with_layout<true>(f32 ? gen::float_layout(arg_layout) : arg_layout, [&](auto lc) {
     return with_flags(hg, [&](auto rb, auto xr, auto cb) {
       constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
       // 8 workgroups of 4 waves fill a CU (launch_windows)
@@ -589,7 +593,7 @@ int streams_push_each(net_streams* g, const void* x, int arg_layout, bool f32, c
                      (long long*)(ring + g->pos_at), plan, (int*)cnt_out, (long long*)win0, (int*)n_bad, (int)g->S, hg.T,
                      (unsigned long long)g->hop, (int)g->cap, (int)n_max);
   if (const int rc = hip_err(hipGetLastError())) return rc;
-  const int rc = with_layout(f32 ? (int)gen::F32 : arg_layout, [&](auto lc) {
+  const int rc = with_layout<true>(f32 ? gen::float_layout(arg_layout) : arg_layout, [&](auto lc) {
     return with_flags(hg, [&](auto rb, auto xr, auto cb) {
       constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
       const size_t wgs = (p.l1_items + win::NW1 - 1) / win::NW1;
@@ -857,6 +861,11 @@ int net_params_load(const void* blob, size_t len) {
   return install(hp);
 }
 
+int net_blob_widen(const void* blob, size_t len, int R, const int32_t* channels, void* out, size_t cap,
+                   size_t* out_len) {
+  return widen_blob(blob, len, R, channels, out, cap, out_len);
+}
+
 int net_params_load_arrays(const net_arrays_t* a) {
   auto hp = std::make_shared<HostParams>();
   if (const int rc = parse_arrays(a, *hp)) return rc;
@@ -974,6 +983,10 @@ int net_streams_push_f32(net_streams_t* st, const float* x, size_t n, int8_t* y,
   return streams_push(st, x, 1, true, n, y, n_bad, stream);
 }
 
+int net_streams_push_f32_tm(net_streams_t* st, const float* x, size_t n, int8_t* y, int32_t* n_bad, void* stream) {
+  return streams_push(st, x, gen::F32TM, true, n, y, n_bad, stream);
+}
+
 int net_streams_restart(net_streams_t* st, size_t i, int32_t set, void* stream) {
   return streams_restart(st, i, set, stream);
 }
@@ -993,6 +1006,11 @@ int net_streams_push_each(net_streams_t* st, const int8_t* x, int layout, const 
 int net_streams_push_each_f32(net_streams_t* st, const float* x, const int32_t* cnt_in, size_t n_max, int8_t* y,
                               int32_t* cnt_out, int64_t* win0, int32_t* n_bad, void* stream) {
   return streams_push_each(st, x, 1, true, cnt_in, n_max, y, cnt_out, win0, n_bad, stream);
+}
+
+int net_streams_push_each_f32_tm(net_streams_t* st, const float* x, const int32_t* cnt_in, size_t n_max, int8_t* y,
+                                 int32_t* cnt_out, int64_t* win0, int32_t* n_bad, void* stream) {
+  return streams_push_each(st, x, gen::F32TM, true, cnt_in, n_max, y, cnt_out, win0, n_bad, stream);
 }
 
 int net_streams_positions(net_streams_t* st, int64_t* pos_out, void* stream) {
@@ -1036,6 +1054,16 @@ int net_model_compute_windows_at(const int8_t* x, int layout, size_t L, const in
 int net_model_compute_windows_at_f32(const float* x, size_t L, const int64_t* onsets, size_t W, float scale, int8_t* y,
                                      int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream) {
   return windows_async(x, 1, true, L, true, 0, onsets, W, scale, y, n_bad, ws, ws_bytes, device, stream);
+}
+
+int net_model_compute_windows_f32_tm(const float* x, size_t L, size_t hop, float scale, int8_t* y, void* ws,
+                                     size_t ws_bytes, int device, void* stream) {
+  return windows_async(x, gen::F32TM, true, L, false, hop, nullptr, 0, scale, y, nullptr, ws, ws_bytes, device, stream);
+}
+
+int net_model_compute_windows_at_f32_tm(const float* x, size_t L, const int64_t* onsets, size_t W, float scale,
+                                        int8_t* y, int32_t* n_bad, void* ws, size_t ws_bytes, int device, void* stream) {
+  return windows_async(x, gen::F32TM, true, L, true, 0, onsets, W, scale, y, n_bad, ws, ws_bytes, device, stream);
 }
 
 size_t net_windows_multi_count(const size_t* lengths, size_t R, size_t hop) {
@@ -1102,6 +1130,12 @@ int net_model_compute_windows_bank_f32(const net_bank_t* bank, const float* x, s
                                        const int64_t* onsets, size_t W, int8_t* y, int32_t* n_bad, void* ws,
                                        size_t ws_bytes, int device, void* stream) {
   return bank_windows_async(bank, x, 1, true, L, blk_set, onsets, W, y, n_bad, ws, ws_bytes, device, stream);
+}
+
+int net_model_compute_windows_bank_f32_tm(const net_bank_t* bank, const float* x, size_t L, const int32_t* blk_set,
+                                          const int64_t* onsets, size_t W, int8_t* y, int32_t* n_bad, void* ws,
+                                          size_t ws_bytes, int device, void* stream) {
+  return bank_windows_async(bank, x, gen::F32TM, true, L, blk_set, onsets, W, y, n_bad, ws, ws_bytes, device, stream);
 }
 
 size_t net_bank_windows_starts(const size_t* lengths, size_t R, int64_t* starts) {

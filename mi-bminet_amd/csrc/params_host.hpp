@@ -16,8 +16,9 @@ constexpr uint32_t FLAG_CLIP_BALANCED = 2;  // golden-model clip_balanced=True (
 
 struct Dims {
   int C = 0, T = 0, F1 = 0, F2 = 0, D = 0, N = 0, wbits = 8;
-  int C_ALIGN() const { return (C + 3) & ~3; }
-  int T_ALIGN() const { return (T + 3) & ~3; }
+  // (unsigned: a header may carry INT_MAX, and the parser asks before it has sized anything)
+  int C_ALIGN() const { return (int)(((unsigned)C + 3u) & ~3u); }
+  int T_ALIGN() const { return (int)(((unsigned)T + 3u) & ~3u); }
   int T8() const { return T / 8; }
   int T8_ALIGN() const { return (T8() + 3) & ~3; }
   int T64() const { return T8() / 8; }
@@ -141,6 +142,52 @@ inline int parse_blob(const void* blob, size_t len, HostParams& hp) {
   hp.l5_weight = r.w((size_t)d.N, F2 * (size_t)d.T64_ALIGN(), d.wbits);  // F2 T64_ALIGN < 2^56
   if (!r.ok || r.pos != len) return NET_ERR_BLOB;
   return check_pads(hp);
+}
+
+// net_blob_widen: the blob over R source rows.  Layer 1 is a dense contraction over its K-slots
+// whatever C is, so the set whose layer-1 weight column channels[c] is the blob's column c, every
+// other column zero, computes on u[R][T] what the blob computes on u[channels]: the same int32
+// accumulators (zeros add nothing), hence the same reachable ranges, requant path and range
+// verdict.  The output is the input with C := R and l1_weight_align as [F2][R_ALIGN]; every other
+// byte is copied.  The parser's verdict comes first; then R in 1 .. 64 and channels, C distinct
+// entries in 0 .. R - 1 (two equal entries would add two columns, and the sum may leave int8); then
+// the size: *out_len (if non-null) is set whenever the arguments pass, out == NULL asks for it only.
+inline int widen_blob(const void* blob, size_t len, int R, const int32_t* channels, void* out, size_t cap,
+                      size_t* out_len) {
+  HostParams hp;
+  if (const int rc = parse_blob(blob, len, hp)) return rc;
+  const Dims& d = hp.d;
+  if (R < 1 || R > 64 || !channels || d.C > R) return NET_ERR_INVALID;  // C > R: no C distinct entries
+  bool seen[64] = {};
+  for (int c = 0; c < d.C; c++) {
+    if (channels[c] < 0 || channels[c] >= R || seen[channels[c]]) return NET_ERR_INVALID;
+    seen[channels[c]] = true;
+  }
+  // the layer-1 weights follow the header and the two int32[F2] arrays; F2 C_ALIGN is a multiple of
+  // 4, so int4 rows pack to whole bytes (Reader::w)
+  const size_t F2n = (size_t)d.F2, CA = (size_t)d.C_ALIGN(), RA = ((size_t)R + 3) & ~(size_t)3;
+  auto packed = [&](size_t count) { return ((d.wbits == 8 ? count : count / 2) + 3) & ~(size_t)3; };
+  const size_t at = (size_t)HEADER_SIZE + 8 * F2n, old_bytes = packed(F2n * CA), new_bytes = packed(F2n * RA);
+  const size_t need = len - old_bytes + new_bytes;  // parse_blob read old_bytes from at: len >= at + old_bytes
+  if (out_len) *out_len = need;
+  if (!out) return NET_OK;
+  if (cap < need) return NET_ERR_INVALID;
+  std::vector<int8_t> w(F2n * RA, 0);
+  for (size_t f = 0; f < F2n; f++)
+    for (int c = 0; c < d.C; c++) w[f * RA + (size_t)channels[c]] = hp.l1_weight_align[f * CA + (size_t)c];
+  uint8_t* o = (uint8_t*)out;
+  const uint8_t* b = (const uint8_t*)blob;
+  std::memcpy(o, b, at);
+  const uint32_t r32 = (uint32_t)R;
+  std::memcpy(o + 12, &r32, 4);  // the header's C (parse_blob: h[1])
+  std::memset(o + at, 0, new_bytes);
+  if (d.wbits == 8) {
+    std::memcpy(o + at, w.data(), w.size());
+  } else {
+    for (size_t i = 0; i < w.size(); i++) o[at + i / 2] |= (uint8_t)((w[i] & 0xF) << (4 * (i & 1)));
+  }
+  std::memcpy(o + at + new_bytes, b + at + old_bytes, len - at - old_bytes);
+  return NET_OK;
 }
 
 // net_params_load_arrays: the blob header's checks (parse_blob, check_dims), then the arrays it would carry

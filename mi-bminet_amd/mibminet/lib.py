@@ -45,6 +45,7 @@ PROTOTYPES = {
     "net_last_error": "int ()",
     "net_params_load": "int (ptr, size_t)",
     "net_params_info": "int (ptr)",
+    "net_blob_widen": "int (ptr, size_t, int, ptr, ptr, size_t, ptr)",
     "net_params_load_arrays": "int (ptr)",
     "net_params_dims": "int (ptr)",
     "net_params_unload": "void ()",
@@ -59,8 +60,10 @@ PROTOTYPES = {
     "net_windows_workspace": "size_t (size_t)",
     "net_model_compute_windows": "int (ptr, int, size_t, size_t, ptr, ptr, size_t, int, ptr)",
     "net_model_compute_windows_f32": "int (ptr, size_t, size_t, float, ptr, ptr, size_t, int, ptr)",
+    "net_model_compute_windows_f32_tm": "int (ptr, size_t, size_t, float, ptr, ptr, size_t, int, ptr)",
     "net_model_compute_windows_at": "int (ptr, int, size_t, ptr, size_t, ptr, ptr, ptr, size_t, int, ptr)",
     "net_model_compute_windows_at_f32": "int (ptr, size_t, ptr, size_t, float, ptr, ptr, ptr, size_t, int, ptr)",
+    "net_model_compute_windows_at_f32_tm": "int (ptr, size_t, ptr, size_t, float, ptr, ptr, ptr, size_t, int, ptr)",
     "net_windows_multi_count": "size_t (ptr, size_t, size_t)",
     "net_windows_multi_onsets": "size_t (ptr, size_t, size_t, ptr, size_t, ptr)",
     "net_model_compute_epochs": "int (ptr, size_t, size_t, ptr, ptr, size_t, ptr, ptr, int, ptr)",
@@ -72,6 +75,7 @@ PROTOTYPES = {
     "net_model_compute_epochs_bank_f32": "int (ptr, ptr, size_t, size_t, ptr, ptr, ptr, size_t, ptr, ptr, int, ptr)",
     "net_model_compute_windows_bank": "int (ptr, ptr, int, size_t, ptr, ptr, size_t, ptr, ptr, ptr, size_t, int, ptr)",
     "net_model_compute_windows_bank_f32": "int (ptr, ptr, size_t, ptr, ptr, size_t, ptr, ptr, ptr, size_t, int, ptr)",
+    "net_model_compute_windows_bank_f32_tm": "int (ptr, ptr, size_t, ptr, ptr, size_t, ptr, ptr, ptr, size_t, int, ptr)",
     "net_bank_windows_starts": "size_t (ptr, size_t, ptr)",
     "net_bank_windows_lists": "size_t (ptr, ptr, ptr, size_t, size_t, ptr, size_t, ptr, size_t, ptr)",
     "net_streams_ring_samples": "size_t (ptr, size_t)",
@@ -82,11 +86,13 @@ PROTOTYPES = {
     "net_streams_origin": "int (ptr, size_t, ptr, ptr)",
     "net_streams_push": "int (ptr, ptr, int, size_t, ptr, ptr, ptr)",
     "net_streams_push_f32": "int (ptr, ptr, size_t, ptr, ptr, ptr)",
+    "net_streams_push_f32_tm": "int (ptr, ptr, size_t, ptr, ptr, ptr)",
     "net_streams_restart": "int (ptr, size_t, int32_t, ptr)",
     "net_streams_create_each": "int (ptr, ptr, size_t, size_t, size_t, int, ptr)",
     "net_streams_each_rows": "size_t (size_t, size_t)",
     "net_streams_push_each": "int (ptr, ptr, int, ptr, size_t, ptr, ptr, ptr, ptr, ptr)",
     "net_streams_push_each_f32": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr, ptr, ptr)",
+    "net_streams_push_each_f32_tm": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr, ptr, ptr)",
     "net_streams_positions": "int (ptr, ptr, ptr)",
     "net_model_compute_batch_multi": "int (int, ptr, ptr, ptr, ptr, ptr)",
     "net_model_compute_batch_multi_ct": "int (int, ptr, ptr, ptr, ptr, ptr)",
@@ -190,6 +196,26 @@ def params_load(ps: ParamSet) -> None:
 
 def params_load_blob(blob: bytes) -> None:
     _load_blob(blob, None)
+
+
+def blob_widen(blob: bytes, R: int, channels) -> bytes:
+    """net_blob_widen: ``blob`` over ``R`` source rows, its channel c reading row ``channels[c]``
+    (ParamSet.widened is the same transform in Python).  Host only."""
+    ch = [int(c) for c in channels]
+    if any(c < -2**31 or c >= 2**31 for c in ch):
+        raise ValueError("channels must be int32 row indices")
+    src = ctypes.create_string_buffer(bytes(blob), len(blob))
+    # the entry reads the blob's C entries (C <= R <= 64 once it reads any): -1, refused, past the list's end
+    arr = (ctypes.c_int32 * max(len(ch), 64))(*ch, *([-1] * (64 - len(ch))))
+    n = ctypes.c_size_t(0)
+    rc = load().net_blob_widen(src, len(blob), R, arr, None, 0, ctypes.byref(n))
+    C = int.from_bytes(bytes(blob)[12:16], "little")
+    if rc != NET_ERR_BLOB and len(ch) != C:  # (a blob the parser took has its C there)
+        raise ValueError(f"channels must list the blob's {C} channels, got {len(ch)}")
+    _check(rc, "net_blob_widen")
+    out = ctypes.create_string_buffer(max(n.value, 1))
+    _check(load().net_blob_widen(src, len(blob), R, arr, out, n.value, ctypes.byref(n)), "net_blob_widen")
+    return out.raw[:n.value]
 
 
 def params_dims() -> dict:
@@ -611,15 +637,18 @@ def forward_windows_torch(x, hop: int, layout: str = "ct", stream=None, return_y
     return (y, ws) if return_y1 else y
 
 
-def forward_windows_f32_torch(x, hop: int, scale: float, stream=None):
-    """net_model_compute_windows_f32: x is a CUDA/HIP float32 recording [C][L], quantised per
-    sample as forward_f32_torch does; returns the logits [W][N] of its sliding windows."""
-    L, _ = _check_recording(x, ("float32",), True, _dims().C)
+def forward_windows_f32_torch(x, hop: int, scale: float, stream=None, layout: str = "ct", return_y1: bool = False):
+    """net_model_compute_windows_f32 / _f32_tm: x is a CUDA/HIP float32 recording, ``layout`` "ct" =
+    [C][L] or "tc" = [L][C] (sample-major frames), quantised per sample as forward_f32_torch does;
+    returns the logits [W][N] of its sliding windows, with ``return_y1`` also the workspace."""
+    _layout_code(layout)
+    L, _ = _check_recording(x, ("float32",), layout == "ct", _dims().C)
     y, ws = _windows_buffers(x, L, hop)
     s, dev = _launch(x, stream)
-    _check(load().net_model_compute_windows_f32(x.data_ptr(), L, hop, scale, y.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                dev, s.cuda_stream), "net_model_compute_windows_f32")
-    return y
+    name = "net_model_compute_windows_f32" + ("" if layout == "ct" else "_tm")
+    _check(getattr(load(), name)(x.data_ptr(), L, hop, scale, y.data_ptr(), ws.data_ptr(), ws.numel(), dev, s.cuda_stream),
+           name)
+    return (y, ws) if return_y1 else y
 
 
 def _require_bank(bank):
@@ -634,6 +663,7 @@ class _Net:
 
     def __init__(self, bank=None):
         self.bank, self.handle, self.scale = bank, () if bank is None else (bank.handle,), ()
+        self.f32_suffix = "_f32"  # "_f32_tm": float32 input in sample-major frames (_windows_source)
 
     dims = property(lambda self: _dims() if self.bank is None else self.bank.dims)
 
@@ -680,7 +710,7 @@ def _forward_onsets(net, name: str, x, head, onsets, mid, stream, check: bool, n
         lists = [v.to(x.device).contiguous() for v in lists]
         nbad = torch.zeros((1,), dtype=torch.int32, device=x.device) if check else None
     y = torch.empty((n, net.dims.N), dtype=torch.int8, device=x.device)
-    name += "_f32" if x.dtype == torch.float32 else ""
+    name += net.f32_suffix if x.dtype == torch.float32 else ""
     ptrs = [v.data_ptr() if n else None for v in lists] + [None] * (set_of is None)
     y_ptr, nbad_ptr = y.data_ptr() if n else None, nbad.data_ptr() if check else None
     _check(getattr(load(), name)(*net.handle, x.data_ptr(), *head, *ptrs, n, *net.scale, y_ptr, nbad_ptr, *mid, dev,
@@ -696,12 +726,12 @@ def _forward_onsets(net, name: str, x, head, onsets, mid, stream, check: bool, n
 
 def _windows_source(net, x, layout: str, scale, noun: str):
     """The checks of the array ``x`` (``noun``) the windows-at entries of ``net`` read: int8 ("ct" =
-    [C][L] or "tc" = [L][C]) or float32 ([C][L]).  Returns (L, the arguments that follow x)."""
+    [C][L] or "tc" = [L][C]) or float32 (the same two: the _f32 entry or the _f32_tm one).  Returns (L,
+    the arguments that follow x)."""
     code = _layout_code(layout)
     L, f32 = _check_recording(x, ("int8", "float32"), layout == "ct", net.dims.C, noun)
-    if f32 and layout != "ct":
-        raise ValueError(f'a float32 {noun.rpartition(" ")[2]} is "ct" ([C][L])')
     net.float_input(f32, scale, "recording")
+    net.f32_suffix = "_f32" if layout == "ct" else "_f32_tm"
     return L, ((L,) if f32 else (code, L))
 
 
@@ -709,7 +739,7 @@ def forward_windows_at_torch(x, onsets, layout: str = "ct", scale: Optional[floa
                              check: bool = True, return_y1: bool = False):
     """net_model_compute_windows_at / _f32: the windows x[:, onsets[i] : onsets[i] + T] of one
     CUDA/HIP recording, layer 1 run once over the whole of it.  ``x`` is int8 ("ct" = [C][L] or
-    "tc" = [L][C]) or float32 ([C][L]; ``scale`` is required iff it is float32), ``onsets`` an int64
+    "tc" = [L][C]) or float32 (either layout; ``scale`` is required iff it is float32), ``onsets`` an int64
     tensor or a sequence, in any order, duplicates allowed.  Returns the logits [W][N] int8, row i
     what forward_ct_torch returns for that window; with ``return_y1`` also the workspace
     [16][row_stride].  The rows of onsets outside 0 .. L - T are zero; with ``check`` their count
@@ -948,8 +978,8 @@ def forward_windows_bank_torch(bank, x, blk_set, onsets, layout: str = "ct", str
                                return_y1: bool = False):
     """net_model_compute_windows_bank / _f32: the windows x[:, onsets[i] : onsets[i] + T] of many
     recordings laid along time in ``x`` at multiples of 16 samples, each classified by the set of
-    its recording.  ``x`` is int8 ("ct" = [C][L] or "tc" = [L][C]) or float32 ([C][L]; needs a bank
-    with scales), C and T the bank's; ``blk_set`` a device int32 tensor of ceil(L / 16) entries, the
+    its recording.  ``x`` is int8 ("ct" = [C][L] or "tc" = [L][C]) or float32 (either layout; needs a
+    bank with scales), C and T the bank's; ``blk_set`` a device int32 tensor of ceil(L / 16) entries, the
     set of each 16-sample block (-1: a gap); ``onsets`` an int64 tensor or a sequence
     (bank_windows_lists builds both).  Returns the logits [W][N] int8, row i what forward_ct_torch
     returns for that window with its set loaded; with ``return_y1`` also the workspace
@@ -1054,6 +1084,7 @@ class Streams:
         return int(load().net_streams_push_windows(self.bank.handle, self.hop, self.info()[4], n))
 
     def _push(self, x, dtype: str, code, n: int, stream, out):
+        """``dtype``: the entry's suffix, "" (int8), "_f32" or "_f32_tm"."""
         torch = _torch()
         k, N = self.windows(n), self.bank.dims.N
         s, _ = _launch(x, stream)
@@ -1063,7 +1094,7 @@ class Streams:
             out = torch.empty((self.S, k, N), dtype=torch.int8, device=x.device)
         else:
             _check_tensor(out, "out", ("int8",), (self.S, k, N))
-        name = "net_streams_push" + ("_f32" if dtype == "float32" else "")
+        name = "net_streams_push" + dtype
         _check(getattr(load(), name)(self.handle, x.data_ptr(), *code, n, out.data_ptr() if k else None, nbad.data_ptr(),
                                      s.cuda_stream), name)
         return out, nbad
@@ -1078,15 +1109,19 @@ class Streams:
         code = _layout_code(layout)
         C = self.bank.dims.C
         _check_tensor(x, "x", ("int8",), (self.S, C, "n") if layout == "ct" else (self.S, "n", C))
-        return self._push(x, "int8", (code,), int(x.shape[2 if layout == "ct" else 1]), stream, out)
+        return self._push(x, "", (code,), int(x.shape[2 if layout == "ct" else 1]), stream, out)
 
-    def push_f32(self, x, stream=None, out=None):
-        """net_streams_push_f32: ``x`` is a CUDA/HIP float32 tensor [S][C][n]; session i is quantised
-        with the bank's scale of its set.  Returns what push returns."""
+    def push_f32(self, x, stream=None, out=None, layout: str = "ct"):
+        """net_streams_push_f32 / _f32_tm: ``x`` is a CUDA/HIP float32 tensor, "ct" = [S][C][n] or "tc" =
+        [S][n][C] (frames as an amplifier delivers them); session i is quantised with the bank's scale
+        of its set.  Returns what push returns."""
+        _layout_code(layout)
         if not self.bank.has_scales:
             raise ValueError("a float32 source needs a bank created with scales")
-        _check_tensor(x, "x", ("float32",), (self.S, self.bank.dims.C, "n"))
-        return self._push(x, "float32", (), int(x.shape[2]), stream, out)
+        C = self.bank.dims.C
+        _check_tensor(x, "x", ("float32",), (self.S, C, "n") if layout == "ct" else (self.S, "n", C))
+        return self._push(x, "_f32" if layout == "ct" else "_f32_tm", (), int(x.shape[2 if layout == "ct" else 1]), stream,
+                          out)
 
     def restart(self, i: int, set: int, stream=None) -> None:
         """net_streams_restart: from the next push session ``i`` is decoded by ``set`` and answers no
@@ -1170,6 +1205,7 @@ class StreamsEach:
         return out
 
     def _push(self, x, dtype: str, code, n_max: int, counts, stream, out):
+        """``dtype``: the entry's suffix, "" (int8), "_f32" or "_f32_tm"."""
         torch = _torch()
         _check_tensor(counts, "counts", ("int32",), (self.S,))
         if counts.device != x.device:
@@ -1182,7 +1218,7 @@ class StreamsEach:
             if out is None:
                 out = torch.empty((self.S, kmax, N), dtype=torch.int8, device=x.device)
         _check_tensor(out, "out", ("int8",), (self.S, kmax, N))
-        name = "net_streams_push_each" + ("_f32" if dtype == "float32" else "")
+        name = "net_streams_push_each" + dtype
         _check(getattr(load(), name)(self.handle, x.data_ptr(), *code, counts.data_ptr(), n_max, out.data_ptr(),
                                      cnt_out.data_ptr(), None, nbad.data_ptr(), s.cuda_stream), name)
         return out, cnt_out, nbad
@@ -1198,15 +1234,19 @@ class StreamsEach:
         code = _layout_code(layout)
         C = self.bank.dims.C
         _check_tensor(x, "x", ("int8",), (self.S, C, "n") if layout == "ct" else (self.S, "n", C))
-        return self._push(x, "int8", (code,), int(x.shape[2 if layout == "ct" else 1]), counts, stream, out)
+        return self._push(x, "", (code,), int(x.shape[2 if layout == "ct" else 1]), counts, stream, out)
 
-    def push_f32(self, x, counts, stream=None, out=None):
-        """net_streams_push_each_f32: ``x`` is a CUDA/HIP float32 tensor [S][C][n_max]; session i is
-        quantised with the bank's scale of its set.  Returns what push returns."""
+    def push_f32(self, x, counts, stream=None, out=None, layout: str = "ct"):
+        """net_streams_push_each_f32 / _f32_tm: ``x`` is a CUDA/HIP float32 tensor of fixed slots, "ct" =
+        [S][C][n_max] or "tc" = [S][n_max][C]; session i is quantised with the bank's scale of its
+        set.  Returns what push returns."""
+        _layout_code(layout)
         if not self.bank.has_scales:
             raise ValueError("a float32 source needs a bank created with scales")
-        _check_tensor(x, "x", ("float32",), (self.S, self.bank.dims.C, "n"))
-        return self._push(x, "float32", (), int(x.shape[2]), counts, stream, out)
+        C = self.bank.dims.C
+        _check_tensor(x, "x", ("float32",), (self.S, C, "n") if layout == "ct" else (self.S, "n", C))
+        return self._push(x, "_f32" if layout == "ct" else "_f32_tm", (), int(x.shape[2 if layout == "ct" else 1]), counts,
+                          stream, out)
 
     def restart(self, i: int, set: int, stream=None) -> None:
         """net_streams_restart on an each-group: session ``i`` starts again at position 0 under

@@ -37,7 +37,22 @@ times are kept apart: the device's (HIP events around the call) and the host's (
 enqueue alone, the queue drained before it).  No gate on these times: nothing here had been
 measured before.
 
-  python tools/bench_streams.py [--cases mmmi_64,bci_1024,bci_1024_shuffled,each_equal,each_ragged]
+Float32 frames as an amplifier delivers them (net_streams_push_f32_tm), 1,024 sessions under 16 sets,
+hop 8, n 16, each candidate with a stream group of its own fed the same samples:
+  f32_tm          22 x 1125.  (new) net_streams_push_f32_tm on [S][n][C]; (a) what a caller did before: a
+                  torch transpose of the tick's frames to [S][C][n] and net_streams_push_f32, both inside
+                  the timed region; (b) net_streams_push_f32 alone on frames transposed outside it.  The
+                  claim checked is new <= a ((a) is an extra pass over the same data, then the same
+                  work); (b) is reported, not judged.
+  f32_tm_montage  19 of 64 electrodes, 19 x 1125.  (new) net_streams_push_f32_tm on [S][n][64] through sets
+                  widened to 64 rows (net_blob_widen); (a) index_select of the 19 columns, the transpose
+                  and net_streams_push_f32 through the original sets, all timed; (b) as above.  One
+                  channel map serves every session here, which flatters (a): index_select cannot apply a
+                  map per session.
+Verified first in both: over six ticks every logit row of (new) equals (a)'s and (b)'s.  The three
+alternate within every warm-up round and every timed repeat.
+
+  python tools/bench_streams.py [--cases mmmi_64,bci_1024,bci_1024_shuffled,each_equal,each_ragged,f32_tm,f32_tm_montage]
                                 [--limit S] [--reps 1000] [--warmup 50] [--variant canonical|plain_bn]
                                 [--out-dir profiles]
 """
@@ -57,11 +72,17 @@ EACH_CASES = {  # name: (sessions, sets, C, T, N, n_max, counts drawn from 0 .. 
     "each_equal": (1024, 16, 22, 1125, 4, 16, False),
     "each_ragged": (1024, 16, 22, 1125, 4, 32, True),
 }
+F32_CASES = {  # name: (sessions, sets, C, T, N, n, source rows R): net_streams_push_f32_tm
+    "f32_tm": (1024, 16, 22, 1125, 4, 16, 22),
+    "f32_tm_montage": (1024, 16, 19, 1125, 4, 16, 64),
+}
 
 
 def run_case(name, limit, reps, warmup, variant, seed=2026):
     if name in EACH_CASES:
         return run_each(name, limit, reps, warmup, variant, seed)
+    if name in F32_CASES:
+        return run_f32(name, limit, reps, warmup, variant, seed)
     import numpy as np
     import torch
 
@@ -307,6 +328,94 @@ def run_each(name, limit, reps, warmup, variant, seed=2026):
     return res
 
 
+def run_f32(name, limit, reps, warmup, variant, seed=2026):
+    import numpy as np
+    import torch
+
+    from mibminet import lib
+    from mibminet.params import ParamSet
+
+    S, n_sets, C, T, N, n, R = F32_CASES[name]
+    S = min(S, limit)
+    n_sets = min(n_sets, S)
+    sets = [ParamSet.synthetic(seed=seed + s, C=C, T=T, N=N, reorder_bn=variant != "plain_bn") for s in range(n_sets)]
+    scales = [1.0 + 0.25 * s for s in range(n_sets)]
+    bank = lib.Bank(sets, scales)
+    montage = R != C
+    ch = sorted(int(c) for c in np.random.default_rng(seed).permutation(R)[:C]) if montage else list(range(C))
+    wide = lib.Bank([ps.widened(R, ch) for ps in sets], scales) if montage else bank
+    set_of = [int(v) for v in np.sort(np.arange(S) * n_sets // S)]
+    groups = {key: lib.Streams(wide if key == "new" else bank, set_of, HOP, n) for key in ("new", "a", "b")}
+    k = n // HOP
+    lead = T % HOP
+    fill = -(-(T - lead) // n)
+    total = lead + (fill + VERIFY) * n
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    x = torch.randn((S, total, R), dtype=torch.float32, device="cuda", generator=g)  # frames [S][t][R]
+    idx = torch.tensor(ch, dtype=torch.int64, device="cuda")
+    xtm = torch.empty((S, n, R), dtype=torch.float32, device="cuda")   # the tick's frames as delivered
+    xct = torch.empty((S, C, n), dtype=torch.float32, device="cuda")   # (a)'s and (b)'s transposed chunk
+    y = {key: torch.empty((S, k, N), dtype=torch.int8, device="cuda") for key in groups}
+    nbad = torch.zeros((1,), dtype=torch.int32, device="cuda")
+    A = lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def gather():  # what a caller does to the tick's frames at the parent commit
+        xct.copy_((xtm.index_select(2, idx) if montage else xtm).transpose(1, 2))
+
+    def new():
+        rc = A.net_streams_push_f32_tm(groups["new"].handle, xtm.data_ptr(), n, y["new"].data_ptr(), nbad.data_ptr(), stream)
+        assert rc == 0, rc
+
+    def b():
+        rc = A.net_streams_push_f32(groups["b"].handle, xct.data_ptr(), n, y["b"].data_ptr(), nbad.data_ptr(), stream)
+        assert rc == 0, rc
+
+    def a():
+        gather()
+        rc = A.net_streams_push_f32(groups["a"].handle, xct.data_ptr(), n, y["a"].data_ptr(), nbad.data_ptr(), stream)
+        assert rc == 0, rc
+
+    pos = 0
+    for m in [lead] * (lead > 0) + [n] * fill:
+        fr = x[:, pos: pos + m].contiguous()
+        groups["new"].push_f32(fr, layout="tc")
+        ct = fr.index_select(2, idx).transpose(1, 2).contiguous()
+        groups["a"].push_f32(ct)
+        groups["b"].push_f32(ct)
+        pos += m
+    assert all(st.windows(n) == k for st in groups.values())
+    mis = 0
+    for _ in range(VERIFY):
+        xtm.copy_(x[:, pos: pos + n])
+        new()
+        a()  # leaves the transposed chunk in xct for (b)
+        b()
+        pos += n
+        torch.cuda.synchronize()
+        mis += int((y["new"] != y["a"]).any(dim=2).sum().item()) + int((y["new"] != y["b"]).any(dim=2).sum().item())
+    assert int(nbad.item()) == 0
+    ms = time_alternating({"new": new, "a": a, "b": b}, reps, warmup)
+    ms["t"] = time_alternating({"t": gather}, reps, warmup)["t"]  # the extra pass alone, for the record
+    med = medians(ms)
+    info = wide.info()
+    res = {"name": name, "sessions": S, "sets": n_sets, "C": C, "source_rows": R, "T": T, "N": N, "hop": HOP, "n": n,
+           "windows_per_tick": S * k, "variant": variant, "exact_division": bool(info[4]), "verified_ticks": VERIFY,
+           "mismatched_rows": mis, "reps": reps, "warmup": warmup, "device": torch.cuda.get_device_name(0),
+           "ms_push_f32_tm": round(med["new"], 4), "ms_transpose_then_push_f32": round(med["a"], 4),
+           "ms_push_f32_alone": round(med["b"], 4), "ms_transpose_alone": round(med["t"], 4),
+           "ms_push_f32_tm_min_max": min_max(ms["new"]), "ms_transpose_then_push_f32_min_max": min_max(ms["a"]),
+           "ms_push_f32_alone_min_max": min_max(ms["b"]),
+           "new_over_a": round(med["new"] / med["a"], 4), "new_over_b": round(med["new"] / med["b"], 4),
+           "gates": {"new <= a": med["new"] <= med["a"]}, "pass": mis == 0}
+    for st in groups.values():
+        st.close()
+    if montage:
+        wide.close()
+    bank.close()
+    return res
+
+
 def b_call(A, bank, recipe, nbad, stream):
     xb, Lx, bsd, ond, W, ws, wsb, yb = recipe
     rc = A.net_model_compute_windows_bank(bank.handle, xb.data_ptr(), 1, Lx, bsd.data_ptr(), ond.data_ptr(), W, yb.data_ptr(),
@@ -316,4 +425,4 @@ def b_call(A, bank, recipe, nbad, stream):
 
 
 if __name__ == "__main__":
-    main(__doc__, {**CASES, **EACH_CASES}, run_case, "limit", "streams", lambda res: res["mismatched_rows"], reps=1000, warmup=50)
+    main(__doc__, {**CASES, **EACH_CASES, **F32_CASES}, run_case, "limit", "streams", lambda res: res["mismatched_rows"], reps=1000, warmup=50)
