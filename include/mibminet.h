@@ -644,6 +644,48 @@ int net_streams_push_each_f32_tm(net_streams_t* st, const float* x, const int32_
  * no unanswered window.  A capturing stream is refused, as for a uniform group. */
 int net_streams_positions(net_streams_t* st, int64_t* pos_out, void* stream);
 
+/* ---- live streams: windows at given onsets, read from the rings ---------------------------------
+ * The live counterpart of net_model_compute_windows_at, for cue-locked trials of a recording that is
+ * still arriving ("Cue-locked trials").  One entry serves both kinds of group.
+ * session: DEVICE int32[W], 4-byte aligned.  onsets: DEVICE int64[W], 8-byte aligned.  y: DEVICE
+ * [W][N] int8, 4-byte aligned.  n_bad: DEVICE, 4-byte aligned, or NULL; the caller zeroes it.
+ * Item w asks for the window of session session[w] whose first sample is onsets[w]: on a uniform
+ * group on the group's position axis (the one net_streams_info's position and the origins live on),
+ * on an each-group in the session's own count since its last restart.  Any order, duplicates
+ * allowed; a workgroup reloads its parameters whenever neighbouring items change sets, so sort the
+ * items by session where the order is free.
+ * Validity.  With pos the session's position when the call runs (the host's position; pos[s] in
+ * device memory for an each-group), item w is valid iff the session index, compared unsigned, is
+ * below S; the session's set is inside the bank; o >= origin[s] (each-group: o >= 0); and
+ * T <= pos - o <= cap: the window is complete and its first sample is still in the ring.  The
+ * comparisons are made in 64 bits in a form that cannot overflow, so a value whose low 32 bits
+ * alone would be valid fails.  From an invalid item no ring or parameter address is formed, its row
+ * is N zeros and *n_bad is incremented once.  The row of a valid item is byte-identical to what
+ * net_model_compute_batch_ct returns for samples o .. o+T-1 of the session with its set loaded.
+ * Retention.  A window completes in the push that takes pos to o+T or beyond; right after that push
+ * pos - o < T + n <= T + max_push <= cap, so a query enqueued after the push that completes a window
+ * always finds it, and the window stays for cap - (pos - o) more samples.  A caller who wants more
+ * slack creates the group with a larger max_push.
+ * State.  The call reads the rings, the sets, the origins and the positions and writes y and *n_bad
+ * alone: no position moves and nothing is stored into a ring.  It is ordered like a push: with
+ * respect to the group's pushes and restarts.  One kernel goes on `stream`; no host sync, no
+ * allocation.
+ * Checks, all before anything is enqueued, in this order: a NULL group, NET_ERR_INVALID; W == 0,
+ * NET_OK and nothing done; then NET_ERR_INVALID for W > INT32_MAX - 65,535, a NULL session, onsets or
+ * y, a misaligned session, onsets, y or n_bad; then, on a uniform group, NET_ERR_UNSUPPORTED for a
+ * `stream` that is capturing (the arguments are computed from the host's position).  On an
+ * each-group the call reads nothing from the host: after one eager call on the device it may be
+ * captured, as net_streams_push_each may, and a push plus a query replayed every tick read the
+ * sessions and onsets as they then are. */
+int net_streams_windows_at(net_streams_t* st, const int32_t* session, const int64_t* onsets, size_t W, int8_t* y,
+                           int32_t* n_bad, void* stream);
+
+/* Host only.  On a uniform group the onsets lo = max(pos - cap, 0) .. hi = pos - T have their window
+ * in the ring now; hi < lo: none yet.  A session's own origin applies on top of the span.
+ * NET_ERR_INVALID for a NULL group or pointer and for an each-group, whose positions are on the
+ * device (net_streams_positions; a session's span is max(pos[s] - cap, 0) .. pos[s] - T). */
+int net_streams_at_span(const net_streams_t* st, int64_t* lo, int64_t* hi);
+
 /* Several devices from one host thread (static split, no collectives): shard i is
  * x[i] / y[i] / B[i] on devices[i] (DEVICE pointers of that device).  Every shard is enqueued
  * before any is waited for, so the devices run concurrently.  streams == NULL: each device's null

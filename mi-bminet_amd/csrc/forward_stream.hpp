@@ -23,6 +23,12 @@
 // k_forward_ring_each are the two kernels above with n, p0, k and the first window's ring position
 // read per session from that record, and from nothing else: the same three launches are valid on
 // every replay of a captured graph.
+//
+// Queries (net_streams_windows_at): the window of a given session from a given sample, read out of
+// the ring as it is, for cue-locked trials.  A retained window is one contiguous run of T bytes like
+// any grid window, so k_forward_ring_at is k_forward_ring's loop over a device list of (session,
+// onset) items with AtRows as its source; it writes logits and *n_bad alone.  Which windows are
+// retained, and for how long, is stream_host.hpp's at_item.
 #pragma once
 #include "forward_bank.hpp"
 #include "stream_host.hpp"  // EachRec, plan_each: shared with the host
@@ -385,6 +391,120 @@ __global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
     __builtin_amdgcn_s_setprio(0);
     __syncthreads();  // B
     prev = i;
+  }
+}
+
+// Where the loop finds item i of a query (net_streams_windows_at): the window of session
+// session[i] whose first sample is onsets[i], read from the ring as it is.  open() reads the two
+// (wave-uniform: scalar loads, as RingRows reads origin[s]), compares the session unsigned with S
+// before anything is indexed by it, then reads set[s] and lim[s], the session's origin (a uniform
+// group, whose position pos and pos mod cap come by argument) or its position (EACH: the onset's
+// floor is 0, and pos[s] mod cap is one 64-bit remainder here, per item, beside layers 2-5 of a
+// window; a plan pass would be a second launch and S records for W items).  Validity is
+// stream::at_item, the function the host program walks; an invalid item forms no ring or parameter
+// address.  The window's first byte is at_ring(pos mod cap, pos - o), its rows win::copy_rows on
+// the view from there, row stride 2 cap, as RingRows'.
+template <bool HT, bool EACH>
+struct AtRows {
+  const int8_t* ring;
+  const int* session_of;
+  const long long* onsets;
+  const long long* lim;
+  const int* set_of;
+  const gen::GenParams* gp;
+  long long pos;
+  int pos_mod, S, cap, n_sets, T, NB1, y1s, tid;
+  int8_t* y1;
+  struct Item {
+    int session, at;  // the window's session and its first byte in the session's rows
+    bool valid;
+    int s;            // the window's set, meaningful if valid
+  };
+  __device__ __forceinline__ Item open(int i, bool more) const {
+    if (!more) return Item{0, 0, false, 0};
+    const int session = session_of[i];
+    const long long o = onsets[i];
+    if ((unsigned)session >= (unsigned)S) return Item{0, 0, false, 0};
+    const int st = set_of[session];
+    const long long l = lim[session];
+    const long long p = EACH ? l : pos;
+    const int t = HT ? T : gp->T;
+    const AtItem a = at_item(o, EACH ? 0ll : l, p, (unsigned)t, (unsigned)cap);
+    if (!a.valid || (unsigned)st >= (unsigned)n_sets) return Item{0, 0, false, 0};
+    const int pm = EACH ? (int)((unsigned long long)p % (unsigned)cap) : pos_mod;
+    return Item{session, at_ring(pm, a.d, cap), true, st};
+  }
+  __device__ __forceinline__ void rows(const Item& it) const {
+    const int t = HT ? T : gp->T;
+    if (it.valid)
+      win::copy_rows(win::window_view(ring + (size_t)it.session * (size_t)(32 * cap), it.at, t, 2 * cap), y1, y1s, t, NB1,
+                     2 * cap, tid, gen::NT - 64);
+  }
+};
+
+// k_forward_ring's loop over the W items of a query, logits [W][N].  A SIBLING OF k_forward_ring,
+// kept in step with it by hand, for the reason k_forward_ring_each gives: a body shared with it
+// changed the code generated for it (tools/asm_cmp.py).  The contiguous ranges, item i - 1 finished
+// on its own set before a switch with its two barriers, an invalid item keeps the current set and is
+// finished as zeros and a count in *n_bad, the zero pads written once.  Items are in the caller's
+// order: sorted by session a range changes sets as seldom as a push's does.  It reads the rings,
+// the sets and the origins or positions, and writes out and *n_bad alone.
+template <bool RB, bool XR, bool CB, bool EACH>
+__global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_forward_ring_at(
+    const gen::GenParams* __restrict__ sets, int n_sets, const int8_t* __restrict__ ring,
+    const int* __restrict__ session_of, const long long* __restrict__ onsets, const long long* __restrict__ lim,
+    const int* __restrict__ set_of, int8_t* __restrict__ out, int* __restrict__ n_bad, int W, int S, long long pos,
+    int pos_mod, int cap) {
+  using namespace gen;
+  extern __shared__ v4i smem_v[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // the geometry is every set's: set 0 stands for it until the first switch
+  const Lds m = lds_of(sets, (int8_t*)smem_v, 3);
+  const int N = sets->N;
+  v4i* z = (v4i*)m.y1;  // the zero pads (gen::setup); the first switch's barriers publish them
+  for (int i = tid; i < m.cv.sg / 16; i += NT) z[i] = (v4i){0, 0, 0, 0};
+  AtRows<RB || XR, EACH> src{ring, session_of, onsets, lim,     set_of,    sets,     pos, pos_mod,
+                             S,    cap,        n_sets, sets->T, sets->NB1, m.cv.y1s, tid, m.y1};
+  L2C k2;
+  const Range64 rg = range_of(blockIdx.x, gridDim.x, (unsigned long long)W);
+  const int end = (int)rg.hi;
+  int cur = -1;   // the set in registers and LDS
+  int prev = -1;  // gen::item_loop's: i valid, -2 - i invalid, -1 none
+  for (int i = (int)rg.lo;; i++) {
+    const bool more = i < end;  // uniform over the workgroup
+    const auto it = src.open(i, more);
+    const int need = it.valid ? it.s : max(cur, 0);  // an invalid item stays where the workgroup is
+    if (more && need != cur) {
+      // item i - 1 ends on its own set before any of that set's state goes
+      if (wave == NW - 1) finish_prev<RB, XR, CB, true>(src.gp, m, out, n_bad, prev, N, lane);
+      prev = -1;
+      __syncthreads();
+      cur = need;
+      src.gp = sets + cur;
+      // the reload's addresses are derived here, per switch, from an opaque copy of the thread
+      // index (bank::k_forward_ep_bank)
+      int t;
+      asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
+      set_l2c(src.gp, k2, wave, t & 63);
+      set_lds(src.gp, m, t);
+      __syncthreads();
+    }
+    const GenParams* __restrict__ gp = src.gp;
+    if (wave < NW - 1) {
+      if (more) src.rows(it);
+    } else {
+      finish_prev<RB, XR, CB, true>(gp, m, out, n_bad, prev, N, lane);
+    }
+    if (!more) break;
+    __syncthreads();  // A
+    layer2<RB, XR, CB>(gp, m.y1, m.cv.y1s, m.y2, m.cv.y2s, k2, wave, lane);
+    wg::wave_sync_lds();  // layer 3 of filter f reads only y2 row f, written by this wave
+    __builtin_amdgcn_s_setprio(wg::PRIO_L3);
+    layer3<XR, CB>(gp, m.sg, m.y2, m.cv.y2s, m.y3, wave, lane);
+    __builtin_amdgcn_s_setprio(0);
+    __syncthreads();  // B
+    prev = it.valid ? i : -2 - i;
   }
 }
 

@@ -12,7 +12,8 @@
 //   (HIP-free);
 // * bank_host.hpp: the HIP-free part of a parameter bank, the build of its images included;
 // * stream_host.hpp: the HIP-free part of a stream group: ring size, per-push arithmetic, checks,
-//   and an each-group's per-session plan, shared with its plan kernel;
+//   an each-group's per-session plan, shared with its plan kernel, and a query's validity
+//   predicate, shared with its kernel;
 // * device_state.hpp: the loaded set, the per-device image cache and the scoped launch entry;
 // * test_hooks.hpp: include/mibminet_testing.h.
 // There is no CPU compute path: without a usable HIP device every entry point returns an error.
@@ -612,6 +613,43 @@ int streams_push_each(net_streams* g, const void* x, int arg_layout, bool f32, c
   return NET_OK;
 }
 
+// net_streams_windows_at: every check comes before the one launch.  A uniform group's arguments
+// come from the host's position, so its launch is not capturable; an each-group's reads nothing from
+// the host.  Nothing of the group changes.
+int streams_windows_at(net_streams* g, const int32_t* session, const int64_t* onsets, size_t W, int8_t* y,
+                       int32_t* n_bad, void* stream) {
+  if (const int rc = stream::check_windows_at(g != nullptr, W, session, onsets, y, n_bad)) return rc;
+  if (W == 0) return NET_OK;
+  const net_bank& b = *g->bank;
+  const gen::GenParams& hg = b.sets[0];
+  DeviceScope sc(g->device, b);
+  if (sc.rc) return sc.rc;
+  const hipStream_t st = (hipStream_t)stream;
+  if (!g->each && capturing(st)) return NET_ERR_UNSUPPORTED;
+  const auto* sets = (const gen::GenParams*)sc.image;
+  const int n_sets = (int)b.sets.size();
+  const int8_t* ring = (const int8_t*)g->mem;
+  const int* set_of = (const int*)(ring + g->at.set);
+  const long long* lim = (const long long*)(ring + (g->each ? g->pos_at : g->at.origin));
+  const long long pos = g->each ? 0ll : (long long)g->pos;
+  const int pos_mod = g->each ? 0 : (int)(g->pos % g->cap);
+  return with_flags(hg, [&](auto rb, auto xr, auto cb) {
+    constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
+    auto go = [&](auto kern) {
+      return launch_items(sc.ds, kern, windows_lds(hg), W, st, sets, n_sets, ring, (const int*)session,
+                          (const long long*)onsets, lim, set_of, y, (int*)n_bad, (int)W, (int)g->S, pos, pos_mod,
+                          (int)g->cap);
+    };
+    return g->each ? go(stream::k_forward_ring_at<RB, XR, CB, true>) : go(stream::k_forward_ring_at<RB, XR, CB, false>);
+  });
+}
+
+int streams_at_span(const net_streams* g, int64_t* lo, int64_t* hi) {
+  if (!g || g->each || !lo || !hi) return NET_ERR_INVALID;
+  stream::at_span((size_t)g->bank->sets[0].T, g->cap, g->pos, lo, hi);
+  return NET_OK;
+}
+
 int streams_positions(net_streams* g, int64_t* pos_out, void* stream) {
   if (!g || !g->each || !pos_out || ((uintptr_t)pos_out & 7) != 0) return NET_ERR_INVALID;
   DeviceScope sc(g->device, *g->bank);
@@ -1016,6 +1054,13 @@ int net_streams_push_each_f32_tm(net_streams_t* st, const float* x, const int32_
 int net_streams_positions(net_streams_t* st, int64_t* pos_out, void* stream) {
   return streams_positions(st, pos_out, stream);
 }
+
+int net_streams_windows_at(net_streams_t* st, const int32_t* session, const int64_t* onsets, size_t W, int8_t* y,
+                           int32_t* n_bad, void* stream) {
+  return streams_windows_at(st, session, onsets, W, y, n_bad, stream);
+}
+
+int net_streams_at_span(const net_streams_t* st, int64_t* lo, int64_t* hi) { return streams_at_span(st, lo, hi); }
 
 int net_model_compute_batch_multi(int ndev, const int* devices, const int8_t* const* x, int8_t* const* y,
                                   const size_t* B, void* const* streams) {

@@ -3,9 +3,11 @@
 // o = j hop end in it, where they and the new samples lie in the ring, how many items the two
 // kernels take) and the argument checks of create and push; for an each-group, whose sessions have
 // a position each, the per-session plan of a push (plan_each, shared with the plan kernel of
-// forward_stream.hpp), the rows of its logits, its allocation and its checks.  HIP-free like
-// entry_host.hpp, whose windows_count it uses: included by mibminet.hip, forward_stream.hpp and two
-// stand-alone host programs (tests/stream_host_main.cpp, tests/stream_each_host_main.cpp).
+// forward_stream.hpp), the rows of its logits, its allocation and its checks; for a query
+// (net_streams_windows_at) which windows a ring still holds and where (at_item, shared with
+// k_forward_ring_at), the span and the checks.  HIP-free like entry_host.hpp, whose windows_count it
+// uses: included by mibminet.hip, forward_stream.hpp and three stand-alone host programs
+// (tests/stream_host_main.cpp, tests/stream_each_host_main.cpp, tests/stream_at_host_main.cpp).
 //
 // The ring.  A session's ring holds the layer-1 output of its last cap samples, sample t at position
 // t mod cap (and again at t mod cap + cap, forward_stream.hpp).  A push of n samples at position p0
@@ -206,6 +208,63 @@ inline int check_push_each(size_t S, size_t hop, size_t max_push, const void* x,
   g.blocks = (n_max + 15) / 16;
   g.l1_items = S * g.blocks;
   g.items = S * g.kmax;
+  return NET_OK;
+}
+
+// ---- windows at given onsets (net_streams_windows_at) -----------------------------------------
+// A query asks for the window of a session whose first sample is o, read from the ring as it is.
+// With pos the session's position (0 <= pos <= INT64_MAX) and lo the first sample a window of it may
+// read (its origin, >= 0; 0 for an each-group), the window is there iff o >= lo and
+// T <= pos - o <= cap: complete, and its first sample not yet overwritten.
+//
+// Retention.  A window completes in the push that takes pos to o + T or beyond.  That push had
+// n <= max_push samples and started below o + T, so right after it pos - o < T + n <= T + max_push
+// <= cap: a query enqueued after the push that completes a window always finds it, and the window
+// stays for cap - (pos - o) more samples.
+
+// What a valid query reads: d = pos - o, in T .. cap.
+struct AtItem {
+  bool valid;
+  unsigned d;
+};
+
+// The predicate, shared by k_forward_ring_at and the host (tests/stream_at_host_main.cpp).  In 64
+// bits, in a form that cannot overflow: o >= 0 first, then o <= pos, then the difference of two
+// non-negative values, compared unsigned with T and cap.  A value whose low 32 bits alone would pass
+// fails.  pos < 0 (no session has one) fails every o.
+MIB_HD inline AtItem at_item(long long o, long long lo, long long pos, unsigned T, unsigned cap) {
+  if (o < 0 || o < lo || o > pos) return AtItem{false, 0};
+  const unsigned long long d = (unsigned long long)pos - (unsigned long long)o;
+  if (d < T || d > cap) return AtItem{false, 0};
+  return AtItem{true, (unsigned)d};
+}
+
+// The ring position of the first byte of a valid query, (pos mod cap - d) mod cap: pos_mod < cap and
+// T <= d <= cap, so the difference is in -cap .. cap - 1 and one conditional correction does.
+MIB_HD inline int at_ring(int pos_mod, unsigned d, int cap) {
+  const int at = pos_mod - (int)d;
+  return at < 0 ? at + cap : at;
+}
+
+// net_streams_at_span on a uniform group at position pos: the onsets lo .. hi have their window in
+// the ring (hi < lo: none yet); a session's origin applies on top.
+inline void at_span(size_t T, size_t cap, uint64_t pos, int64_t* lo, int64_t* hi) {
+  *lo = pos > cap ? (int64_t)(pos - cap) : 0;
+  *hi = (int64_t)pos - (int64_t)T;  // pos <= INT64_MAX (check_push), T < 2^31
+}
+
+// The checks of net_streams_windows_at in their documented order; W == 0 is NET_OK with nothing to
+// do (the caller returns before it looks further).  A uniform group's capturing stream comes after
+// them.
+inline int check_windows_at(bool have_group, size_t W, const void* session, const void* onsets, const void* y,
+                            const void* n_bad) {
+  if (!have_group) return NET_ERR_INVALID;
+  if (W == 0) return NET_OK;
+  if (W > MAX_ITEMS) return NET_ERR_INVALID;
+  if (!session || !onsets || !y) return NET_ERR_INVALID;
+  if (((uintptr_t)session & 3) != 0 || ((uintptr_t)onsets & 7) != 0 || ((uintptr_t)y & 3) != 0 ||
+      ((uintptr_t)n_bad & 3) != 0)
+    return NET_ERR_INVALID;
   return NET_OK;
 }
 

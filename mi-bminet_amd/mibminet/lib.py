@@ -94,6 +94,8 @@ PROTOTYPES = {
     "net_streams_push_each_f32": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr, ptr, ptr)",
     "net_streams_push_each_f32_tm": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr, ptr, ptr)",
     "net_streams_positions": "int (ptr, ptr, ptr)",
+    "net_streams_windows_at": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr)",
+    "net_streams_at_span": "int (ptr, ptr, ptr)",
     "net_model_compute_batch_multi": "int (int, ptr, ptr, ptr, ptr, ptr)",
     "net_model_compute_batch_multi_ct": "int (int, ptr, ptr, ptr, ptr, ptr)",
     "net_quantize_input_f32": "int (ptr, ptr, size_t, int, int, float, int, ptr)",
@@ -1038,6 +1040,39 @@ def forward_windows_multi_bank_torch(bank, recordings, sets, hop: int, layout: s
         return _stitch(net, tensors[0], out), first
 
 
+def _streams_windows_at(group, sessions, onsets, stream, out, check: bool):
+    """net_streams_windows_at on ``group`` (a Streams or a StreamsEach): the windows of sessions
+    ``sessions[w]`` that start at samples ``onsets[w]``, read from the layer-1 rings as they are.  The
+    lists are device tensors (int32 and int64, 1-D) or sequences of ints, through _index_list; their
+    device copies and the zeroed counter are made on the launch stream.  ``check`` is
+    forward_windows_at_torch's: the stream is synchronised, the count of invalid items read back and
+    a ValueError raised if it is not zero; ``check=False`` passes NULL for the counter.  Returns the
+    logits [W][N]."""
+    torch = _torch()
+    ses = _index_list(sessions, torch.int32, "sessions")
+    ons = _index_list(onsets, torch.int64, "onsets")
+    W, N = int(ses.numel()), group.bank.dims.N
+    if int(ons.numel()) != W:
+        raise ValueError(f"{W} sessions for {int(ons.numel())} onsets")
+    dev = torch.device("cuda", group.device)
+    s = torch.cuda.current_stream(group.device) if stream is None else stream
+    with torch.cuda.stream(s):  # the lists' copies and the counter's zeroing precede the launch on its stream
+        ses, ons = ses.to(dev).contiguous(), ons.to(dev).contiguous()
+        nbad = torch.zeros((1,), dtype=torch.int32, device=dev) if check else None
+        if out is None:
+            out = torch.empty((W, N), dtype=torch.int8, device=dev)
+    _check_tensor(out, "out", ("int8",), (W, N))
+    _check(load().net_streams_windows_at(group.handle, ses.data_ptr() if W else None, ons.data_ptr() if W else None, W,
+                                         out.data_ptr() if W else None, nbad.data_ptr() if check else None,
+                                         s.cuda_stream), "net_streams_windows_at")
+    if check and W:
+        s.synchronize()
+        bad = int(nbad.item())
+        if bad:
+            raise ValueError(f"{bad} of {W} windows are not in the rings (their logit rows are zero)")
+    return out
+
+
 class Streams:
     """net_streams_create: ``len(sets)`` live sessions of ``bank``'s geometry on ``device``, session i
     decoded by set ``sets[i]`` (``sets`` an int: that many sessions under set 0), windows at every
@@ -1122,6 +1157,26 @@ class Streams:
         _check_tensor(x, "x", ("float32",), (self.S, C, "n") if layout == "ct" else (self.S, "n", C))
         return self._push(x, "_f32" if layout == "ct" else "_f32_tm", (), int(x.shape[2 if layout == "ct" else 1]), stream,
                           out)
+
+    def windows_at(self, sessions, onsets, stream=None, out=None, check: bool = True):
+        """net_streams_windows_at: the windows of sessions ``sessions[w]`` whose first samples are
+        ``onsets[w]`` on the group's position axis, read from the rings as they are (cue-locked
+        trials).  Device tensors (int32, int64) or sequences of ints, any order, duplicates allowed;
+        sorted by session the call reloads parameters least.  Returns the logits [W][N] int8, row w
+        what forward_ct_torch returns for samples onsets[w] .. + T - 1 of the session with its set
+        loaded.  A window that is not complete, no longer in the ring (see ``at_span``), from before
+        the session's origin, or of a session outside the group gives a zero row; with ``check``
+        their count is read back (a host sync) and a ValueError names it.  ``out``: an int8 device
+        tensor [W][N] to write instead.  Ordered like a push; moves nothing."""
+        return _streams_windows_at(self, sessions, onsets, stream, out, check)
+
+    def at_span(self) -> tuple:
+        """net_streams_at_span: (lo, hi), the onsets whose windows are in the rings now, lo =
+        max(position - cap, 0) and hi = position - T; hi < lo: none yet.  A session's origin applies
+        on top."""
+        lo, hi = ctypes.c_int64(0), ctypes.c_int64(0)
+        _check(load().net_streams_at_span(self.handle, ctypes.byref(lo), ctypes.byref(hi)), "net_streams_at_span")
+        return lo.value, hi.value
 
     def restart(self, i: int, set: int, stream=None) -> None:
         """net_streams_restart: from the next push session ``i`` is decoded by ``set`` and answers no
@@ -1247,6 +1302,13 @@ class StreamsEach:
         _check_tensor(x, "x", ("float32",), (self.S, C, "n") if layout == "ct" else (self.S, "n", C))
         return self._push(x, "_f32" if layout == "ct" else "_f32_tm", (), int(x.shape[2 if layout == "ct" else 1]), counts,
                           stream, out)
+
+    def windows_at(self, sessions, onsets, stream=None, out=None, check: bool = True):
+        """net_streams_windows_at on an each-group: Streams.windows_at with every onset in its
+        session's own count since its last restart; a session's span is max(pos - cap, 0) ..
+        pos - T of its position (``positions()``).  With device tensors and ``check=False`` the call
+        reads nothing from the host and, after one eager call, may be captured behind a push."""
+        return _streams_windows_at(self, sessions, onsets, stream, out, check)
 
     def restart(self, i: int, set: int, stream=None) -> None:
         """net_streams_restart on an each-group: session ``i`` starts again at position 0 under

@@ -52,7 +52,21 @@ hop 8, n 16, each candidate with a stream group of its own fed the same samples:
 Verified first in both: over six ticks every logit row of (new) equals (a)'s and (b)'s.  The three
 alternate within every warm-up round and every timed repeat.
 
-  python tools/bench_streams.py [--cases mmmi_64,bci_1024,bci_1024_shuffled,each_equal,each_ragged,f32_tm,f32_tm_montage]
+Cue-locked trials of live sessions (net_streams_windows_at), 1,024 sessions of 22 x 1125 under 16
+grouped sets, hop 8, n 16:
+  at_cues         Every tick is a push followed by one query per session, at an onset drawn uniformly
+                  inside the session's span of cap - T + 1 onsets, the items sorted by session.  (new)
+                  net_streams_windows_at: layers 2-5 on rows read out of the rings; (b) what a caller ran
+                  before: net_model_compute_epochs_bank on the same onsets over a raw-sample array
+                  [S][C][cap] of every session's last cap samples, which runs layer 1 on T samples per
+                  window.  The array is prepared outside the timed region, which flatters (b): a caller
+                  rewrites it every tick.  (g) a hop-1 group's grid rows cover a cue only at hop times
+                  the layers 2-5 work of every push, for windows nobody reads: said, not timed.
+                  Verified first: over six ticks every row of (new) equals (b)'s.  Then per tick the push
+                  is timed on its own and (new) and (b) take turns going first; the only claim is
+                  new <= b on the medians.
+
+  python tools/bench_streams.py [--cases mmmi_64,bci_1024,bci_1024_shuffled,each_equal,each_ragged,f32_tm,f32_tm_montage,at_cues]
                                 [--limit S] [--reps 1000] [--warmup 50] [--variant canonical|plain_bn]
                                 [--out-dir profiles]
 """
@@ -78,7 +92,14 @@ F32_CASES = {  # name: (sessions, sets, C, T, N, n, source rows R): net_streams_
 }
 
 
+AT_CASES = {  # name: (sessions, sets, C, T, N, n): net_streams_windows_at
+    "at_cues": (1024, 16, 22, 1125, 4, 16),
+}
+
+
 def run_case(name, limit, reps, warmup, variant, seed=2026):
+    if name in AT_CASES:
+        return run_at(name, limit, reps, warmup, variant, seed)
     if name in EACH_CASES:
         return run_each(name, limit, reps, warmup, variant, seed)
     if name in F32_CASES:
@@ -416,6 +437,112 @@ def run_f32(name, limit, reps, warmup, variant, seed=2026):
     return res
 
 
+def run_at(name, limit, reps, warmup, variant, seed=2026):
+    import numpy as np
+    import torch
+
+    from mibminet import lib
+    from mibminet.params import ParamSet
+
+    S, n_sets, C, T, N, n = AT_CASES[name]
+    S = min(S, limit)
+    n_sets = min(n_sets, S)
+    sets = [ParamSet.synthetic(seed=seed + s, C=C, T=T, N=N, reorder_bn=variant != "plain_bn") for s in range(n_sets)]
+    bank = lib.Bank(sets)
+    set_of = [int(v) for v in np.sort(np.arange(S) * n_sets // S)]  # grouped: the queries are sorted by session
+    st = lib.Streams(bank, set_of, HOP, n)
+    cap = st.cap
+    fill = -(-cap // n)  # pushes until the ring is full, so that every span is cap - T + 1 onsets
+    total = (fill + VERIFY) * n
+    rng = np.random.default_rng(seed)
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    x = torch.randint(-128, 128, (S, C, total), dtype=torch.int8, device="cuda", generator=g)
+    A = lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    xa = x[:, :, :n].contiguous()
+    k = n // HOP
+    yp = torch.empty((S, max(k, 1), N), dtype=torch.int8, device="cuda")
+    yn, yb = (torch.empty((S, N), dtype=torch.int8, device="cuda") for _ in range(2))
+    ses = torch.arange(S, dtype=torch.int32, device="cuda")
+    sod = torch.tensor(set_of, dtype=torch.int32, device="cuda")
+    ons = torch.zeros((S,), dtype=torch.int64, device="cuda")  # (new)'s: on the group's position axis
+    onb = torch.zeros((S,), dtype=torch.int64, device="cuda")  # (b)'s: flat element indices of raw
+    raw = torch.zeros((S, C, cap), dtype=torch.int8, device="cuda")  # (b): the last cap samples of every session
+    nbad = torch.zeros((1,), dtype=torch.int32, device="cuda")
+
+    def p():
+        rc = A.net_streams_push(st.handle, xa.data_ptr(), 1, n, yp.data_ptr(), nbad.data_ptr(), stream)
+        assert rc == 0, rc
+
+    def new():
+        rc = A.net_streams_windows_at(st.handle, ses.data_ptr(), ons.data_ptr(), S, yn.data_ptr(), nbad.data_ptr(), stream)
+        assert rc == 0, rc
+
+    def b():
+        rc = A.net_model_compute_epochs_bank(bank.handle, raw.data_ptr(), S * C * cap, cap, None, onb.data_ptr(), sod.data_ptr(),
+                                             S, yb.data_ptr(), nbad.data_ptr(), 0, stream)
+        assert rc == 0, rc
+
+    def draw(pos):
+        """One cue per session inside its span; (b)'s onsets address the same samples in raw."""
+        rel = rng.integers(0, cap - T + 1, size=S)
+        ons.copy_(torch.from_numpy(rel + (pos - cap)))
+        onb.copy_(torch.from_numpy(rel + np.arange(S, dtype=np.int64) * (C * cap)))
+
+    pos = 0
+    for _ in range(fill):
+        st.push(x[:, :, pos: pos + n].contiguous())
+        pos += n
+    mis = 0
+    for _ in range(VERIFY):
+        xa.copy_(x[:, :, pos: pos + n])
+        p()
+        pos += n
+        raw.copy_(x[:, :, pos - cap: pos])
+        draw(pos)
+        new()
+        b()
+        torch.cuda.synchronize()
+        mis += int((yn != yb).any(dim=1).sum().item())
+    assert int(nbad.item()) == 0 and st.at_span() == (pos - cap, pos - T)
+    # every timed tick: a push (timed on its own), the cues moved along with the position, then (new) and (b),
+    # which take turns going first; raw stays as it is, which flatters (b): a caller rewrites it every tick
+    ms = {"p": [], "new": [], "b": []}
+
+    def timed(key, fn, keep):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        if keep:
+            ms[key].append(e0.elapsed_time(e1))
+
+    for r in range(warmup + reps):
+        keep = r >= warmup
+        timed("p", p, keep)
+        ons.add_(n)
+        for key in (("new", "b") if r % 2 else ("b", "new")):
+            timed(key, new if key == "new" else b, keep)
+    torch.cuda.synchronize()
+    assert int(nbad.item()) == 0  # every timed query was valid
+    med = medians(ms)
+    info = bank.info()
+    res = {"name": name, "sessions": S, "sets": n_sets, "C": C, "T": T, "N": N, "hop": HOP, "n": n, "queries_per_tick": S,
+           "ring_samples": cap, "onsets": "one per session, uniform in its span of cap - T + 1, sorted by session",
+           "variant": variant, "exact_division": bool(info[4]), "verified_ticks": VERIFY, "mismatched_rows": mis,
+           "reps": reps, "warmup": warmup, "device": torch.cuda.get_device_name(0),
+           "ms_windows_at": round(med["new"], 4), "ms_epochs_bank_on_raw": round(med["b"], 4), "ms_push": round(med["p"], 4),
+           "ms_windows_at_min_max": min_max(ms["new"]), "ms_epochs_bank_on_raw_min_max": min_max(ms["b"]),
+           "ms_push_min_max": min_max(ms["p"]), "new_over_b": round(med["new"] / med["b"], 4),
+           "layer1_samples_b_over_new": "T per window against none (the ring holds them)",
+           "not_timed": "(g) a hop-1 group: its grid covers every cue, at hop times the layers 2-5 work per push",
+           "gates": {"new <= b": med["new"] <= med["b"]}, "pass": mis == 0}
+    st.close()
+    bank.close()
+    return res
+
+
 def b_call(A, bank, recipe, nbad, stream):
     xb, Lx, bsd, ond, W, ws, wsb, yb = recipe
     rc = A.net_model_compute_windows_bank(bank.handle, xb.data_ptr(), 1, Lx, bsd.data_ptr(), ond.data_ptr(), W, yb.data_ptr(),
@@ -425,4 +552,4 @@ def b_call(A, bank, recipe, nbad, stream):
 
 
 if __name__ == "__main__":
-    main(__doc__, {**CASES, **EACH_CASES, **F32_CASES}, run_case, "limit", "streams", lambda res: res["mismatched_rows"], reps=1000, warmup=50)
+    main(__doc__, {**CASES, **EACH_CASES, **F32_CASES, **AT_CASES}, run_case, "limit", "streams", lambda res: res["mismatched_rows"], reps=1000, warmup=50)
