@@ -362,9 +362,11 @@ int net_model_compute_epochs_f32(const float* x, size_t n_elems, size_t row_stri
                                  int device, void* stream);
 
 /* ---- parameter banks: many networks resident, one set index per epoch -------------------------
- * A bank is an immutable collection of parameter sets of one geometry (per-subject, per-fold or
- * per-repeat models), resident on the device side by side; the epochs-bank entries classify epoch e
- * with set set_of[e], all in one launch ("Many networks in one call").  A bank is
+ * A bank is a collection of parameter sets of one geometry (per-subject, per-fold or per-repeat
+ * models), resident on the device side by side; the epochs-bank entries classify epoch e with set
+ * set_of[e], all in one launch ("Many networks in one call").  Its number of sets,
+ * geometry, build variant and kernel form are fixed at creation; one set at a time may be replaced
+ * in stream order (net_bank_replace).  A bank is
  * independent of the loaded set: creating, using and destroying one leaves the set net_params_load
  * installed, net_params_info and the devices' copies of loaded sets as they were, and the bank
  * entries need no loaded set. */
@@ -395,6 +397,58 @@ int net_bank_info(const net_bank_t* bank, int32_t* info);
  * graph that captured a call on it afterwards, is the caller's error. */
 void net_bank_destroy(net_bank_t* bank);
 
+/* A refitted network goes into service: set `set` of a resident bank becomes the network of `blob`
+ * (a HOST net_params_load blob of `len` bytes), ordered on `stream`.  The calls on the bank enqueued
+ * on `stream` before it read the old set, those enqueued on it after it the new one; every other set,
+ * and every stream group on the bank, stays as it is ("Recalibrating a live
+ * decoder").  Calls on OTHER streams that may run while the copy does must be ordered with it by the
+ * caller (events): unordered, they may read a slot half written.
+ * The blob goes through net_params_load's checks like a blob of net_bank_create and must agree with
+ * what the bank was CREATED with on C, T, N, the REORDER_BN flag and the clip, not with whatever set
+ * 0 is now: set 0 is replaceable like any other.  The new image is byte-identical to the one that
+ * slot has in a bank freshly created with the new list of blobs (as long as that list still makes a
+ * bank of the same kernel form).  Exact division: a bank that runs the exact-division form
+ * (net_bank_info) takes a float set in that form.  A bank that runs the float form REFUSES a set
+ * that needs exact division: promoting the resident sets would change the kernel under calls in
+ * flight.  Remedy: if such sets may arrive, create the bank with one set that needs exact division.
+ * scale: the set's input-quantiser scale, checked and installed iff the bank was created with
+ * scales; ignored otherwise.
+ * device: the device whose copy of the bank is updated.  If it holds one, the slot (the image and
+ * the scale entry) is overwritten by copies enqueued on `stream` out of a pinned buffer the bank
+ * keeps: the call may return before the device has the bytes, and the caller may free the blob and
+ * replace the same slot again right away (the later call wins).  If no device holds a copy yet,
+ * only the host master changes, `stream` is not looked at, and each device receives the new bank on
+ * its first call as usual.  A bank with a copy on any device other than `device` is refused:
+ * replacing across several devices is not part of this entry.
+ * Checks, all before anything changes, in this order: NET_ERR_INVALID for a NULL bank,
+ * set >= n_sets, a NULL blob or a device outside the library's range; the blob's own code
+ * (NET_ERR_BLOB, NET_ERR_RANGE, NET_ERR_UNSUPPORTED); NET_ERR_UNSUPPORTED for a disagreement with
+ * the bank's geometry or variant, and for the exact-division case above; NET_ERR_INVALID or
+ * NET_ERR_RANGE for a bad scale (bank with scales); NET_ERR_UNSUPPORTED for a `stream` that is
+ * capturing (host data is copied; asked where the device holds a copy); NET_ERR_UNSUPPORTED for a
+ * copy on another device.  A refused call leaves the master, every copy and every result exactly as
+ * they were.  A HIP error of a copy (NET_ERR_HIP and below) is no refusal: the device's slot may
+ * then be partly written while the master is unchanged; replace the slot again or destroy the bank.
+ * HIP graphs: a bank or stream call captured earlier reads the bank's copy when it REPLAYS, so after
+ * a replacement it decodes under the new set without recapture.
+ * Stream groups: a session's ring holds layer-1 outputs of the set that was there.  After replacing
+ * a set, call net_streams_restart(st, i, set, stream) for every session i under it.  The exception
+ * is a new set whose layer 1 is the old one's (a refitted head, or new layers 2-5): then nothing
+ * need be done, and every later row, windows that began before the replacement included, is exact
+ * under the new set.  Without a restart the rows are still defined: layers 2-5 of the new set over
+ * the ring as it is.
+ * Host threads: the call may run while other threads enqueue calls on the bank; two replacements of
+ * one bank are serialised.  No allocation after the first replacement on a device whose earlier
+ * copies have finished; no host sync.
+ * Out of scope: promoting a resident float bank to the exact-division form, a bank resident on
+ * several devices, growing a bank's set count. */
+int net_bank_replace(net_bank_t* bank, size_t set, const void* blob, size_t len, float scale, int device,
+                     void* stream);
+
+/* Bytes of one item's layer-4 feature row, 16 * (T / 64): what the _feat entries below write per
+ * item.  0 for a NULL bank. */
+size_t net_bank_feature_bytes(const net_bank_t* bank);
+
 /* net_model_compute_epochs with the network chosen per epoch: x, n_elems, row_stride, channels,
  * onsets, E, y, n_bad, device and stream are that entry's, with C and T the bank's, and so are the
  * checks and their order (a NULL bank, NET_ERR_INVALID, stands where NET_ERR_NO_PARAMS does).
@@ -419,6 +473,24 @@ int net_model_compute_epochs_bank(const net_bank_t* bank, const int8_t* x, size_
 int net_model_compute_epochs_bank_f32(const net_bank_t* bank, const float* x, size_t n_elems, size_t row_stride,
                                       const int32_t* channels, const int64_t* onsets, const int32_t* set_of, size_t E,
                                       int8_t* y, int32_t* n_bad, int device, void* stream);
+
+/* The two entries above with the layer-4 activations beside the logits: what a head refit (layer 5
+ * over 16 x T/64 features) reads, for calibration epochs where they lie (INTEGRATION.md,
+ * "Recalibrating a live decoder").  feat: DEVICE [E][16][T64] int8, T64 = T / 64
+ * (net_bank_feature_bytes per row), 16-BYTE ALIGNED.  Row e is the reference's net_layer4 output of
+ * epoch e under set set_of[e] with the T64_ALIGN pad columns dropped: feat[e][k][v] =
+ * layer4[k][v], v < T64, the bytes layer 5 multiplies.  An invalid epoch (onset or set index) gets
+ * a zero feature row as it gets a zero logit row, and is counted once.  The logits are
+ * byte-identical to the plain entry's, and everything else of its contract carries over: the
+ * checks and their order, with NET_ERR_INVALID for a NULL feat with E > 0 or a feat that is not
+ * 16-byte aligned standing beside y's check; one kernel, no allocation, no host sync, capturable.
+ * Features from the other entries (batched, windows, pushes) are out of scope. */
+int net_model_compute_epochs_bank_feat(const net_bank_t* bank, const int8_t* x, size_t n_elems, size_t row_stride,
+                                       const int32_t* channels, const int64_t* onsets, const int32_t* set_of, size_t E,
+                                       int8_t* y, int8_t* feat, int32_t* n_bad, int device, void* stream);
+int net_model_compute_epochs_bank_feat_f32(const net_bank_t* bank, const float* x, size_t n_elems, size_t row_stride,
+                                           const int32_t* channels, const int64_t* onsets, const int32_t* set_of,
+                                           size_t E, int8_t* y, int8_t* feat, int32_t* n_bad, int device, void* stream);
 
 /* ---- windows through a bank: many recordings, each with its own network ----------------------
  * The windows-at entries with the network chosen per recording.  R recordings lie along time in one
@@ -679,6 +751,16 @@ int net_streams_positions(net_streams_t* st, int64_t* pos_out, void* stream);
  * sessions and onsets as they then are. */
 int net_streams_windows_at(net_streams_t* st, const int32_t* session, const int64_t* onsets, size_t W, int8_t* y,
                            int32_t* n_bad, void* stream);
+
+/* net_streams_windows_at with the layer-4 activations beside the logits, for the cue-locked trials
+ * of a live session that a recalibration refits on.  feat: DEVICE [W][16][T64] int8, 16-byte
+ * aligned, row w as net_model_compute_epochs_bank_feat defines it for item w under its session's
+ * set; an invalid item gets a zero feature row beside its zero logit row and is counted once.  The
+ * logits are byte-identical to net_streams_windows_at's and the rest of its contract carries over
+ * (state, ordering, one kernel, capturability on an each-group).  Checks: that entry's, with
+ * NET_ERR_INVALID for a NULL or misaligned feat after y's and before the capturing stream's. */
+int net_streams_windows_at_feat(net_streams_t* st, const int32_t* session, const int64_t* onsets, size_t W, int8_t* y,
+                                int8_t* feat, int32_t* n_bad, void* stream);
 
 /* Host only.  On a uniform group the onsets lo = max(pos - cap, 0) .. hi = pos - T have their window
  * in the ring now; hi < lo: none yet.  A session's own origin applies on top of the span.

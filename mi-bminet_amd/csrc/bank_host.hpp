@@ -1,11 +1,13 @@
 // bank_host.hpp — the HIP-free part of a parameter bank (net_bank_create, include/mibminet.h): which
 // sets may share a bank, the exact-division form every slice of a mixed bank takes, the images of
-// a bank built from its blobs (bank::build: all of net_bank_create but the allocation), the
-// partition of an item list over the workgroups of bank::bank_loop (forward_bank.hpp), and the
+// a bank built from its blobs (bank::build: all of net_bank_create but the allocation), the image
+// of a set that replaces one of a resident bank (bank::replace_set: all of net_bank_replace but the
+// locking and the copy), the partition of an item list over the workgroups of bank::bank_loop (forward_bank.hpp), and the
 // layout and lists of many recordings' windows (net_bank_windows_starts, net_bank_windows_lists).
 // HIP-free like params_host.hpp, entry_host.hpp (whose windows_count the lists use) and images.hpp:
 // included by mibminet.hip and the stand-alone host programs (tests/bank_host_main.cpp,
-// tests/windows_bank_host_main.cpp); forward_bank.hpp includes it for range_of alone.
+// tests/bank_replace_host_main.cpp, tests/windows_bank_host_main.cpp); forward_bank.hpp includes it
+// for range_of alone.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -63,12 +65,33 @@ inline int bank_set_exact(const HostParams& hp, gen::GenParams& gp) {
   return build_genparams(hp, pl, gp);
 }
 
+// What a bank was created with, kept for the sets that replace one of its own later
+// (net_bank_replace): the geometry and build variant every set agreed on, the form its kernels run
+// (exact division iff some set needed it at creation), how its images were built and whether it has
+// scales.  It never changes: a set that replaces set 0 is held to it like any other.
+struct Record {
+  Dims d;
+  bool reorder_bn = true, clip_balanced = false;
+  bool xr = false;
+  bool force_general = false;
+  bool has_scales = false;
+};
+inline bool agree(const Record& r, const HostParams& b) {
+  HostParams a;
+  a.d = r.d;
+  a.reorder_bn = r.reorder_bn;
+  a.clip_balanced = r.clip_balanced;
+  return agree(a, b);
+}
+
 // The images of a bank of n_sets blobs (scales: one per set, or null), in order: each set parsed and
 // built as bank_set does, held to set 0 (agree), its scale checked; then, where some sets need exact
 // division and others do not, the others promoted (bank_set_exact).  Returns the first error, *failed
-// (if non-null) the set it belongs to; sets and scales then hold nothing a caller may use.
+// (if non-null) the set it belongs to; sets and scales then hold nothing a caller may use.  *rec (if
+// non-null) is the bank's creation record.
 inline int build(const void* const* blobs, const size_t* sizes, const float* scales, size_t n_sets, bool force_general,
-                 std::vector<gen::GenParams>& sets, std::vector<Scale>& out_scales, size_t* failed) {
+                 std::vector<gen::GenParams>& sets, std::vector<Scale>& out_scales, size_t* failed,
+                 Record* rec = nullptr) {
   auto fail = [&](size_t i, int rc) {
     if (failed) *failed = i;
     return rc;
@@ -92,6 +115,32 @@ inline int build(const void* const* blobs, const size_t* sizes, const float* sca
     for (size_t i = 0; i < n_sets; i++)
       if (!sets[i].xr)
         if (const int rc = bank_set_exact(hps[i], sets[i])) return fail(i, rc);
+  if (rec) *rec = Record{hps[0].d, hps[0].reorder_bn, hps[0].clip_balanced, any_xr, force_general, scales != nullptr};
+  return NET_OK;
+}
+
+// The decision of net_bank_replace: the image (and, for a bank with scales, the scale entry) that
+// `blob` with `scale` gets as a set of the bank created with `rec`, or why it cannot be one.  The blob
+// goes through the loader's path as in bank_set and comes back with its own code if that refuses it;
+// it must agree with the record (NET_ERR_UNSUPPORTED), not with whatever set 0 is now.  A bank that
+// runs the exact-division form takes a float set in that form (bank_set_exact); a bank that runs the
+// float form refuses a set that needs exact division (NET_ERR_UNSUPPORTED): promoting the resident
+// sets would change the kernel instantiation under calls in flight.  The scale is checked and given
+// its reciprocal iff the bank has scales, and ignored otherwise (sc then {0, 0}).  The result is what
+// bank::build gives that slot in a bank created with the new list.  On an error gp and sc hold
+// nothing a caller may use.
+inline int replace_set(const Record& rec, const void* blob, size_t len, float scale, gen::GenParams& gp, Scale& sc) {
+  HostParams hp;
+  if (const int rc = bank_set(blob, len, rec.force_general, hp, gp)) return rc;
+  if (!agree(rec, hp)) return NET_ERR_UNSUPPORTED;
+  if (gp.xr && !rec.xr) return NET_ERR_UNSUPPORTED;
+  if (!gp.xr && rec.xr)
+    if (const int rc = bank_set_exact(hp, gp)) return rc;
+  sc = Scale{0.0f, 0.0f};
+  if (rec.has_scales) {
+    if (const int rc = check_scale(scale)) return rc;
+    sc = Scale{scale, recip_scale(scale)};
+  }
   return NET_OK;
 }
 

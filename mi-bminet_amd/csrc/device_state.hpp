@@ -11,19 +11,27 @@
 #include <utility>
 #include <vector>
 
+#include "bank_host.hpp"     // bank::Record
 #include "entry_host.hpp"    // MAX_DEVICES
 #include "image_layout.hpp"  // gen::GenParams, bank::Scale
 #include "images.hpp"        // Image
 
-// A parameter bank (net_bank_t, include/mibminet.h): the images of its sets, immutable after
-// net_bank_create, and one device copy per device that has run a call on it.  A copy is the n_sets
-// images followed, for a bank with scales, by n_sets bank::Scale entries.  Banks live beside the
-// loaded set, not in it: nothing here touches g_set or a device's image cache.
+// A parameter bank (net_bank_t, include/mibminet.h): the images of its sets (the host master) and
+// one device copy per device that has run a call on it.  A copy is the n_sets images followed, for a
+// bank with scales, by n_sets bank::Scale entries.  net_bank_replace changes one slot of the master
+// and of a device's copy; what it never changes is rec, the number of sets and the head of every
+// image (the geometry and flags before gen::GenParams::l3_m, which the record fixes), so the
+// launching calls read those of sets[0] without the lock.  Banks live beside the loaded set, not in
+// it: nothing here touches g_set or a device's image cache.
 struct net_bank {
   std::vector<mib::gen::GenParams> sets;
   std::vector<mib::bank::Scale> scales;  // empty: created without scales
-  mutable std::mutex mu;                           // guards dev
-  mutable std::vector<std::pair<int, void*>> dev;  // (device, its copy): the one part a call changes
+  mib::bank::Record rec;                 // what the bank was created with
+  mutable std::mutex mu;                           // guards dev, staging and the slots' bodies
+  mutable std::vector<std::pair<int, void*>> dev;  // (device, its copy)
+  // net_bank_replace's pinned sources (one image and one scale entry each) with the event recorded
+  // behind the copies that read them: a buffer is used again once its event has completed
+  std::vector<std::pair<void*, hipEvent_t>> staging;
 };
 
 namespace mib {

@@ -47,6 +47,12 @@ inline int check_scale(float qs) {
   return qs >= 0x1p-60f && qs <= 0x1p60f ? NET_OK : NET_ERR_RANGE;
 }
 
+// The feature buffer of a _feat entry (DEVICE [items][16][T64] int8): there where there are items,
+// and 16-byte aligned, because an item's 16 T64 bytes leave the kernel in 16-byte pieces.
+inline int check_feat(size_t items, const void* feat) {
+  return (items && !feat) || ((uintptr_t)feat & 15) != 0 ? NET_ERR_INVALID : NET_OK;
+}
+
 inline size_t trial_stride(const Dims& d) { return ((size_t)d.C * d.T + 15) / 16 * 16; }
 
 // ---- sliding windows over a recording (forward_win.hpp) --------------------------------------

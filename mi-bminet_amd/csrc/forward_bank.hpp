@@ -1,5 +1,6 @@
 // forward_bank.hpp — epochs classified by many resident networks in one launch (gfx950):
-// net_model_compute_epochs_bank[_f32], include/mibminet.h.  A bank is an array of gen::GenParams
+// net_model_compute_epochs_bank[_f32] and, with the layer-4 activations beside the logits,
+// net_model_compute_epochs_bank_feat[_f32], include/mibminet.h.  A bank is an array of gen::GenParams
 // images of one geometry; epoch e is classified by image set_of[e].
 //
 // The fetch is ep::Epochs and the layers are gen::'s, as in ep::k_forward_ep.  The persistent loop
@@ -116,6 +117,85 @@ __global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
     prev = it.valid ? i : -2 - i;
   }
   MIB_STAMP_FLUSH(lane == 0, wave)
+}
+
+// k_forward_ep_bank with the layer-4 activations beside the logits
+// (net_model_compute_epochs_bank_feat[_f32]): feat [E][16][T64] int8, 16-byte aligned.  A SIBLING OF
+// k_forward_ep_bank, kept in step with it by hand: the same loop with gen::finish_prev_feat where
+// that kernel has gen::finish_prev, so the logits are its logits and an invalid item's feature row
+// is zeros.  A flag on the shared kernel would rename every existing instantiation (DESIGN.md §3,
+// "Features beside the logits").
+template <int L, bool RB, bool XR, bool CB>
+__global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_forward_ep_bank_feat(
+    const gen::GenParams* __restrict__ sets, int n_sets, const int* __restrict__ set_of,
+    const Scale* __restrict__ scales, const int8_t* __restrict__ x, const long long* __restrict__ onsets,
+    int8_t* __restrict__ out, int8_t* __restrict__ feat, int* __restrict__ n_bad, int E, long long last,
+    unsigned span_bytes, unsigned long long row_stride, const ep::ChanTab tab) {
+  using namespace gen;
+  static_assert(L == CT || L == F32, "epochs are channel-major");
+  extern __shared__ v4i smem_v[];
+  int8_t* smem = (int8_t*)smem_v;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // the geometry is every set's: set 0 stands for it until the first switch
+  const Lds m = lds_of(sets, smem, F32);
+  const int N = sets->N, T64 = sets->T64;
+  v4i* z = (v4i*)m.y1;  // the zero pads (gen::setup); the first switch's barriers publish them
+  for (int i = tid; i < m.cv.sg / 16; i += NT) z[i] = (v4i){0, 0, 0, 0};
+  const unsigned rowoff =
+      (unsigned)((L == F32 ? 4ull : 1ull) * (unsigned long long)tab.c[min(lane, sets->C - 1)] * row_stride);
+  ep::Epochs<L, XR, CB> src{sets, x, onsets, last, span_bytes, rowoff, m.y1, smem + m.cv.stg + 1024 * wave, m.cv.y1s,
+                            sets->NB1, sets->K7, wave, lane, m.cv.bytes <= LDS_2WG, L1C{}, 0.0f, 0.0f};
+  L2C k2;
+  const Range64 rg = range_of(blockIdx.x, gridDim.x, (unsigned long long)E);
+  const int end = (int)rg.hi;
+  int cur = -1;   // the set in registers and LDS
+  int prev = -1;  // gen::item_loop's: i valid, -2 - i invalid, -1 none
+  for (int i = (int)rg.lo;; i++) {
+    const bool more = i < end;  // uniform over the workgroup
+    auto it = src.open(i, more);
+    // (wave-uniform: one scalar load)  no address is formed from an index outside the bank
+    const int s = more && set_of ? set_of[i] : 0;
+    it.valid = it.valid && (unsigned)s < (unsigned)n_sets;
+    const int need = it.valid ? s : max(cur, 0);  // an invalid item stays where the workgroup is
+    if (more && need != cur) {
+      // item i - 1 ends on its own set before any of that set's state goes
+      if (wave == NW - 1) finish_prev_feat<RB, XR, CB>(src.gp, m, out, feat, n_bad, prev, N, T64, lane);
+      prev = -1;
+      __syncthreads();
+      cur = need;
+      src.gp = sets + cur;
+      // the reload's addresses are derived here, per switch, from an opaque copy of the thread
+      // index (k_forward_ep_bank)
+      int t;
+      asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
+      src.k1 = l1_consts<L>(src.gp, t & 63);
+      if constexpr (L == F32) {
+        const Scale q = scales[cur];
+        src.qs = q.qs;
+        src.qy = q.qy;
+      }
+      set_l2c(src.gp, k2, wave, t & 63);
+      set_lds(src.gp, m, t);
+      __syncthreads();
+    }
+    const GenParams* __restrict__ gp = src.gp;
+    if (wave < NW - 1) {
+      if (more) src.rows(it);
+    } else {
+      finish_prev_feat<RB, XR, CB>(gp, m, out, feat, n_bad, prev, N, T64, lane);
+      if (more) src.rows_last(it);
+    }
+    if (!more) break;
+    __syncthreads();  // A
+    layer2<RB, XR, CB>(gp, m.y1, m.cv.y1s, m.y2, m.cv.y2s, k2, wave, lane);
+    wg::wave_sync_lds();  // layer 3 of filter f reads only y2 row f, written by this wave
+    __builtin_amdgcn_s_setprio(wg::PRIO_L3);
+    layer3<XR, CB>(gp, m.sg, m.y2, m.cv.y2s, m.y3, wave, lane);
+    __builtin_amdgcn_s_setprio(0);
+    __syncthreads();  // B
+    prev = it.valid ? i : -2 - i;
+  }
 }
 
 // ---- windows through a bank (net_model_compute_windows_bank, include/mibminet.h) -------------

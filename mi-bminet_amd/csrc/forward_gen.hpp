@@ -589,6 +589,61 @@ __device__ __forceinline__ void finish_prev(const GenParams* __restrict__ gp, co
   }
 }
 
+// The layer-4 activations of the item whose y4 rows this wave has just written, for the entries that
+// return them beside the logits (net_model_compute_epochs_bank_feat, net_streams_windows_at_feat):
+// rows k < 16, columns v < T64 of y4 (row stride T64A) -> dst[k T64 + v], the T64_ALIGN pad columns
+// dropped: the bytes layer 5 multiplies.  dst is 16-byte aligned and an item's row is 16 T64 bytes,
+// so where T64 is a multiple of 4 (T64A = T64: the rows are contiguous in LDS too) it is T64 pieces
+// of 16 bytes, one per lane; otherwise each y4 row leaves as T64 bytes.  T64 <= 64 (TMAX / 64).
+__device__ __forceinline__ void store_feat(const int8_t* y4, int T64, int T64A, int8_t* __restrict__ dst, int ln) {
+  // the lane's addresses are derived here, per call, from an opaque copy of the lane (layer4's device)
+  int lane;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"(ln));
+  if ((T64 & 3) == 0) {
+    if (lane < T64) ((v4i*)dst)[lane] = ((const v4i*)y4)[lane];
+  } else {
+    if (lane < T64) {
+      // (by four: all sixteen rows' addresses at once cost the plain float builds up to 132 bytes of scratch)
+#pragma unroll 4
+      for (int k = 0; k < F2; k++) dst[k * T64 + lane] = y4[k * T64A + lane];
+    }
+  }
+}
+
+// finish_prev with the feature row beside the logit row.  A SIBLING OF finish_prev (and of
+// finish_trial inside it), not a flag on them: a template parameter there changed the names, and a
+// run-time one the code, of every existing instantiation (tools/asm_cmp.py).  The features leave
+// after layer 4 and the wave's LDS sync, before layer 5: y4 is this wave's until its next call, so no
+// barrier is added.  An invalid item gets 16 T64 zero bytes (T64 pieces of 16) as it gets N zero
+// logits, and is counted once.  T64: every set's (the geometry), so the invalid branch reads no set.
+template <bool RB, bool XR, bool CB>
+__device__ __forceinline__ void finish_prev_feat(const GenParams* __restrict__ gp, const Lds& m,
+                                                 int8_t* __restrict__ out, int8_t* __restrict__ feat,
+                                                 int* __restrict__ n_bad, int prev, int N, int T64, int lane) {
+  if (prev != -1) {
+    const bool vprev = prev >= 0;
+    const size_t item = (size_t)(vprev ? prev : -2 - prev);
+    int8_t* o = out + item * N;
+    int8_t* f = feat + item * (size_t)(F2 * T64);
+    if (vprev) {
+      __builtin_amdgcn_s_setprio(wg::PRIO_L45);
+      layer4<RB, XR, CB>(gp, m.y3, m.y4, m.sg, lane, 0, 1);
+      wg::wave_sync_lds();
+      store_feat(m.y4, T64, (T64 + 3) & ~3, f, lane);
+      layer5<CB>(gp, m.y4, m.w5, o, 0, 1, lane);
+      __builtin_amdgcn_s_setprio(0);
+    } else {
+      if (lane < N) o[lane] = 0;
+      // (the zero is made here: as a constant it was hoisted out of the loop, held in four registers
+      // across every layer and spilled in the plain float builds)
+      int zero;
+      asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
+      if (lane < T64) ((v4i*)f)[lane] = (v4i){zero, zero, zero, zero};
+      if (lane == 0 && n_bad) atomicAdd(n_bad, 1);
+    }
+  }
+}
+
 // The persistent loop of the kernels that read their items where they lie (win::k_forward_y1,
 // win::k_forward_y1_at, ep::k_forward_ep): items blockIdx.x, + gridDim.x, ... < n, logits [n][N].
 // Two barriers per item, as k_forward: waves 0 .. NW-2 bring in item i's y1 rows while the last

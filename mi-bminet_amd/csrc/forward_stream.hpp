@@ -28,7 +28,8 @@
 // the ring as it is, for cue-locked trials.  A retained window is one contiguous run of T bytes like
 // any grid window, so k_forward_ring_at is k_forward_ring's loop over a device list of (session,
 // onset) items with AtRows as its source; it writes logits and *n_bad alone.  Which windows are
-// retained, and for how long, is stream_host.hpp's at_item.
+// retained, and for how long, is stream_host.hpp's at_item.  k_forward_ring_at_feat
+// (net_streams_windows_at_feat) is that kernel writing each item's layer-4 activations as well.
 #pragma once
 #include "forward_bank.hpp"
 #include "stream_host.hpp"  // EachRec, plan_each: shared with the host
@@ -495,6 +496,69 @@ __global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
       if (more) src.rows(it);
     } else {
       finish_prev<RB, XR, CB, true>(gp, m, out, n_bad, prev, N, lane);
+    }
+    if (!more) break;
+    __syncthreads();  // A
+    layer2<RB, XR, CB>(gp, m.y1, m.cv.y1s, m.y2, m.cv.y2s, k2, wave, lane);
+    wg::wave_sync_lds();  // layer 3 of filter f reads only y2 row f, written by this wave
+    __builtin_amdgcn_s_setprio(wg::PRIO_L3);
+    layer3<XR, CB>(gp, m.sg, m.y2, m.cv.y2s, m.y3, wave, lane);
+    __builtin_amdgcn_s_setprio(0);
+    __syncthreads();  // B
+    prev = it.valid ? i : -2 - i;
+  }
+}
+
+// k_forward_ring_at with the layer-4 activations beside the logits (net_streams_windows_at_feat):
+// feat [W][16][T64] int8, 16-byte aligned.  A SIBLING OF k_forward_ring_at, kept in step with it by
+// hand: the same loop with gen::finish_prev_feat where that kernel has gen::finish_prev
+// (bank::k_forward_ep_bank_feat says why it is no flag).  It writes out, feat and *n_bad alone.
+template <bool RB, bool XR, bool CB, bool EACH>
+__global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_forward_ring_at_feat(
+    const gen::GenParams* __restrict__ sets, int n_sets, const int8_t* __restrict__ ring,
+    const int* __restrict__ session_of, const long long* __restrict__ onsets, const long long* __restrict__ lim,
+    const int* __restrict__ set_of, int8_t* __restrict__ out, int8_t* __restrict__ feat, int* __restrict__ n_bad, int W,
+    int S, long long pos, int pos_mod, int cap) {
+  using namespace gen;
+  extern __shared__ v4i smem_v[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // the geometry is every set's: set 0 stands for it until the first switch
+  const Lds m = lds_of(sets, (int8_t*)smem_v, 3);
+  const int N = sets->N, T64 = sets->T64;
+  v4i* z = (v4i*)m.y1;  // the zero pads (gen::setup); the first switch's barriers publish them
+  for (int i = tid; i < m.cv.sg / 16; i += NT) z[i] = (v4i){0, 0, 0, 0};
+  AtRows<RB || XR, EACH> src{ring, session_of, onsets, lim,     set_of,    sets,     pos, pos_mod,
+                             S,    cap,        n_sets, sets->T, sets->NB1, m.cv.y1s, tid, m.y1};
+  L2C k2;
+  const Range64 rg = range_of(blockIdx.x, gridDim.x, (unsigned long long)W);
+  const int end = (int)rg.hi;
+  int cur = -1;   // the set in registers and LDS
+  int prev = -1;  // gen::item_loop's: i valid, -2 - i invalid, -1 none
+  for (int i = (int)rg.lo;; i++) {
+    const bool more = i < end;  // uniform over the workgroup
+    const auto it = src.open(i, more);
+    const int need = it.valid ? it.s : max(cur, 0);  // an invalid item stays where the workgroup is
+    if (more && need != cur) {
+      // item i - 1 ends on its own set before any of that set's state goes
+      if (wave == NW - 1) finish_prev_feat<RB, XR, CB>(src.gp, m, out, feat, n_bad, prev, N, T64, lane);
+      prev = -1;
+      __syncthreads();
+      cur = need;
+      src.gp = sets + cur;
+      // the reload's addresses are derived here, per switch, from an opaque copy of the thread
+      // index (bank::k_forward_ep_bank)
+      int t;
+      asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
+      set_l2c(src.gp, k2, wave, t & 63);
+      set_lds(src.gp, m, t);
+      __syncthreads();
+    }
+    const GenParams* __restrict__ gp = src.gp;
+    if (wave < NW - 1) {
+      if (more) src.rows(it);
+    } else {
+      finish_prev_feat<RB, XR, CB>(gp, m, out, feat, n_bad, prev, N, T64, lane);
     }
     if (!more) break;
     __syncthreads();  // A

@@ -10,7 +10,8 @@
 //   shared with the kernels (HIP-free);
 // * images.hpp: the gfx950 operand fragments and both parameter images, laid out from the plan
 //   (HIP-free);
-// * bank_host.hpp: the HIP-free part of a parameter bank, the build of its images included;
+// * bank_host.hpp: the HIP-free part of a parameter bank, the build of its images and the decision
+//   of a replacement (net_bank_replace) included;
 // * stream_host.hpp: the HIP-free part of a stream group: ring size, per-push arithmetic, checks,
 //   an each-group's per-session plan, shared with its plan kernel, and a query's validity
 //   predicate, shared with its kernel;
@@ -20,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -370,6 +372,14 @@ int epochs_async(const void* x, bool f32, size_t n_elems, size_t row_stride, con
   });
 }
 
+// A launch on a capturing stream would be replayed with the host state its arguments were computed
+// from (a stream group's position, a replacement's bytes); a status that cannot be read counts as
+// capturing.
+bool capturing(hipStream_t st) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+}
+
 // ---- parameter banks (forward_bank.hpp, bank_host.hpp) ---------------------------------------
 // (a bank's images are built by bank::build, bank_host.hpp: net_bank_create below only allocates)
 void bank_destroy(net_bank* b) {
@@ -381,19 +391,92 @@ void bank_destroy(net_bank* b) {
     if (guard.err == hipSuccess) (void)hipDeviceSynchronize();  // no launch still reads the copy
     (void)hipFree(c.second);
   }
+  for (const auto& sb : b->staging) {  // the devices are idle: every copy out of a buffer has finished
+    (void)hipEventDestroy(sb.second);
+    (void)hipHostFree(sb.first);
+  }
   delete b;
 }
 
+// net_bank_replace (include/mibminet.h).  The decision is bank::replace_set's (bank_host.hpp); here
+// are the locks and the copy.  Order of the locks as in a launching call: the device's, then the
+// bank's (ensure_bank).  The device's copy of the slot is overwritten by copies enqueued on `stream`
+// out of a pinned buffer of the bank's own, never out of the master or the caller's blob: the call
+// returns before they run, and both may change right after it.  The master changes last, and only
+// its body: the head (geometry and flags) is the record's and is read by other threads unlocked.
+int bank_replace(net_bank* b, size_t set, const void* blob, size_t len, float scale, int device, void* stream) {
+  if (!b || set >= b->sets.size() || !blob) return NET_ERR_INVALID;
+  if (device < 0 || device >= MAX_DEVICES) return NET_ERR_INVALID;
+  auto cand = std::make_unique<gen::GenParams>();
+  bank::Scale sc{};
+  if (const int rc = bank::replace_set(b->rec, blob, len, scale, *cand, sc)) return rc;
+  constexpr size_t HEAD = offsetof(gen::GenParams, l3_m), IMG = sizeof(gen::GenParams);
+  const hipStream_t st = (hipStream_t)stream;
+  std::lock_guard<std::mutex> dl(g_devs[device].mu);
+  std::lock_guard<std::mutex> bl(b->mu);
+  void* copy = nullptr;
+  bool elsewhere = false;
+  for (const auto& c : b->dev) {
+    if (c.first == device) copy = c.second;
+    else elsewhere = true;
+  }
+  // host data is copied, which a replay would not do again (asked only where something is enqueued:
+  // a bank without a copy touches no device here)
+  if (copy && capturing(st)) return NET_ERR_UNSUPPORTED;
+  if (elsewhere) return NET_ERR_UNSUPPORTED;  // replacing across devices is not part of this entry
+  // (agree and the exact-division rule fix every field of the head; held to it all the same)
+  if (std::memcmp(cand.get(), &b->sets[set], HEAD) != 0) return NET_ERR_UNSUPPORTED;
+  if (copy) {
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return hip_err(guard.err);
+    std::pair<void*, hipEvent_t>* buf = nullptr;
+    for (auto& sb : b->staging)
+      if (hipEventQuery(sb.second) == hipSuccess) {
+        buf = &sb;
+        break;
+      }
+    if (!buf) {
+      void* p = nullptr;
+      hipEvent_t ev = nullptr;
+      hipError_t e = hipHostMalloc(&p, IMG + sizeof(bank::Scale), hipHostMallocDefault);
+      if (e != hipSuccess) return hip_err(e);
+      e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+      if (e != hipSuccess) {
+        (void)hipHostFree(p);
+        return hip_err(e);
+      }
+      b->staging.emplace_back(p, ev);
+      buf = &b->staging.back();
+    }
+    std::memcpy(buf->first, cand.get(), IMG);
+    std::memcpy((char*)buf->first + IMG, &sc, sizeof(sc));
+    char* slot = (char*)copy + set * IMG;
+    hipError_t e = hipMemcpyAsync(slot, buf->first, IMG, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && !b->scales.empty())
+      e = hipMemcpyAsync((char*)copy + b->sets.size() * IMG + set * sizeof(bank::Scale), (char*)buf->first + IMG,
+                         sizeof(bank::Scale), hipMemcpyHostToDevice, st);
+    // recorded even after a failed copy: the buffer is not written again while one may still read it
+    const hipError_t er = hipEventRecord(buf->second, st);
+    if (e != hipSuccess || er != hipSuccess) return hip_err(e != hipSuccess ? e : er);
+  }
+  std::memcpy((char*)&b->sets[set] + HEAD, (const char*)cand.get() + HEAD, IMG - HEAD);
+  if (!b->scales.empty()) b->scales[set] = sc;
+  return NET_OK;
+}
+
 // epochs_async on a bank: the same checks in the same order, C and T the bank's; then the set
-// indices' and, for float input, the bank's scales.
+// indices' and, for float input, the bank's scales.  with_feat: the _feat entries, which also write
+// the layer-4 activations to feat (its check stands with y's: check_epochs' are all NET_ERR_INVALID).
 int bank_epochs_async(const net_bank* b, const void* x, bool f32, size_t n_elems, size_t row_stride,
                       const int32_t* channels, const int64_t* onsets, const int32_t* set_of, size_t E, int8_t* y,
-                      int32_t* n_bad, int device, void* stream) {
+                      int32_t* n_bad, int device, void* stream, bool with_feat = false, int8_t* feat = nullptr) {
   if (!b) return NET_ERR_INVALID;
   const gen::GenParams& hg = b->sets[0];
   EpochGeom g;
   if (const int rc = check_epochs(hg.C, hg.T, x, f32, n_elems, row_stride, channels, onsets, E, y, n_bad, device, g))
     return rc;
+  if (with_feat)
+    if (const int rc = check_feat(E, feat)) return rc;
   if (((uintptr_t)set_of & 3) != 0 || (E && !set_of && b->sets.size() != 1)) return NET_ERR_INVALID;
   if (f32 && b->scales.empty()) return NET_ERR_INVALID;
   if (E == 0) return NET_OK;
@@ -407,7 +490,15 @@ int bank_epochs_async(const net_bank* b, const void* x, bool f32, size_t n_elems
                           (const int8_t*)x, (const long long*)onsets, y, (int*)n_bad, (int)E, g.last, g.span_bytes,
                           (unsigned long long)row_stride, g.tab);
     };
+    auto go_feat = [&](auto kern) {
+      return launch_items(sc.ds, kern, epochs_lds(hg), E, (hipStream_t)stream, sets, (int)b->sets.size(), (const int*)set_of, scales,
+                          (const int8_t*)x, (const long long*)onsets, y, feat, (int*)n_bad, (int)E, g.last, g.span_bytes,
+                          (unsigned long long)row_stride, g.tab);
+    };
     constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
+    if (with_feat)
+      return f32 ? go_feat(bank::k_forward_ep_bank_feat<gen::F32, RB, XR, CB>)
+                 : go_feat(bank::k_forward_ep_bank_feat<gen::CT, RB, XR, CB>);
     return f32 ? go(bank::k_forward_ep_bank<gen::F32, RB, XR, CB>) : go(bank::k_forward_ep_bank<gen::CT, RB, XR, CB>);
   });
 }
@@ -448,12 +539,6 @@ int bank_windows_async(const net_bank* b, const void* x, int arg_layout, bool f3
 }
 
 // ---- live streams (forward_stream.hpp, stream_host.hpp) --------------------------------------
-// A launch on a capturing stream would be replayed with the position its arguments were computed
-// from; a status that cannot be read counts as capturing.
-bool capturing(hipStream_t st) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  return hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-}
 
 int streams_create(const net_bank* b, const int32_t* sets, size_t S, size_t hop, size_t max_push, int device,
                    net_streams** out, bool each = false) {
@@ -613,13 +698,15 @@ int streams_push_each(net_streams* g, const void* x, int arg_layout, bool f32, c
   return NET_OK;
 }
 
-// net_streams_windows_at: every check comes before the one launch.  A uniform group's arguments
+// net_streams_windows_at[_feat]: every check comes before the one launch.  A uniform group's arguments
 // come from the host's position, so its launch is not capturable; an each-group's reads nothing from
 // the host.  Nothing of the group changes.
 int streams_windows_at(net_streams* g, const int32_t* session, const int64_t* onsets, size_t W, int8_t* y,
-                       int32_t* n_bad, void* stream) {
+                       int32_t* n_bad, void* stream, bool with_feat = false, int8_t* feat = nullptr) {
   if (const int rc = stream::check_windows_at(g != nullptr, W, session, onsets, y, n_bad)) return rc;
   if (W == 0) return NET_OK;
+  if (with_feat)
+    if (const int rc = check_feat(W, feat)) return rc;
   const net_bank& b = *g->bank;
   const gen::GenParams& hg = b.sets[0];
   DeviceScope sc(g->device, b);
@@ -640,6 +727,14 @@ int streams_windows_at(net_streams* g, const int32_t* session, const int64_t* on
                           (const long long*)onsets, lim, set_of, y, (int*)n_bad, (int)W, (int)g->S, pos, pos_mod,
                           (int)g->cap);
     };
+    auto go_feat = [&](auto kern) {
+      return launch_items(sc.ds, kern, windows_lds(hg), W, st, sets, n_sets, ring, (const int*)session,
+                          (const long long*)onsets, lim, set_of, y, feat, (int*)n_bad, (int)W, (int)g->S, pos, pos_mod,
+                          (int)g->cap);
+    };
+    if (with_feat)
+      return g->each ? go_feat(stream::k_forward_ring_at_feat<RB, XR, CB, true>)
+                     : go_feat(stream::k_forward_ring_at_feat<RB, XR, CB, false>);
     return g->each ? go(stream::k_forward_ring_at<RB, XR, CB, true>) : go(stream::k_forward_ring_at<RB, XR, CB, false>);
   });
 }
@@ -1060,6 +1155,11 @@ int net_streams_windows_at(net_streams_t* st, const int32_t* session, const int6
   return streams_windows_at(st, session, onsets, W, y, n_bad, stream);
 }
 
+int net_streams_windows_at_feat(net_streams_t* st, const int32_t* session, const int64_t* onsets, size_t W, int8_t* y,
+                                int8_t* feat, int32_t* n_bad, void* stream) {
+  return streams_windows_at(st, session, onsets, W, y, n_bad, stream, true, feat);
+}
+
 int net_streams_at_span(const net_streams_t* st, int64_t* lo, int64_t* hi) { return streams_at_span(st, lo, hi); }
 
 int net_model_compute_batch_multi(int ndev, const int* devices, const int8_t* const* x, int8_t* const* y,
@@ -1137,7 +1237,8 @@ int net_bank_create(const void* const* blobs, const size_t* sizes, const float* 
   if (bank) *bank = nullptr;
   if (!blobs || !sizes || !bank || n_sets == 0 || n_sets > NET_BANK_MAX_SETS) return NET_ERR_INVALID;
   auto b = std::make_unique<net_bank>();
-  if (const int rc = bank::build(blobs, sizes, scales, n_sets, g_force_general.load() != 0, b->sets, b->scales, failed))
+  if (const int rc = bank::build(blobs, sizes, scales, n_sets, g_force_general.load() != 0, b->sets, b->scales, failed,
+                                 &b->rec))
     return rc;
   *bank = b.release();
   return NET_OK;
@@ -1153,6 +1254,13 @@ int net_bank_info(const net_bank_t* bank, int32_t* info) {
 
 void net_bank_destroy(net_bank_t* bank) { bank_destroy(bank); }
 
+int net_bank_replace(net_bank_t* bank, size_t set, const void* blob, size_t len, float scale, int device,
+                     void* stream) {
+  return bank_replace(bank, set, blob, len, scale, device, stream);
+}
+
+size_t net_bank_feature_bytes(const net_bank_t* bank) { return bank ? (size_t)16 * (size_t)bank->sets[0].T64 : 0; }
+
 int net_model_compute_epochs_bank(const net_bank_t* bank, const int8_t* x, size_t n_elems, size_t row_stride,
                                   const int32_t* channels, const int64_t* onsets, const int32_t* set_of, size_t E,
                                   int8_t* y, int32_t* n_bad, int device, void* stream) {
@@ -1163,6 +1271,20 @@ int net_model_compute_epochs_bank_f32(const net_bank_t* bank, const float* x, si
                                       const int32_t* channels, const int64_t* onsets, const int32_t* set_of, size_t E,
                                       int8_t* y, int32_t* n_bad, int device, void* stream) {
   return bank_epochs_async(bank, x, true, n_elems, row_stride, channels, onsets, set_of, E, y, n_bad, device, stream);
+}
+
+int net_model_compute_epochs_bank_feat(const net_bank_t* bank, const int8_t* x, size_t n_elems, size_t row_stride,
+                                       const int32_t* channels, const int64_t* onsets, const int32_t* set_of, size_t E,
+                                       int8_t* y, int8_t* feat, int32_t* n_bad, int device, void* stream) {
+  return bank_epochs_async(bank, x, false, n_elems, row_stride, channels, onsets, set_of, E, y, n_bad, device, stream,
+                           true, feat);
+}
+
+int net_model_compute_epochs_bank_feat_f32(const net_bank_t* bank, const float* x, size_t n_elems, size_t row_stride,
+                                           const int32_t* channels, const int64_t* onsets, const int32_t* set_of,
+                                           size_t E, int8_t* y, int8_t* feat, int32_t* n_bad, int device, void* stream) {
+  return bank_epochs_async(bank, x, true, n_elems, row_stride, channels, onsets, set_of, E, y, n_bad, device, stream,
+                           true, feat);
 }
 
 int net_model_compute_windows_bank(const net_bank_t* bank, const int8_t* x, int layout, size_t L,

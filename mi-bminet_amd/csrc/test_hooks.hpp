@@ -145,6 +145,7 @@ int mibminet_test_bank_copy(const net_bank_t* bank, size_t set, void* buf, size_
   *bytes = sizeof(gen::GenParams);
   if (!buf) return NET_OK;
   if (cap < *bytes) return NET_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(bank->mu);  // net_bank_replace writes a slot under it
   std::memcpy(buf, &bank->sets[set], *bytes);
   return NET_OK;
 }

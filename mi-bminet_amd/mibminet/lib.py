@@ -71,8 +71,12 @@ PROTOTYPES = {
     "net_bank_create": "int (ptr, ptr, ptr, size_t, ptr, ptr)",
     "net_bank_info": "int (ptr, ptr)",
     "net_bank_destroy": "void (ptr)",
+    "net_bank_replace": "int (ptr, size_t, ptr, size_t, float, int, ptr)",
+    "net_bank_feature_bytes": "size_t (ptr)",
     "net_model_compute_epochs_bank": "int (ptr, ptr, size_t, size_t, ptr, ptr, ptr, size_t, ptr, ptr, int, ptr)",
     "net_model_compute_epochs_bank_f32": "int (ptr, ptr, size_t, size_t, ptr, ptr, ptr, size_t, ptr, ptr, int, ptr)",
+    "net_model_compute_epochs_bank_feat": "int (ptr, ptr, size_t, size_t, ptr, ptr, ptr, size_t, ptr, ptr, ptr, int, ptr)",
+    "net_model_compute_epochs_bank_feat_f32": "int (ptr, ptr, size_t, size_t, ptr, ptr, ptr, size_t, ptr, ptr, ptr, int, ptr)",
     "net_model_compute_windows_bank": "int (ptr, ptr, int, size_t, ptr, ptr, size_t, ptr, ptr, ptr, size_t, int, ptr)",
     "net_model_compute_windows_bank_f32": "int (ptr, ptr, size_t, ptr, ptr, size_t, ptr, ptr, ptr, size_t, int, ptr)",
     "net_model_compute_windows_bank_f32_tm": "int (ptr, ptr, size_t, ptr, ptr, size_t, ptr, ptr, ptr, size_t, int, ptr)",
@@ -95,6 +99,7 @@ PROTOTYPES = {
     "net_streams_push_each_f32_tm": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr, ptr, ptr)",
     "net_streams_positions": "int (ptr, ptr, ptr)",
     "net_streams_windows_at": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr)",
+    "net_streams_windows_at_feat": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr, ptr)",
     "net_streams_at_span": "int (ptr, ptr, ptr)",
     "net_model_compute_batch_multi": "int (int, ptr, ptr, ptr, ptr, ptr)",
     "net_model_compute_batch_multi_ct": "int (int, ptr, ptr, ptr, ptr, ptr)",
@@ -297,6 +302,31 @@ class Bank:
     def device_copies(self) -> int:
         """Test hook (mibminet_test_bank_device_copies): devices that hold a copy of the bank."""
         return int(load().mibminet_test_bank_device_copies(self.handle))
+
+    def feature_bytes(self) -> int:
+        """net_bank_feature_bytes: bytes of one item's layer-4 feature row, 16 * (T // 64)."""
+        return int(load().net_bank_feature_bytes(self.handle))
+
+    def replace(self, s: int, param_set_or_blob, scale: Optional[float] = None, device: int = 0, stream=None) -> None:
+        """net_bank_replace: set ``s`` becomes ``param_set_or_blob`` (a ParamSet or a blob), ordered on
+        ``stream`` (a torch stream; default: the current one of ``device``): the calls enqueued on it
+        before read the old set, those after it the new one, and every other set stays as it is.
+        The new set must agree with what the bank was created with (C, T, N, REORDER_BN, clip); a
+        bank that runs the float form refuses a set that needs exact division.  ``scale`` is the
+        set's input-quantiser scale, required iff the bank has scales.  Only ``device``'s copy of the
+        bank is updated (a bank resident on another device is refused); before any device holds a
+        copy only the host master changes and no stream is needed.  A refused call raises NetError
+        and changes nothing.  Sessions of a stream group under set ``s`` need a restart afterwards
+        unless the new set shares the old one's layer 1 (ParamSet.with_head)."""
+        blob = param_set_or_blob.to_blob() if isinstance(param_set_or_blob, ParamSet) else bytes(param_set_or_blob)
+        if self.has_scales and scale is None:
+            raise ValueError("the bank has scales: the new set needs one")
+        st = stream.cuda_stream if stream is not None else None
+        if stream is None and self.device_copies():
+            st = _torch().cuda.current_stream(device).cuda_stream
+        buf = ctypes.create_string_buffer(blob, len(blob))
+        _check(load().net_bank_replace(self.handle, s, buf, len(blob), 0.0 if scale is None else float(scale), device, st),
+               f"net_bank_replace, set {s}")
 
     def close(self) -> None:
         if self._h is not None:
@@ -687,7 +717,8 @@ def _index_list(v, dtype, what: str):
     return v
 
 
-def _forward_onsets(net, name: str, x, head, onsets, mid, stream, check: bool, noun: str, set_of=False):
+def _forward_onsets(net, name: str, x, head, onsets, mid, stream, check: bool, noun: str, set_of=False,
+                    features: bool = False):
     """The call of an entry of ``net`` (a _Net) that takes an onset list, ``name`` or, for a float32
     ``x``, ``name``_f32: entry([bank,] x, *head, onsets, [set_of,] n, [scale,] y, n_bad, *mid, device,
     stream).  ``onsets`` is a 1-D int64 tensor or a sequence of ints; ``set_of`` False (the entry takes
@@ -696,7 +727,8 @@ def _forward_onsets(net, name: str, x, head, onsets, mid, stream, check: bool, n
     counter are made on the launch stream.  An empty list passes NULL for the lists and the logits,
     ``check=False`` NULL for the counter.  With ``check`` and a non-empty list the stream is
     synchronised, the count of items outside the ``noun`` read back and a ValueError raised if it is
-    not zero.  Returns the logits [n][N]."""
+    not zero.  Returns the logits [n][N]; with ``features`` the entry is ``name``_feat[_f32], which takes
+    a feature buffer after the logits, and (logits, features [n][16][T64] int8) is returned."""
     torch = _torch()
     lists = [_index_list(onsets, torch.int64, "onsets")]
     n = int(lists[0].numel())
@@ -712,18 +744,20 @@ def _forward_onsets(net, name: str, x, head, onsets, mid, stream, check: bool, n
         lists = [v.to(x.device).contiguous() for v in lists]
         nbad = torch.zeros((1,), dtype=torch.int32, device=x.device) if check else None
     y = torch.empty((n, net.dims.N), dtype=torch.int8, device=x.device)
-    name += net.f32_suffix if x.dtype == torch.float32 else ""
+    feat = torch.empty((n, net.dims.F2, net.dims.T64), dtype=torch.int8, device=x.device) if features else None
+    name += ("_feat" if features else "") + (net.f32_suffix if x.dtype == torch.float32 else "")
     ptrs = [v.data_ptr() if n else None for v in lists] + [None] * (set_of is None)
     y_ptr, nbad_ptr = y.data_ptr() if n else None, nbad.data_ptr() if check else None
-    _check(getattr(load(), name)(*net.handle, x.data_ptr(), *head, *ptrs, n, *net.scale, y_ptr, nbad_ptr, *mid, dev,
-                                 s.cuda_stream), name)
+    feat_ptr = ((feat.data_ptr() if n else None),) if features else ()
+    _check(getattr(load(), name)(*net.handle, x.data_ptr(), *head, *ptrs, n, *net.scale, y_ptr, *feat_ptr, nbad_ptr, *mid,
+                                 dev, s.cuda_stream), name)
     if check and n:
         s.synchronize()
         bad = int(nbad.item())
         if bad:
             what = "onsets" if set_of is False else "onsets or set indices"
             raise ValueError(f"{bad} of {n} {what} lie outside the {noun} (their logit rows are zero)")
-    return y
+    return (y, feat) if features else y
 
 
 def _windows_source(net, x, layout: str, scale, noun: str):
@@ -921,7 +955,7 @@ def forward_crop_torch(x, t0: int, channels=None, scale: Optional[float] = None,
 
 
 def forward_epochs_bank_torch(bank, x, onsets, set_of, channels=None, row_stride: Optional[int] = None, stream=None,
-                              check: bool = True):
+                              check: bool = True, features: bool = False):
     """net_model_compute_epochs_bank / _f32: forward_epochs_torch with the network chosen per
     epoch: epoch e is classified by set ``set_of[e]`` of ``bank`` (a Bank; the loaded set plays no
     part).  ``x``, ``onsets``, ``channels`` and ``row_stride`` are forward_epochs_torch's, C and T
@@ -930,10 +964,13 @@ def forward_epochs_bank_torch(bank, x, onsets, set_of, channels=None, row_stride
     one set).  Returns the logits [E][N] int8, row e what forward_epochs_torch returns for that
     epoch with set ``set_of[e]`` loaded.  Any order is correct; grouped by set is fast.  The rows
     of invalid onsets and of indices outside the bank are zero; with ``check`` their count is read
-    back (a host sync) and a ValueError names it."""
+    back (a host sync) and a ValueError names it.  With ``features``
+    (net_model_compute_epochs_bank_feat / _f32) returns (logits, features [E][16][T // 64] int8): row e
+    is layer 4's output of epoch e under its set, the bytes layer 5 multiplies, zeros for an invalid
+    epoch; a head refitted on them goes back through ParamSet.with_head and Bank.replace."""
     net = _Net(_require_bank(bank))
     return _forward_onsets(net, "net_model_compute_epochs_bank", x, _epoch_source(net, x, channels, row_stride, None),
-                           onsets, (), stream, check, "source or the bank", set_of=set_of)
+                           onsets, (), stream, check, "source or the bank", set_of=set_of, features=features)
 
 
 def forward_bank_torch(bank, x, set_of, stream=None, check: bool = True):
@@ -1040,14 +1077,15 @@ def forward_windows_multi_bank_torch(bank, recordings, sets, hop: int, layout: s
         return _stitch(net, tensors[0], out), first
 
 
-def _streams_windows_at(group, sessions, onsets, stream, out, check: bool):
+def _streams_windows_at(group, sessions, onsets, stream, out, check: bool, features: bool = False):
     """net_streams_windows_at on ``group`` (a Streams or a StreamsEach): the windows of sessions
     ``sessions[w]`` that start at samples ``onsets[w]``, read from the layer-1 rings as they are.  The
     lists are device tensors (int32 and int64, 1-D) or sequences of ints, through _index_list; their
     device copies and the zeroed counter are made on the launch stream.  ``check`` is
     forward_windows_at_torch's: the stream is synchronised, the count of invalid items read back and
     a ValueError raised if it is not zero; ``check=False`` passes NULL for the counter.  Returns the
-    logits [W][N]."""
+    logits [W][N]; with ``features`` (net_streams_windows_at_feat) the pair (logits, features
+    [W][16][T64] int8), a zero feature row beside every zero logit row."""
     torch = _torch()
     ses = _index_list(sessions, torch.int32, "sessions")
     ons = _index_list(onsets, torch.int64, "onsets")
@@ -1061,16 +1099,22 @@ def _streams_windows_at(group, sessions, onsets, stream, out, check: bool):
         nbad = torch.zeros((1,), dtype=torch.int32, device=dev) if check else None
         if out is None:
             out = torch.empty((W, N), dtype=torch.int8, device=dev)
+        d = group.bank.dims
+        feat = torch.empty((W, d.F2, d.T64), dtype=torch.int8, device=dev) if features else None
     _check_tensor(out, "out", ("int8",), (W, N))
-    _check(load().net_streams_windows_at(group.handle, ses.data_ptr() if W else None, ons.data_ptr() if W else None, W,
-                                         out.data_ptr() if W else None, nbad.data_ptr() if check else None,
-                                         s.cuda_stream), "net_streams_windows_at")
+    lead = (group.handle, ses.data_ptr() if W else None, ons.data_ptr() if W else None, W, out.data_ptr() if W else None)
+    tail = (nbad.data_ptr() if check else None, s.cuda_stream)
+    if features:
+        _check(load().net_streams_windows_at_feat(*lead, feat.data_ptr() if W else None, *tail),
+               "net_streams_windows_at_feat")
+    else:
+        _check(load().net_streams_windows_at(*lead, *tail), "net_streams_windows_at")
     if check and W:
         s.synchronize()
         bad = int(nbad.item())
         if bad:
             raise ValueError(f"{bad} of {W} windows are not in the rings (their logit rows are zero)")
-    return out
+    return (out, feat) if features else out
 
 
 class Streams:
@@ -1158,7 +1202,7 @@ class Streams:
         return self._push(x, "_f32" if layout == "ct" else "_f32_tm", (), int(x.shape[2 if layout == "ct" else 1]), stream,
                           out)
 
-    def windows_at(self, sessions, onsets, stream=None, out=None, check: bool = True):
+    def windows_at(self, sessions, onsets, stream=None, out=None, check: bool = True, features: bool = False):
         """net_streams_windows_at: the windows of sessions ``sessions[w]`` whose first samples are
         ``onsets[w]`` on the group's position axis, read from the rings as they are (cue-locked
         trials).  Device tensors (int32, int64) or sequences of ints, any order, duplicates allowed;
@@ -1167,8 +1211,10 @@ class Streams:
         loaded.  A window that is not complete, no longer in the ring (see ``at_span``), from before
         the session's origin, or of a session outside the group gives a zero row; with ``check``
         their count is read back (a host sync) and a ValueError names it.  ``out``: an int8 device
-        tensor [W][N] to write instead.  Ordered like a push; moves nothing."""
-        return _streams_windows_at(self, sessions, onsets, stream, out, check)
+        tensor [W][N] to write instead.  Ordered like a push; moves nothing.  With ``features``
+        returns (logits, features [W][16][T // 64] int8): each window's layer-4 output under its
+        session's set (forward_epochs_bank_torch), zeros beside a zero logit row."""
+        return _streams_windows_at(self, sessions, onsets, stream, out, check, features)
 
     def at_span(self) -> tuple:
         """net_streams_at_span: (lo, hi), the onsets whose windows are in the rings now, lo =
@@ -1303,12 +1349,13 @@ class StreamsEach:
         return self._push(x, "_f32" if layout == "ct" else "_f32_tm", (), int(x.shape[2 if layout == "ct" else 1]), counts,
                           stream, out)
 
-    def windows_at(self, sessions, onsets, stream=None, out=None, check: bool = True):
+    def windows_at(self, sessions, onsets, stream=None, out=None, check: bool = True, features: bool = False):
         """net_streams_windows_at on an each-group: Streams.windows_at with every onset in its
         session's own count since its last restart; a session's span is max(pos - cap, 0) ..
         pos - T of its position (``positions()``).  With device tensors and ``check=False`` the call
-        reads nothing from the host and, after one eager call, may be captured behind a push."""
-        return _streams_windows_at(self, sessions, onsets, stream, out, check)
+        reads nothing from the host and, after one eager call, may be captured behind a push.
+        ``features``: Streams.windows_at's."""
+        return _streams_windows_at(self, sessions, onsets, stream, out, check, features)
 
     def restart(self, i: int, set: int, stream=None) -> None:
         """net_streams_restart on an each-group: session ``i`` starts again at position 0 under

@@ -15,11 +15,19 @@ the median of --reps calls of one candidate; gate: every A round at most 1.05 x 
 neighbouring C medians plus their difference (the rule of profiles/binding_speed.json).  One JSON
 line per case goes to <out-dir>/bank_<name>.json and to stdout.  There is no CPU path.
 
-  python tools/bench_bank.py [--cases bci_63x288,mmmi_105x84,big_4x16384,bci_shuffled] [--limit N]
+bci_63x288_feat (report only, no gate): on bci_63x288's epochs, (a) the plain bank call, (a2) the same
+call again, so that the run-to-run spread of one candidate stands beside the numbers, and (f)
+net_model_compute_epochs_bank_feat, which also stores 16 T64 bytes of layer-4 activations per epoch;
+the three alternate within every repeat.  Verified first: (f)'s logits equal (a)'s.  Then
+net_bank_replace of one slot, --reps times, the queue drained before each: the host's time per call
+(a clock around it) and the device's time of the slot update (HIP events around it).
+
+  python tools/bench_bank.py [--cases bci_63x288,mmmi_105x84,big_4x16384,bci_shuffled,bci_63x288_feat] [--limit N]
                              [--reps 7] [--warmup 2] [--variant canonical|plain_bn] [--out-dir profiles]
 """
 import ctypes
 import statistics
+import time
 
 from bench_common import main, medians, min_max, time_alternating
 
@@ -29,9 +37,80 @@ CASES = {  # name: (sets, epochs per set, C, T, N, shuffled, rounds C A C A C)
     "big_4x16384": (4, 16384, 22, 1125, 4, False, True),
     "bci_shuffled": (63, 288, 22, 1125, 4, True, False),
 }
+FEAT_CASES = {"bci_63x288_feat": (63, 288, 22, 1125, 4)}  # name: (sets, epochs per set, C, T, N)
+
+
+def run_feat(name, limit, reps, warmup, variant, seed=2026):
+    import torch
+
+    from mibminet import lib
+    from mibminet.params import ParamSet
+
+    S, per, C, T, N = FEAT_CASES[name]
+    per = min(per, limit)
+    E = S * per
+    sets = [ParamSet.synthetic(seed=seed + s, C=C, T=T, N=N, reorder_bn=variant != "plain_bn") for s in range(S)]
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    x = torch.randint(-128, 128, (E, C, T), dtype=torch.int8, device="cuda", generator=g)
+    onsets = torch.arange(E, dtype=torch.int64, device="cuda") * (C * T)
+    set_of = torch.arange(E, dtype=torch.int32, device="cuda") // per
+    L = lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    ya, yf = (torch.empty((E, N), dtype=torch.int8, device="cuda") for _ in range(2))
+    bank = lib.Bank(sets)
+    fb = bank.feature_bytes()
+    feat = torch.empty((E, fb), dtype=torch.int8, device="cuda")
+
+    def a():
+        rc = L.net_model_compute_epochs_bank(bank.handle, x.data_ptr(), x.numel(), T, None, onsets.data_ptr(),
+                                             set_of.data_ptr(), E, ya.data_ptr(), None, 0, st)
+        assert rc == 0, rc
+
+    def f():
+        rc = L.net_model_compute_epochs_bank_feat(bank.handle, x.data_ptr(), x.numel(), T, None, onsets.data_ptr(),
+                                                  set_of.data_ptr(), E, yf.data_ptr(), feat.data_ptr(), None, 0, st)
+        assert rc == 0, rc
+
+    a()
+    f()
+    torch.cuda.synchronize()
+    mismatches = int((ya != yf).any(dim=1).sum().item())
+    ms = time_alternating({"a": a, "f": f, "a2": a}, reps, warmup)
+    med = medians(ms)
+    # net_bank_replace of slot S // 2 by another set of the geometry
+    blob = ParamSet.synthetic(seed=seed + S, C=C, T=T, N=N, reorder_bn=variant != "plain_bn").to_blob()
+    buf = ctypes.create_string_buffer(blob, len(blob))
+    host_ms, dev_ms = [], []
+    for r in range(warmup + reps):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        t0 = time.perf_counter()
+        rc = L.net_bank_replace(bank.handle, S // 2, buf, len(blob), 0.0, 0, st)
+        t1 = time.perf_counter()
+        e1.record()
+        e1.synchronize()
+        assert rc == 0, rc
+        if r >= warmup:
+            host_ms.append((t1 - t0) * 1e3)
+            dev_ms.append(e0.elapsed_time(e1))
+    info = bank.info()
+    res = {"name": name, "sets": S, "epochs_per_set": per, "epochs": E, "C": C, "T": T, "N": N, "variant": variant,
+           "feature_bytes_per_epoch": fb, "input_bytes_per_epoch": C * T, "reps": reps, "warmup": warmup,
+           "mismatched_epochs": mismatches, "device": torch.cuda.get_device_name(0),
+           "ms_plain": round(med["a"], 4), "ms_plain_again": round(med["a2"], 4), "ms_feat": round(med["f"], 4),
+           "ms_plain_min_max": min_max(ms["a"]), "ms_plain_again_min_max": min_max(ms["a2"]), "ms_feat_min_max": min_max(ms["f"]),
+           "feat_over_plain": round(med["f"] / med["a"], 4), "plain_again_over_plain": round(med["a2"] / med["a"], 4),
+           "replace_bytes": info[6], "replace_host_ms": round(statistics.median(host_ms), 4),
+           "replace_host_ms_min_max": min_max(host_ms), "replace_events_ms": round(statistics.median(dev_ms), 4),
+           "replace_events_ms_min_max": min_max(dev_ms), "gate": "none: report only", "pass": mismatches == 0}
+    bank.close()
+    return res
 
 
 def run_case(name, limit, reps, warmup, variant, seed=2026):
+    if name in FEAT_CASES:
+        return run_feat(name, limit, reps, warmup, variant, seed)
     import torch
 
     from mibminet import lib
@@ -118,4 +197,4 @@ def run_case(name, limit, reps, warmup, variant, seed=2026):
 
 
 if __name__ == "__main__":
-    main(__doc__, CASES, run_case, "limit", "bank", lambda res: res["mismatched_epochs"])
+    main(__doc__, {**CASES, **FEAT_CASES}, run_case, "limit", "bank", lambda res: res["mismatched_epochs"])

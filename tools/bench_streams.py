@@ -65,8 +65,13 @@ grouped sets, hop 8, n 16:
                   Verified first: over six ticks every row of (new) equals (b)'s.  Then per tick the push
                   is timed on its own and (new) and (b) take turns going first; the only claim is
                   new <= b on the medians.
+  at_feat         (report only, no gate) at_cues' sessions, pushes and cues: per tick (new)
+                  net_streams_windows_at, (new2) the same call again, so that the run-to-run spread of
+                  one candidate stands beside the numbers, and (feat) net_streams_windows_at_feat, which
+                  also stores 16 T64 bytes of layer-4 activations per window; the three rotate their
+                  order from tick to tick.  Verified first: over six ticks (feat)'s logits equal (new)'s.
 
-  python tools/bench_streams.py [--cases mmmi_64,bci_1024,bci_1024_shuffled,each_equal,each_ragged,f32_tm,f32_tm_montage,at_cues]
+  python tools/bench_streams.py [--cases mmmi_64,bci_1024,bci_1024_shuffled,each_equal,each_ragged,f32_tm,f32_tm_montage,at_cues,at_feat]
                                 [--limit S] [--reps 1000] [--warmup 50] [--variant canonical|plain_bn]
                                 [--out-dir profiles]
 """
@@ -95,11 +100,16 @@ F32_CASES = {  # name: (sessions, sets, C, T, N, n, source rows R): net_streams_
 AT_CASES = {  # name: (sessions, sets, C, T, N, n): net_streams_windows_at
     "at_cues": (1024, 16, 22, 1125, 4, 16),
 }
+AT_FEAT_CASES = {  # name: (sessions, sets, C, T, N, n): net_streams_windows_at_feat beside net_streams_windows_at
+    "at_feat": (1024, 16, 22, 1125, 4, 16),
+}
 
 
 def run_case(name, limit, reps, warmup, variant, seed=2026):
     if name in AT_CASES:
         return run_at(name, limit, reps, warmup, variant, seed)
+    if name in AT_FEAT_CASES:
+        return run_at_feat(name, limit, reps, warmup, variant, seed)
     if name in EACH_CASES:
         return run_each(name, limit, reps, warmup, variant, seed)
     if name in F32_CASES:
@@ -543,6 +553,94 @@ def run_at(name, limit, reps, warmup, variant, seed=2026):
     return res
 
 
+def run_at_feat(name, limit, reps, warmup, variant, seed=2026):
+    import numpy as np
+    import torch
+
+    from mibminet import lib
+    from mibminet.params import ParamSet
+
+    S, n_sets, C, T, N, n = AT_FEAT_CASES[name]
+    S = min(S, limit)
+    n_sets = min(n_sets, S)
+    sets = [ParamSet.synthetic(seed=seed + s, C=C, T=T, N=N, reorder_bn=variant != "plain_bn") for s in range(n_sets)]
+    bank = lib.Bank(sets)
+    set_of = [int(v) for v in np.sort(np.arange(S) * n_sets // S)]
+    st = lib.Streams(bank, set_of, HOP, n)
+    cap = st.cap
+    fill = -(-cap // n)
+    rng = np.random.default_rng(seed)
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    x = torch.randint(-128, 128, (S, C, (fill + VERIFY) * n), dtype=torch.int8, device="cuda", generator=g)
+    A = lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    xa = x[:, :, :n].contiguous()
+    yp = torch.empty((S, max(n // HOP, 1), N), dtype=torch.int8, device="cuda")
+    yn, yf = (torch.empty((S, N), dtype=torch.int8, device="cuda") for _ in range(2))
+    fb = bank.feature_bytes()
+    feat = torch.empty((S, fb), dtype=torch.int8, device="cuda")
+    ses = torch.arange(S, dtype=torch.int32, device="cuda")
+    ons = torch.zeros((S,), dtype=torch.int64, device="cuda")
+    nbad = torch.zeros((1,), dtype=torch.int32, device="cuda")
+
+    def p():
+        rc = A.net_streams_push(st.handle, xa.data_ptr(), 1, n, yp.data_ptr(), nbad.data_ptr(), stream)
+        assert rc == 0, rc
+
+    def new():
+        rc = A.net_streams_windows_at(st.handle, ses.data_ptr(), ons.data_ptr(), S, yn.data_ptr(), nbad.data_ptr(), stream)
+        assert rc == 0, rc
+
+    def with_feat():
+        rc = A.net_streams_windows_at_feat(st.handle, ses.data_ptr(), ons.data_ptr(), S, yf.data_ptr(), feat.data_ptr(),
+                                           nbad.data_ptr(), stream)
+        assert rc == 0, rc
+
+    pos = 0
+    for _ in range(fill):
+        st.push(x[:, :, pos: pos + n].contiguous())
+        pos += n
+    mis = 0
+    for _ in range(VERIFY):
+        xa.copy_(x[:, :, pos: pos + n])
+        p()
+        pos += n
+        ons.copy_(torch.from_numpy(rng.integers(0, cap - T + 1, size=S) + (pos - cap)))
+        new()
+        with_feat()
+        torch.cuda.synchronize()
+        mis += int((yn != yf).any(dim=1).sum().item())
+    assert int(nbad.item()) == 0
+    ms = {"new": [], "new2": [], "feat": []}
+    fns = {"new": new, "new2": new, "feat": with_feat}
+    order = ["new", "feat", "new2"]
+    for r in range(warmup + reps):
+        p()
+        ons.add_(n)
+        for key in order[r % 3:] + order[: r % 3]:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fns[key]()
+            e1.record()
+            e1.synchronize()
+            if r >= warmup:
+                ms[key].append(e0.elapsed_time(e1))
+    torch.cuda.synchronize()
+    assert int(nbad.item()) == 0  # every timed query was valid
+    med = medians(ms)
+    res = {"name": name, "sessions": S, "sets": n_sets, "C": C, "T": T, "N": N, "hop": HOP, "n": n, "queries_per_tick": S,
+           "ring_samples": cap, "feature_bytes_per_window": fb, "ring_bytes_read_per_window": 16 * T, "variant": variant,
+           "verified_ticks": VERIFY, "mismatched_rows": mis, "reps": reps, "warmup": warmup,
+           "device": torch.cuda.get_device_name(0), "ms_windows_at": round(med["new"], 4),
+           "ms_windows_at_again": round(med["new2"], 4), "ms_windows_at_feat": round(med["feat"], 4),
+           "ms_windows_at_min_max": min_max(ms["new"]), "ms_windows_at_again_min_max": min_max(ms["new2"]),
+           "ms_windows_at_feat_min_max": min_max(ms["feat"]), "feat_over_plain": round(med["feat"] / med["new"], 4),
+           "plain_again_over_plain": round(med["new2"] / med["new"], 4), "gates": "none: report only", "pass": mis == 0}
+    st.close()
+    bank.close()
+    return res
+
+
 def b_call(A, bank, recipe, nbad, stream):
     xb, Lx, bsd, ond, W, ws, wsb, yb = recipe
     rc = A.net_model_compute_windows_bank(bank.handle, xb.data_ptr(), 1, Lx, bsd.data_ptr(), ond.data_ptr(), W, yb.data_ptr(),
@@ -552,4 +650,4 @@ def b_call(A, bank, recipe, nbad, stream):
 
 
 if __name__ == "__main__":
-    main(__doc__, {**CASES, **EACH_CASES, **F32_CASES, **AT_CASES}, run_case, "limit", "streams", lambda res: res["mismatched_rows"], reps=1000, warmup=50)
+    main(__doc__, {**CASES, **EACH_CASES, **F32_CASES, **AT_CASES, **AT_FEAT_CASES}, run_case, "limit", "streams", lambda res: res["mismatched_rows"], reps=1000, warmup=50)
