@@ -26,10 +26,14 @@
 //
 // Queries (net_streams_windows_at): the window of a given session from a given sample, read out of
 // the ring as it is, for cue-locked trials.  A retained window is one contiguous run of T bytes like
-// any grid window, so k_forward_ring_at is k_forward_ring's loop over a device list of (session,
-// onset) items with AtRows as its source; it writes logits and *n_bad alone.  Which windows are
-// retained, and for how long, is stream_host.hpp's at_item.  k_forward_ring_at_feat
-// (net_streams_windows_at_feat) is that kernel writing each item's layer-4 activations as well.
+// any grid window, so k_forward_ring_at runs over a device list of (session, onset) items with
+// AtRows as its source; it writes logits and *n_bad alone.  Which windows are retained, and for how
+// long, is stream_host.hpp's at_item.  k_forward_ring_at_feat (net_streams_windows_at_feat) is that
+// kernel writing each item's layer-4 activations as well.
+//
+// One body each: the two layer-1 kernels are layer1_ring, and the four kernels of layers 2-5 are
+// bank::set_loop (forward_bank.hpp) over their sources RingRows, EachRows and AtRows, which say
+// where an item's rows are, whether it is valid and under which set.
 #pragma once
 #include "forward_bank.hpp"
 #include "stream_host.hpp"  // EachRec, plan_each: shared with the host
@@ -41,30 +45,34 @@ using bank::Range64;
 using bank::range_of;
 using bank::Scale;
 
-// Layer 1 of the new samples.  Items are (session s, 16-sample block b of its chunk), session-major
-// (item = s nb + b); wave g of gridDim.x NW1 takes the contiguous items range_of(g, gridDim.x NW1, S nb)
-// with a current set per wave, as bank::k_layer1_rec_bank does.  x: the S chunks, contiguous, in
-// layout L ([n][C] int8, [C][n] int8, [C][n] float32, [n][C] float32) at any byte alignment (float32:
-// 4); the view is one session's chunk, the row stride of the channel-major layouts n (so a time-major
-// fragment's K-slots past C read the session's own next sample, or zeros past its last).  A set index is compared
-// unsigned before any address is formed from it; a session whose index is outside the bank stores
-// nothing.  Stores: sample 16 b + 4 g + r < n of the chunk goes to position (p0 + 16 b + 4 g + r)
-// mod cap of the lane's row and to that + cap.  Samples >= n of a partial last block are not
-// stored: their positions hold live older samples.  Where p0 is a multiple of 4 a lane's four
-// positions do not cross the seam (cap is a multiple of 4) and, when all four samples exist, leave
-// as two dwords; otherwise as bytes.
-template <int L, bool XR, bool CB>
-__global__ __launch_bounds__(win::NT1) void k_layer1_ring(const gen::GenParams* __restrict__ sets, int n_sets,
-                                                          const int* __restrict__ set_of,
-                                                          const Scale* __restrict__ scales,
-                                                          const int8_t* __restrict__ x, int8_t* __restrict__ ring,
-                                                          int items, int nb, int n, int p0, int cap) {
+// Layer 1 of the new samples, the body of k_layer1_ring and k_layer1_ring_each.  Items are (session
+// s, 16-sample block b of its chunk), session-major (item = s nb + b); wave g of gridDim.x NW1 takes
+// the contiguous items range_of(g, gridDim.x NW1, S nb) with a current set per wave, as
+// bank::k_layer1_rec_bank does.  x: the S chunks of n_view samples each, contiguous, in layout L
+// ([n][C] int8, [C][n] int8, [C][n] float32, [n][C] float32) at any byte alignment (float32: 4); the
+// view is one session's chunk, the row stride of the channel-major layouts n_view (so a time-major
+// fragment's K-slots past C read the session's own next sample, or zeros past its last).  A set
+// index is compared unsigned before any address is formed from it; a session whose index is outside
+// the bank stores nothing.  Stores: sample 16 b + 4 g + r < n of the chunk goes to position
+// (p0 + 16 b + 4 g + r) mod cap of the lane's row and to that + cap.  Samples >= n of a partial last
+// block are not stored: their positions hold live older samples.  Where p0 is a multiple of 4 a
+// lane's four positions do not cross the seam (cap is a multiple of 4) and, when all four samples
+// exist, leave as two dwords; otherwise as bytes.
+// EACH: n and p0 are the session's own, read from its plan record (wave-uniform: one scalar load;
+// k_stream_plan validated the record, so n <= n_view = n_max and p0 < cap), and a wave skips the
+// blocks b >= ceil(n / 16); samples >= n are read inside the session's slot and not stored.
+template <int L, bool XR, bool CB, bool EACH>
+__device__ __forceinline__ void layer1_ring(const gen::GenParams* __restrict__ sets, int n_sets,
+                                            const int* __restrict__ set_of, const Scale* __restrict__ scales,
+                                            const int8_t* __restrict__ x, int8_t* __restrict__ ring,
+                                            const EachRec* __restrict__ plan, int items, int nb, int n_view, int n,
+                                            int p0, int cap) {
   __shared__ v4i stg_v[win::NW1 * 64];  // channel-major transpose staging, 1 KB per wave
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int8_t* stg = (int8_t*)stg_v + 1024 * wave;
   const int C = sets->C;  // every set's
-  const unsigned chunk = gen::elem_bytes(L) * (unsigned)C * (unsigned)n;  // <= 2^24
+  const unsigned chunk = gen::elem_bytes(L) * (unsigned)C * (unsigned)n_view;  // <= 2^24
   const int g = lane >> 4;
   const Range64 rg = range_of(blockIdx.x * win::NW1 + (unsigned)wave, gridDim.x * win::NW1, (unsigned long long)items);
   const int end = (int)rg.hi;
@@ -73,6 +81,12 @@ __global__ __launch_bounds__(win::NT1) void k_layer1_ring(const gen::GenParams* 
   int cur = -1;
   for (int it = (int)rg.lo; it < end; it++) {  // wave-uniform
     const int s = it / nb, b = it - s * nb;
+    if constexpr (EACH) {
+      const EachRec rec = plan[s];
+      n = rec.n;
+      p0 = rec.p0;
+      if (16 * b >= n) continue;
+    }
     const int set = set_of[s];
     if ((unsigned)set >= (unsigned)n_sets) continue;
     if (set != cur) {
@@ -86,7 +100,7 @@ __global__ __launch_bounds__(win::NT1) void k_layer1_ring(const gen::GenParams* 
     }
     const gen::View v = gen::make_view(x + (size_t)s * chunk, chunk);
     int y[4];
-    gen::l1_outputs<L, XR, CB>(gen::l1_fetch<L>(v, b, C, n, lane, qs, qy), stg, k, lane, y);
+    gen::l1_outputs<L, XR, CB>(gen::l1_fetch<L>(v, b, C, n_view, lane, qs, qy), stg, k, lane, y);
     const unsigned w = gen::sat4(y[0], y[1], y[2], y[3]);
     int8_t* row = ring + ((size_t)s * 16 + (size_t)(lane & 15)) * (size_t)(2 * cap);
     const int t0 = 16 * b + 4 * g;  // the lane's first sample of the chunk
@@ -109,13 +123,19 @@ __global__ __launch_bounds__(win::NT1) void k_layer1_ring(const gen::GenParams* 
   }
 }
 
-// An each-group's layer 1 (net_streams_push_each).  A SIBLING OF k_layer1_ring, kept in step with it
-// by hand: the same body with n and p0 per session, read from the session's plan record (wave-
-// uniform: one scalar load; k_stream_plan validated the record, so n <= n_max and p0 < cap).  A
-// body shared by both changed the code generated for k_layer1_ring (tools/asm_cmp.py), so it is a
-// copy.  Items are (s, b) with b < nb = ceil(n_max / 16), session-major; a wave skips the blocks
-// b >= ceil(n[s] / 16).  The view is the session's fixed slot of n_max samples, the row stride of
-// the channel-major layouts n_max; samples >= n[s] are read inside the slot and not stored.
+// A uniform group's layer 1 (net_streams_push): every session's chunk is n samples from ring
+// position p0.
+template <int L, bool XR, bool CB>
+__global__ __launch_bounds__(win::NT1) void k_layer1_ring(const gen::GenParams* __restrict__ sets, int n_sets,
+                                                          const int* __restrict__ set_of,
+                                                          const Scale* __restrict__ scales,
+                                                          const int8_t* __restrict__ x, int8_t* __restrict__ ring,
+                                                          int items, int nb, int n, int p0, int cap) {
+  layer1_ring<L, XR, CB, false>(sets, n_sets, set_of, scales, x, ring, nullptr, items, nb, n, n, p0, cap);
+}
+
+// An each-group's layer 1 (net_streams_push_each): items are (s, b) with b < nb = ceil(n_max / 16),
+// the view is the session's fixed slot of n_max samples.
 template <int L, bool XR, bool CB>
 __global__ __launch_bounds__(win::NT1) void k_layer1_ring_each(const gen::GenParams* __restrict__ sets, int n_sets,
                                                                const int* __restrict__ set_of,
@@ -123,57 +143,7 @@ __global__ __launch_bounds__(win::NT1) void k_layer1_ring_each(const gen::GenPar
                                                                const int8_t* __restrict__ x, int8_t* __restrict__ ring,
                                                                const EachRec* __restrict__ plan, int items, int nb,
                                                                int n_max, int cap) {
-  __shared__ v4i stg_v[win::NW1 * 64];  // channel-major transpose staging, 1 KB per wave
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int8_t* stg = (int8_t*)stg_v + 1024 * wave;
-  const int C = sets->C;  // every set's
-  const unsigned slot = gen::elem_bytes(L) * (unsigned)C * (unsigned)n_max;  // <= 2^24
-  const int g = lane >> 4;
-  const Range64 rg = range_of(blockIdx.x * win::NW1 + (unsigned)wave, gridDim.x * win::NW1, (unsigned long long)items);
-  const int end = (int)rg.hi;
-  gen::L1C k{};
-  float qs = 0.0f, qy = 0.0f;
-  int cur = -1;
-  for (int it = (int)rg.lo; it < end; it++) {  // wave-uniform
-    const int s = it / nb, b = it - s * nb;
-    const EachRec rec = plan[s];
-    const int n = rec.n, p0 = rec.p0;
-    if (16 * b >= n) continue;
-    const int set = set_of[s];
-    if ((unsigned)set >= (unsigned)n_sets) continue;
-    if (set != cur) {
-      cur = set;
-      k = gen::l1_consts<L>(sets + set, lane);
-      if constexpr (gen::is_float(L)) {
-        const Scale q = scales[set];
-        qs = q.qs;
-        qy = q.qy;
-      }
-    }
-    const gen::View v = gen::make_view(x + (size_t)s * slot, slot);
-    int y[4];
-    gen::l1_outputs<L, XR, CB>(gen::l1_fetch<L>(v, b, C, n_max, lane, qs, qy), stg, k, lane, y);
-    const unsigned w = gen::sat4(y[0], y[1], y[2], y[3]);
-    int8_t* row = ring + ((size_t)s * 16 + (size_t)(lane & 15)) * (size_t)(2 * cap);
-    const int t0 = 16 * b + 4 * g;  // the lane's first sample of the slot
-    int q = p0 + t0;                // < 2 cap: p0 < cap, t0 < n <= cap
-    q = q >= cap ? q - cap : q;
-    if ((p0 & 3) == 0 && t0 + 3 < n) {
-      *(unsigned*)(row + q) = w;
-      *(unsigned*)(row + q + cap) = w;
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        if (t0 + r < n) {
-          const int qr = q + r >= cap ? q + r - cap : q + r;
-          const int8_t byte = (int8_t)(w >> (8 * r));
-          row[qr] = byte;
-          row[qr + cap] = byte;
-        }
-      }
-    }
-  }
+  layer1_ring<L, XR, CB, true>(sets, n_sets, set_of, scales, x, ring, plan, items, nb, n_max, 0, 0, cap);
 }
 
 // The first kernel of an each-group's push: one thread per session.  It reads cnt_in[s] and pos[s],
@@ -233,77 +203,33 @@ struct RingRows {
       win::copy_rows(win::window_view(ring + (size_t)it.session * (size_t)(32 * cap), it.at, t, 2 * cap), y1, y1s, t, NB1,
                      2 * cap, tid, gen::NT - 64);
   }
+  __device__ __forceinline__ void rows_last(const Item&) const {}
+  static constexpr bool SKIP = false;
+  __device__ __forceinline__ void on_switch(int, int) const {}
 };
 
-// bank::k_forward_y1_bank's loop over the W = S k windows of a push, logits [S][k][N]: the
-// contiguous ranges (session-major items: a range changes sets when it changes sessions), item
-// i - 1 finished on its own set before a switch with its two barriers, an invalid window keeps the
-// current set, the zero pads written once.  The loop is a copy, as that kernel's is of
-// bank::k_forward_ep_bank's.
+// bank::set_loop over the W = S k windows of a push, logits [S][k][N] (session-major items: a range
+// changes sets when it changes sessions).
 template <bool RB, bool XR, bool CB>
 __global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_forward_ring(
     const gen::GenParams* __restrict__ sets, int n_sets, const int8_t* __restrict__ ring,
     const long long* __restrict__ origin, const int* __restrict__ set_of, int8_t* __restrict__ out,
     int* __restrict__ n_bad, int W, int k, long long first, long long hop, int first_mod, int cap) {
-  using namespace gen;
   extern __shared__ v4i smem_v[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // the geometry is every set's: set 0 stands for it until the first switch
-  const Lds m = lds_of(sets, (int8_t*)smem_v, 3);
-  const int N = sets->N;
-  v4i* z = (v4i*)m.y1;  // the zero pads (gen::setup); the first switch's barriers publish them
-  for (int i = tid; i < m.cv.sg / 16; i += NT) z[i] = (v4i){0, 0, 0, 0};
+  const gen::Lds m = bank::carve_and_pads(sets, (int8_t*)smem_v, 3, tid);
   RingRows<RB || XR> src{ring, origin, set_of, sets,      first, hop, k,  first_mod,
                          cap,  n_sets, sets->T, sets->NB1, m.cv.y1s, tid, m.y1};
-  L2C k2;
-  const Range64 rg = range_of(blockIdx.x, gridDim.x, (unsigned long long)W);
-  const int end = (int)rg.hi;
-  int cur = -1;   // the set in registers and LDS
-  int prev = -1;  // gen::item_loop's: i valid, -2 - i invalid, -1 none
-  for (int i = (int)rg.lo;; i++) {
-    const bool more = i < end;  // uniform over the workgroup
-    const auto it = src.open(i, more);
-    const int need = it.valid ? it.s : max(cur, 0);  // an invalid window stays where the workgroup is
-    if (more && need != cur) {
-      // window i - 1 ends on its own set before any of that set's state goes
-      if (wave == NW - 1) finish_prev<RB, XR, CB, true>(src.gp, m, out, n_bad, prev, N, lane);
-      prev = -1;
-      __syncthreads();
-      cur = need;
-      src.gp = sets + cur;
-      // the reload's addresses are derived here, per switch, from an opaque copy of the thread
-      // index (bank::k_forward_ep_bank)
-      int t;
-      asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
-      set_l2c(src.gp, k2, wave, t & 63);
-      set_lds(src.gp, m, t);
-      __syncthreads();
-    }
-    const GenParams* __restrict__ gp = src.gp;
-    if (wave < NW - 1) {
-      if (more) src.rows(it);
-    } else {
-      finish_prev<RB, XR, CB, true>(gp, m, out, n_bad, prev, N, lane);
-    }
-    if (!more) break;
-    __syncthreads();  // A
-    layer2<RB, XR, CB>(gp, m.y1, m.cv.y1s, m.y2, m.cv.y2s, k2, wave, lane);
-    wg::wave_sync_lds();  // layer 3 of filter f reads only y2 row f, written by this wave
-    __builtin_amdgcn_s_setprio(wg::PRIO_L3);
-    layer3<XR, CB>(gp, m.sg, m.y2, m.cv.y2s, m.y3, wave, lane);
-    __builtin_amdgcn_s_setprio(0);
-    __syncthreads();  // B
-    prev = it.valid ? i : -2 - i;
-  }
+  bank::set_loop<RB, XR, CB, false>(sets, m, src, out, nullptr, n_bad, W, tid, wave, lane);
 }
 
 // Where the loop finds item i = s kmax + j of an each-group's push: window j of those session s
 // completes in it.  open() reads the session's record and set[s] (wave-uniform: scalar loads).  The
 // item exists iff j < k[s] (and the set is in the bank, which create and restart see to): its rows
 // start at ring position (at0 + j hop) mod cap, one conditional subtraction (at0 < cap and
-// j hop < n[s] <= cap).  An item that does not exist is no invalid window: the loop skips it and
-// nothing is written.
+// j hop < n[s] <= cap).  An item that does not exist is no invalid window: bank::set_loop passes
+// over it (SKIP) and nothing is written.
 template <bool HT>
 struct EachRows {
   const int8_t* ring;
@@ -331,68 +257,25 @@ struct EachRows {
     win::copy_rows(win::window_view(ring + (size_t)it.session * (size_t)(32 * cap), it.at, t, 2 * cap), y1, y1s, t, NB1,
                    2 * cap, tid, gen::NT - 64);
   }
+  __device__ __forceinline__ void rows_last(const Item&) const {}
+  static constexpr bool SKIP = true;
+  __device__ __forceinline__ void on_switch(int, int) const {}
 };
 
-// k_forward_ring's loop over the S kmax items of an each-group's push, logits [S][kmax][N]: row
-// s kmax + j is written iff the item exists.  A sibling, not a shared body: here an item may be
-// absent, which the loop passes over before any barrier (the records are uniform over the
-// workgroup), leaving `prev` as it is, so the last item that did exist is still finished, on its own
-// set, at the next switch or on the pass past the last item.  Every item that is not skipped is
-// valid, so prev is i or -1 and n_bad is never counted here.
+// bank::set_loop over the S kmax items of an each-group's push, logits [S][kmax][N]: row s kmax + j
+// is written iff the item exists (EachRows::SKIP).  Every item that is not skipped is valid, so
+// nothing is counted here.
 template <bool RB, bool XR, bool CB>
 __global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_forward_ring_each(
     const gen::GenParams* __restrict__ sets, int n_sets, const int8_t* __restrict__ ring,
     const EachRec* __restrict__ plan, const int* __restrict__ set_of, int8_t* __restrict__ out, int W, int kmax, int hop,
     int cap) {
-  using namespace gen;
   extern __shared__ v4i smem_v[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const Lds m = lds_of(sets, (int8_t*)smem_v, 3);
-  const int N = sets->N;
-  v4i* z = (v4i*)m.y1;  // the zero pads (gen::setup); the first switch's barriers publish them
-  for (int i = tid; i < m.cv.sg / 16; i += NT) z[i] = (v4i){0, 0, 0, 0};
+  const gen::Lds m = bank::carve_and_pads(sets, (int8_t*)smem_v, 3, tid);
   EachRows<RB || XR> src{ring, plan, set_of, sets, kmax, hop, cap, n_sets, sets->T, sets->NB1, m.cv.y1s, tid, m.y1};
-  L2C k2;
-  const Range64 rg = range_of(blockIdx.x, gridDim.x, (unsigned long long)W);
-  const int end = (int)rg.hi;
-  int cur = -1;   // the set in registers and LDS
-  int prev = -1;  // the item whose layers 4-5 are owed, -1 none
-  for (int i = (int)rg.lo;; i++) {
-    const bool more = i < end;  // uniform over the workgroup
-    const auto it = src.open(i, more);
-    if (more && !it.valid) continue;  // uniform over the workgroup: an absent item
-    if (more && it.s != cur) {
-      // the last item ends on its own set before any of that set's state goes
-      if (wave == NW - 1) finish_prev<RB, XR, CB, true>(src.gp, m, out, nullptr, prev, N, lane);
-      prev = -1;
-      __syncthreads();
-      cur = it.s;
-      src.gp = sets + cur;
-      // the reload's addresses are derived here, per switch, from an opaque copy of the thread
-      // index (bank::k_forward_ep_bank)
-      int t;
-      asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
-      set_l2c(src.gp, k2, wave, t & 63);
-      set_lds(src.gp, m, t);
-      __syncthreads();
-    }
-    const GenParams* __restrict__ gp = src.gp;
-    if (wave < NW - 1) {
-      if (more) src.rows(it);
-    } else {
-      finish_prev<RB, XR, CB, true>(gp, m, out, nullptr, prev, N, lane);
-    }
-    if (!more) break;
-    __syncthreads();  // A
-    layer2<RB, XR, CB>(gp, m.y1, m.cv.y1s, m.y2, m.cv.y2s, k2, wave, lane);
-    wg::wave_sync_lds();  // layer 3 of filter f reads only y2 row f, written by this wave
-    __builtin_amdgcn_s_setprio(wg::PRIO_L3);
-    layer3<XR, CB>(gp, m.sg, m.y2, m.cv.y2s, m.y3, wave, lane);
-    __builtin_amdgcn_s_setprio(0);
-    __syncthreads();  // B
-    prev = i;
-  }
+  bank::set_loop<RB, XR, CB, false>(sets, m, src, out, nullptr, nullptr, W, tid, wave, lane);
 }
 
 // Where the loop finds item i of a query (net_streams_windows_at): the window of session
@@ -441,135 +324,53 @@ struct AtRows {
       win::copy_rows(win::window_view(ring + (size_t)it.session * (size_t)(32 * cap), it.at, t, 2 * cap), y1, y1s, t, NB1,
                      2 * cap, tid, gen::NT - 64);
   }
+  __device__ __forceinline__ void rows_last(const Item&) const {}
+  static constexpr bool SKIP = false;
+  __device__ __forceinline__ void on_switch(int, int) const {}
 };
 
-// k_forward_ring's loop over the W items of a query, logits [W][N].  A SIBLING OF k_forward_ring,
-// kept in step with it by hand, for the reason k_forward_ring_each gives: a body shared with it
-// changed the code generated for it (tools/asm_cmp.py).  The contiguous ranges, item i - 1 finished
-// on its own set before a switch with its two barriers, an invalid item keeps the current set and is
-// finished as zeros and a count in *n_bad, the zero pads written once.  Items are in the caller's
-// order: sorted by session a range changes sets as seldom as a push's does.  It reads the rings,
-// the sets and the origins or positions, and writes out and *n_bad alone.
+// The body of k_forward_ring_at and k_forward_ring_at_feat: bank::set_loop over the W items of a
+// query.  An invalid item keeps the current set and is finished as zeros and a count in *n_bad.
+// Items are in the caller's order: sorted by session a range changes sets as seldom as a push's does.
+template <bool RB, bool XR, bool CB, bool EACH, bool FEAT>
+__device__ __forceinline__ void forward_ring_at(const gen::GenParams* __restrict__ sets, int n_sets,
+                                                const int8_t* __restrict__ ring, const int* __restrict__ session_of,
+                                                const long long* __restrict__ onsets,
+                                                const long long* __restrict__ lim, const int* __restrict__ set_of,
+                                                int8_t* __restrict__ out, int8_t* __restrict__ feat,
+                                                int* __restrict__ n_bad, int W, int S, long long pos, int pos_mod,
+                                                int cap) {
+  extern __shared__ v4i smem_v[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const gen::Lds m = bank::carve_and_pads(sets, (int8_t*)smem_v, 3, tid);
+  AtRows<RB || XR, EACH> src{ring, session_of, onsets, lim,     set_of,    sets,     pos, pos_mod,
+                             S,    cap,        n_sets, sets->T, sets->NB1, m.cv.y1s, tid, m.y1};
+  bank::set_loop<RB, XR, CB, FEAT>(sets, m, src, out, feat, n_bad, W, tid, wave, lane);
+}
+
+// The windows of a query, logits [W][N].  It reads the rings, the sets and the origins or positions,
+// and writes out and *n_bad alone.
 template <bool RB, bool XR, bool CB, bool EACH>
 __global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_forward_ring_at(
     const gen::GenParams* __restrict__ sets, int n_sets, const int8_t* __restrict__ ring,
     const int* __restrict__ session_of, const long long* __restrict__ onsets, const long long* __restrict__ lim,
     const int* __restrict__ set_of, int8_t* __restrict__ out, int* __restrict__ n_bad, int W, int S, long long pos,
     int pos_mod, int cap) {
-  using namespace gen;
-  extern __shared__ v4i smem_v[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // the geometry is every set's: set 0 stands for it until the first switch
-  const Lds m = lds_of(sets, (int8_t*)smem_v, 3);
-  const int N = sets->N;
-  v4i* z = (v4i*)m.y1;  // the zero pads (gen::setup); the first switch's barriers publish them
-  for (int i = tid; i < m.cv.sg / 16; i += NT) z[i] = (v4i){0, 0, 0, 0};
-  AtRows<RB || XR, EACH> src{ring, session_of, onsets, lim,     set_of,    sets,     pos, pos_mod,
-                             S,    cap,        n_sets, sets->T, sets->NB1, m.cv.y1s, tid, m.y1};
-  L2C k2;
-  const Range64 rg = range_of(blockIdx.x, gridDim.x, (unsigned long long)W);
-  const int end = (int)rg.hi;
-  int cur = -1;   // the set in registers and LDS
-  int prev = -1;  // gen::item_loop's: i valid, -2 - i invalid, -1 none
-  for (int i = (int)rg.lo;; i++) {
-    const bool more = i < end;  // uniform over the workgroup
-    const auto it = src.open(i, more);
-    const int need = it.valid ? it.s : max(cur, 0);  // an invalid item stays where the workgroup is
-    if (more && need != cur) {
-      // item i - 1 ends on its own set before any of that set's state goes
-      if (wave == NW - 1) finish_prev<RB, XR, CB, true>(src.gp, m, out, n_bad, prev, N, lane);
-      prev = -1;
-      __syncthreads();
-      cur = need;
-      src.gp = sets + cur;
-      // the reload's addresses are derived here, per switch, from an opaque copy of the thread
-      // index (bank::k_forward_ep_bank)
-      int t;
-      asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
-      set_l2c(src.gp, k2, wave, t & 63);
-      set_lds(src.gp, m, t);
-      __syncthreads();
-    }
-    const GenParams* __restrict__ gp = src.gp;
-    if (wave < NW - 1) {
-      if (more) src.rows(it);
-    } else {
-      finish_prev<RB, XR, CB, true>(gp, m, out, n_bad, prev, N, lane);
-    }
-    if (!more) break;
-    __syncthreads();  // A
-    layer2<RB, XR, CB>(gp, m.y1, m.cv.y1s, m.y2, m.cv.y2s, k2, wave, lane);
-    wg::wave_sync_lds();  // layer 3 of filter f reads only y2 row f, written by this wave
-    __builtin_amdgcn_s_setprio(wg::PRIO_L3);
-    layer3<XR, CB>(gp, m.sg, m.y2, m.cv.y2s, m.y3, wave, lane);
-    __builtin_amdgcn_s_setprio(0);
-    __syncthreads();  // B
-    prev = it.valid ? i : -2 - i;
-  }
+  forward_ring_at<RB, XR, CB, EACH, false>(sets, n_sets, ring, session_of, onsets, lim, set_of, out, nullptr, n_bad, W, S,
+                                           pos, pos_mod, cap);
 }
 
 // k_forward_ring_at with the layer-4 activations beside the logits (net_streams_windows_at_feat):
-// feat [W][16][T64] int8, 16-byte aligned.  A SIBLING OF k_forward_ring_at, kept in step with it by
-// hand: the same loop with gen::finish_prev_feat where that kernel has gen::finish_prev
-// (bank::k_forward_ep_bank_feat says why it is no flag).  It writes out, feat and *n_bad alone.
+// feat [W][16][T64] int8, 16-byte aligned.  It writes out, feat and *n_bad alone.
 template <bool RB, bool XR, bool CB, bool EACH>
 __global__ __launch_bounds__(gen::NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_forward_ring_at_feat(
     const gen::GenParams* __restrict__ sets, int n_sets, const int8_t* __restrict__ ring,
     const int* __restrict__ session_of, const long long* __restrict__ onsets, const long long* __restrict__ lim,
     const int* __restrict__ set_of, int8_t* __restrict__ out, int8_t* __restrict__ feat, int* __restrict__ n_bad, int W,
     int S, long long pos, int pos_mod, int cap) {
-  using namespace gen;
-  extern __shared__ v4i smem_v[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // the geometry is every set's: set 0 stands for it until the first switch
-  const Lds m = lds_of(sets, (int8_t*)smem_v, 3);
-  const int N = sets->N, T64 = sets->T64;
-  v4i* z = (v4i*)m.y1;  // the zero pads (gen::setup); the first switch's barriers publish them
-  for (int i = tid; i < m.cv.sg / 16; i += NT) z[i] = (v4i){0, 0, 0, 0};
-  AtRows<RB || XR, EACH> src{ring, session_of, onsets, lim,     set_of,    sets,     pos, pos_mod,
-                             S,    cap,        n_sets, sets->T, sets->NB1, m.cv.y1s, tid, m.y1};
-  L2C k2;
-  const Range64 rg = range_of(blockIdx.x, gridDim.x, (unsigned long long)W);
-  const int end = (int)rg.hi;
-  int cur = -1;   // the set in registers and LDS
-  int prev = -1;  // gen::item_loop's: i valid, -2 - i invalid, -1 none
-  for (int i = (int)rg.lo;; i++) {
-    const bool more = i < end;  // uniform over the workgroup
-    const auto it = src.open(i, more);
-    const int need = it.valid ? it.s : max(cur, 0);  // an invalid item stays where the workgroup is
-    if (more && need != cur) {
-      // item i - 1 ends on its own set before any of that set's state goes
-      if (wave == NW - 1) finish_prev_feat<RB, XR, CB>(src.gp, m, out, feat, n_bad, prev, N, T64, lane);
-      prev = -1;
-      __syncthreads();
-      cur = need;
-      src.gp = sets + cur;
-      // the reload's addresses are derived here, per switch, from an opaque copy of the thread
-      // index (bank::k_forward_ep_bank)
-      int t;
-      asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
-      set_l2c(src.gp, k2, wave, t & 63);
-      set_lds(src.gp, m, t);
-      __syncthreads();
-    }
-    const GenParams* __restrict__ gp = src.gp;
-    if (wave < NW - 1) {
-      if (more) src.rows(it);
-    } else {
-      finish_prev_feat<RB, XR, CB>(gp, m, out, feat, n_bad, prev, N, T64, lane);
-    }
-    if (!more) break;
-    __syncthreads();  // A
-    layer2<RB, XR, CB>(gp, m.y1, m.cv.y1s, m.y2, m.cv.y2s, k2, wave, lane);
-    wg::wave_sync_lds();  // layer 3 of filter f reads only y2 row f, written by this wave
-    __builtin_amdgcn_s_setprio(wg::PRIO_L3);
-    layer3<XR, CB>(gp, m.sg, m.y2, m.cv.y2s, m.y3, wave, lane);
-    __builtin_amdgcn_s_setprio(0);
-    __syncthreads();  // B
-    prev = it.valid ? i : -2 - i;
-  }
+  forward_ring_at<RB, XR, CB, EACH, true>(sets, n_sets, ring, session_of, onsets, lim, set_of, out, feat, n_bad, W, S,
+                                          pos, pos_mod, cap);
 }
 
 // net_streams_restart: from the pushes enqueued after it session i is decoded by `set`, and no

@@ -146,6 +146,9 @@ struct Rows {
     if (it.valid) copy_rows(window_view(ws, it.on, t, rs), y1, y1s, t, NB1, rs, tid, gen::NT - 64);
   }
   __device__ __forceinline__ void rows_last(const Item&) const {}
+  // BK, for bank::set_loop: an invalid window is finished as zeros, and the source holds nothing of a set
+  static constexpr bool SKIP = false;
+  __device__ __forceinline__ void on_switch(int, int) const {}
 };
 
 // Fused forward over W windows of a recording whose layer-1 output is in ws, logits [W][N]:

@@ -224,6 +224,13 @@ int launch_items(const DeviceState& ds, K kern, int lds, size_t items, hipStream
   hipLaunchKernelGGL(kern, dim3(gen_grid(ds, (const void*)kern, lds, items)), dim3(gen::NT), (size_t)lds, st, args...);
   return hip_err(hipGetLastError());
 }
+// The launch of a layer-1 kernel over `wgs` workgroups of win::NT1 threads: 8 workgroups of 4 waves
+// fill a CU.
+template <class K, class... A>
+int launch_l1(const DeviceState& ds, K kern, size_t wgs, hipStream_t st, A... args) {
+  hipLaunchKernelGGL(kern, dim3((unsigned)capped_grid(ds, wgs, 8)), dim3(win::NT1), 0, st, args...);
+  return hip_err(hipGetLastError());
+}
 
 // hg: the host copy of the gen::GenParams p points to (the general path reads its dimensions and
 // flags).  Int8 trials that fit in LDS run the staged instantiation (gen::carve_of).
@@ -292,10 +299,9 @@ int launch_windows(DeviceState& ds, const gen::GenParams& hg, const void* p, con
   return with_layout<true>(g.layout, [&](auto lc) {
     return with_flags(hg, [&](auto rb, auto xr, auto cb) {
       constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
-      // 8 workgroups of 4 waves fill a CU
-      hipLaunchKernelGGL((win::k_layer1_rec<decltype(lc)::value, XR, CB>), dim3((unsigned)capped_grid(ds, g.wgs, 8)),
-                         dim3(win::NT1), 0, st, gp, x, ws, (int)Lr, g.rs, qs, recip_scale(qs));
-      if (const int rc = hip_err(hipGetLastError())) return rc;
+      if (const int rc = launch_l1(ds, win::k_layer1_rec<decltype(lc)::value, XR, CB>, g.wgs, st, gp, x, ws, (int)Lr,
+                                   g.rs, qs, recip_scale(qs)))
+        return rc;
       // hop > INT32_MAX: a single window (hop <= L - T < 2^27 otherwise), at sample 0 whatever hop is
       const int rc = onsets ? launch_items(ds, win::k_forward_y1_at<RB, XR, CB>, lds, g.W, st, gp, (const int8_t*)ws,
                                            (const long long*)onsets, y, (int*)n_bad, (int)g.W, g.last, g.rs)
@@ -464,6 +470,18 @@ int bank_replace(net_bank* b, size_t set, const void* blob, size_t len, float sc
   return NET_OK;
 }
 
+// The device view of a bank's upload on sc's device: the images, their count and, for float input
+// (f32), the scales that follow them.
+struct BankView {
+  const gen::GenParams* sets;
+  int n_sets;
+  const bank::Scale* scales;
+};
+BankView bank_view(const DeviceScope& sc, const net_bank& b, bool f32) {
+  const auto* sets = (const gen::GenParams*)sc.image;
+  return BankView{sets, (int)b.sets.size(), f32 ? (const bank::Scale*)(sets + b.sets.size()) : nullptr};
+}
+
 // epochs_async on a bank: the same checks in the same order, C and T the bank's; then the set
 // indices' and, for float input, the bank's scales.  with_feat: the _feat entries, which also write
 // the layer-4 activations to feat (its check stands with y's: check_epochs' are all NET_ERR_INVALID).
@@ -482,23 +500,18 @@ int bank_epochs_async(const net_bank* b, const void* x, bool f32, size_t n_elems
   if (E == 0) return NET_OK;
   DeviceScope sc(device, *b);
   if (sc.rc) return sc.rc;
-  const auto* sets = (const gen::GenParams*)sc.image;
-  const auto* scales = f32 ? (const bank::Scale*)(sets + b->sets.size()) : nullptr;
+  const BankView v = bank_view(sc, *b, f32);
   return with_flags(hg, [&](auto rb, auto xr, auto cb) {
-    auto go = [&](auto kern) {
-      return launch_items(sc.ds, kern, epochs_lds(hg), E, (hipStream_t)stream, sets, (int)b->sets.size(), (const int*)set_of, scales,
-                          (const int8_t*)x, (const long long*)onsets, y, (int*)n_bad, (int)E, g.last, g.span_bytes,
-                          (unsigned long long)row_stride, g.tab);
-    };
-    auto go_feat = [&](auto kern) {
-      return launch_items(sc.ds, kern, epochs_lds(hg), E, (hipStream_t)stream, sets, (int)b->sets.size(), (const int*)set_of, scales,
-                          (const int8_t*)x, (const long long*)onsets, y, feat, (int*)n_bad, (int)E, g.last, g.span_bytes,
-                          (unsigned long long)row_stride, g.tab);
+    // f: nothing, or the feature rows' pointer, which the _feat kernels take after y
+    auto go = [&](auto kern, auto... f) {
+      return launch_items(sc.ds, kern, epochs_lds(hg), E, (hipStream_t)stream, v.sets, v.n_sets, (const int*)set_of,
+                          v.scales, (const int8_t*)x, (const long long*)onsets, y, f..., (int*)n_bad, (int)E, g.last,
+                          g.span_bytes, (unsigned long long)row_stride, g.tab);
     };
     constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
     if (with_feat)
-      return f32 ? go_feat(bank::k_forward_ep_bank_feat<gen::F32, RB, XR, CB>)
-                 : go_feat(bank::k_forward_ep_bank_feat<gen::CT, RB, XR, CB>);
+      return f32 ? go(bank::k_forward_ep_bank_feat<gen::F32, RB, XR, CB>, feat)
+                 : go(bank::k_forward_ep_bank_feat<gen::CT, RB, XR, CB>, feat);
     return f32 ? go(bank::k_forward_ep_bank<gen::F32, RB, XR, CB>) : go(bank::k_forward_ep_bank<gen::CT, RB, XR, CB>);
   });
 }
@@ -519,19 +532,15 @@ int bank_windows_async(const net_bank* b, const void* x, int arg_layout, bool f3
   if (W == 0) return NET_OK;
   DeviceScope sc(device, *b);
   if (sc.rc) return sc.rc;
-  const auto* sets = (const gen::GenParams*)sc.image;
-  const auto* scales = f32 ? (const bank::Scale*)(sets + b->sets.size()) : nullptr;
-  const int n_sets = (int)b->sets.size();
+  const BankView v = bank_view(sc, *b, f32);
   const hipStream_t st = (hipStream_t)stream;
   return with_layout<true>(g.layout, [&](auto lc) {
     return with_flags(hg, [&](auto rb, auto xr, auto cb) {
       constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
-      // 8 workgroups of 4 waves fill a CU (launch_windows)
-      hipLaunchKernelGGL((bank::k_layer1_rec_bank<decltype(lc)::value, XR, CB>),
-                         dim3((unsigned)capped_grid(sc.ds, g.wgs, 8)), dim3(win::NT1), 0, st, sets, n_sets,
-                         (const int*)blk_set, scales, (const int8_t*)x, (int8_t*)ws, (int)L, g.rs);
-      if (const int rc = hip_err(hipGetLastError())) return rc;
-      return launch_items(sc.ds, bank::k_forward_y1_bank<RB, XR, CB>, windows_lds(hg), W, st, sets, n_sets,
+      if (const int rc = launch_l1(sc.ds, bank::k_layer1_rec_bank<decltype(lc)::value, XR, CB>, g.wgs, st, v.sets,
+                                   v.n_sets, (const int*)blk_set, v.scales, (const int8_t*)x, (int8_t*)ws, (int)L, g.rs))
+        return rc;
+      return launch_items(sc.ds, bank::k_forward_y1_bank<RB, XR, CB>, windows_lds(hg), W, st, v.sets, v.n_sets,
                           (const int*)blk_set, (const int8_t*)ws, (const long long*)onsets, y, (int*)n_bad, (int)W,
                           g.last, g.rs);
     });
@@ -609,23 +618,20 @@ int streams_push(net_streams* g, const void* x, int arg_layout, bool f32, size_t
   if (sc.rc) return sc.rc;
   const hipStream_t st = (hipStream_t)stream;
   if (capturing(st)) return NET_ERR_UNSUPPORTED;
-  const auto* sets = (const gen::GenParams*)sc.image;
-  const auto* scales = f32 ? (const bank::Scale*)(sets + b.sets.size()) : nullptr;
-  const int n_sets = (int)b.sets.size();
+  const BankView v = bank_view(sc, b, f32);
   int8_t* ring = (int8_t*)g->mem;
   const long long* origin = (const long long*)(ring + g->at.origin);
   const int* set_of = (const int*)(ring + g->at.set);
   const int rc = with_layout<true>(f32 ? gen::float_layout(arg_layout) : arg_layout, [&](auto lc) {
     return with_flags(hg, [&](auto rb, auto xr, auto cb) {
       constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
-      // 8 workgroups of 4 waves fill a CU (launch_windows)
       const size_t wgs = (p.l1_items + win::NW1 - 1) / win::NW1;
-      hipLaunchKernelGGL((stream::k_layer1_ring<decltype(lc)::value, XR, CB>), dim3((unsigned)capped_grid(sc.ds, wgs, 8)),
-                         dim3(win::NT1), 0, st, sets, n_sets, set_of, scales, (const int8_t*)x, ring, (int)p.l1_items,
-                         (int)p.blocks, (int)n, p.p0, (int)g->cap);
-      if (const int rc = hip_err(hipGetLastError())) return rc;
+      if (const int rc = launch_l1(sc.ds, stream::k_layer1_ring<decltype(lc)::value, XR, CB>, wgs, st, v.sets, v.n_sets,
+                                   set_of, v.scales, (const int8_t*)x, ring, (int)p.l1_items, (int)p.blocks, (int)n, p.p0,
+                                   (int)g->cap))
+        return rc;
       if (p.k == 0) return (int)NET_OK;
-      return launch_items(sc.ds, stream::k_forward_ring<RB, XR, CB>, windows_lds(hg), p.items, st, sets, n_sets,
+      return launch_items(sc.ds, stream::k_forward_ring<RB, XR, CB>, windows_lds(hg), p.items, st, v.sets, v.n_sets,
                           (const int8_t*)ring, origin, set_of, y, (int*)n_bad, (int)p.items, (int)p.k, p.first, p.hop,
                           p.first_mod, (int)g->cap);
     });
@@ -669,9 +675,7 @@ int streams_push_each(net_streams* g, const void* x, int arg_layout, bool f32, c
   DeviceScope sc(g->device, b);
   if (sc.rc) return sc.rc;
   const hipStream_t st = (hipStream_t)stream;
-  const auto* sets = (const gen::GenParams*)sc.image;
-  const auto* scales = f32 ? (const bank::Scale*)(sets + b.sets.size()) : nullptr;
-  const int n_sets = (int)b.sets.size();
+  const BankView v = bank_view(sc, b, f32);
   int8_t* ring = (int8_t*)g->mem;
   const int* set_of = (const int*)(ring + g->at.set);
   auto* plan = (stream::EachRec*)(ring + g->plan_at);
@@ -683,12 +687,11 @@ int streams_push_each(net_streams* g, const void* x, int arg_layout, bool f32, c
     return with_flags(hg, [&](auto rb, auto xr, auto cb) {
       constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
       const size_t wgs = (p.l1_items + win::NW1 - 1) / win::NW1;
-      hipLaunchKernelGGL((stream::k_layer1_ring_each<decltype(lc)::value, XR, CB>),
-                         dim3((unsigned)capped_grid(sc.ds, wgs, 8)), dim3(win::NT1), 0, st, sets, n_sets, set_of, scales,
-                         (const int8_t*)x, ring, (const stream::EachRec*)plan, (int)p.l1_items, (int)p.blocks, (int)n_max,
-                         (int)g->cap);
-      if (const int rc = hip_err(hipGetLastError())) return rc;
-      return launch_items(sc.ds, stream::k_forward_ring_each<RB, XR, CB>, windows_lds(hg), p.items, st, sets, n_sets,
+      if (const int rc = launch_l1(sc.ds, stream::k_layer1_ring_each<decltype(lc)::value, XR, CB>, wgs, st, v.sets,
+                                   v.n_sets, set_of, v.scales, (const int8_t*)x, ring, (const stream::EachRec*)plan,
+                                   (int)p.l1_items, (int)p.blocks, (int)n_max, (int)g->cap))
+        return rc;
+      return launch_items(sc.ds, stream::k_forward_ring_each<RB, XR, CB>, windows_lds(hg), p.items, st, v.sets, v.n_sets,
                           (const int8_t*)ring, (const stream::EachRec*)plan, set_of, y, (int)p.items, (int)p.kmax, p.hop,
                           (int)g->cap);
     });
@@ -713,8 +716,7 @@ int streams_windows_at(net_streams* g, const int32_t* session, const int64_t* on
   if (sc.rc) return sc.rc;
   const hipStream_t st = (hipStream_t)stream;
   if (!g->each && capturing(st)) return NET_ERR_UNSUPPORTED;
-  const auto* sets = (const gen::GenParams*)sc.image;
-  const int n_sets = (int)b.sets.size();
+  const BankView v = bank_view(sc, b, false);  // layer 1 ran at the push: no scales here
   const int8_t* ring = (const int8_t*)g->mem;
   const int* set_of = (const int*)(ring + g->at.set);
   const long long* lim = (const long long*)(ring + (g->each ? g->pos_at : g->at.origin));
@@ -722,19 +724,15 @@ int streams_windows_at(net_streams* g, const int32_t* session, const int64_t* on
   const int pos_mod = g->each ? 0 : (int)(g->pos % g->cap);
   return with_flags(hg, [&](auto rb, auto xr, auto cb) {
     constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
-    auto go = [&](auto kern) {
-      return launch_items(sc.ds, kern, windows_lds(hg), W, st, sets, n_sets, ring, (const int*)session,
-                          (const long long*)onsets, lim, set_of, y, (int*)n_bad, (int)W, (int)g->S, pos, pos_mod,
-                          (int)g->cap);
-    };
-    auto go_feat = [&](auto kern) {
-      return launch_items(sc.ds, kern, windows_lds(hg), W, st, sets, n_sets, ring, (const int*)session,
-                          (const long long*)onsets, lim, set_of, y, feat, (int*)n_bad, (int)W, (int)g->S, pos, pos_mod,
+    // f: nothing, or the feature rows' pointer, which the _feat kernel takes after y
+    auto go = [&](auto kern, auto... f) {
+      return launch_items(sc.ds, kern, windows_lds(hg), W, st, v.sets, v.n_sets, ring, (const int*)session,
+                          (const long long*)onsets, lim, set_of, y, f..., (int*)n_bad, (int)W, (int)g->S, pos, pos_mod,
                           (int)g->cap);
     };
     if (with_feat)
-      return g->each ? go_feat(stream::k_forward_ring_at_feat<RB, XR, CB, true>)
-                     : go_feat(stream::k_forward_ring_at_feat<RB, XR, CB, false>);
+      return g->each ? go(stream::k_forward_ring_at_feat<RB, XR, CB, true>, feat)
+                     : go(stream::k_forward_ring_at_feat<RB, XR, CB, false>, feat);
     return g->each ? go(stream::k_forward_ring_at<RB, XR, CB, true>) : go(stream::k_forward_ring_at<RB, XR, CB, false>);
   });
 }
