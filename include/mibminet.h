@@ -638,6 +638,59 @@ int net_streams_push_f32_tm(net_streams_t* st, const float* x, size_t n, int8_t*
  * NET_ERR_UNSUPPORTED for a capturing stream. */
 int net_streams_restart(net_streams_t* st, size_t i, int32_t set, void* stream);
 
+/* ---- live streams: frames at q times the network's rate, FIR-decimated ---------------------------
+ * A uniform group may be given a decimator: an integer factor q and K float32 FIR taps h.  It is then
+ * pushed raw float32 frames [S][n_raw][C] (every electrode of the bank's geometry, as
+ * net_streams_push_f32_tm takes them) at q times the rate the network runs at.  A raw push computes
+ * the decimated samples the new frames complete inside the layer-1 kernel (no decimated float array
+ * is written), quantises them with each session's set's scale, runs layer 1 on them into the rings
+ * and returns the windows that end in them.  The last K-1 raw frames of every session live in device
+ * memory owned by the group.
+ * Arithmetic, bit for bit.  With raw_s[a] session s's raw frame a on the group's raw axis and
+ * raw_s[a] = 0 for a < 0, decimated sample d, electrode r, is
+ *     acc = +0.0f;  for k = 0 .. K-1, ascending:  acc = RN(acc + RN(h[k] * raw_s[q*d - k][r]))
+ * with every product and every sum rounded to float32 on its own; nothing is contracted into an fma.
+ * In exact arithmetic this is scipy.signal.upfirdn(h, x, 1, q); it does not depend on how the frames
+ * are split into pushes.  What happens to SUBNORMAL intermediates follows the device's float mode and
+ * is not part of the contract.  An unselected electrode of a widened set may carry anything, NaN
+ * included: whatever the filter makes of it is quantised to a finite int8 and meets a zero weight.
+ * Sample d exists once raw frame q*d has arrived: after P raw frames a session has D(P) = ceil(P/q)
+ * samples, and a push of n_raw frames at P adds m = D(P+n_raw) - D(P) <= ceil(n_raw/q).  Those m
+ * floats are quantised exactly as net_streams_push_f32_tm quantises a frame's, and from there on the
+ * push IS net_streams_push_f32_tm of the m samples at position D(P): q = 1, K = 1, h = {1.0f} gives
+ * that entry's rings and rows, and K = 1, h = {1.0f} with q > 1 is plain striding, x[::q].
+ * The group's position, the origins, net_streams_info, net_streams_windows_at[_feat] and
+ * net_streams_at_span all stay on the DECIMATED axis: a cue at raw frame a is the onset ceil(a/q).
+ *
+ * _set_decimator: once, before the group's first push.  taps: HOST float32[K].  One allocation (the
+ * taps, then K-1 frames of C floats per session, zeroed), none afterwards; the call waits for
+ * `stream`.  Checks: a NULL group, NET_ERR_INVALID; an each-group, NET_ERR_UNSUPPORTED; then
+ * NET_ERR_INVALID for a group that has a decimator or has been pushed to, q outside 1 .. 16, K outside
+ * 1 .. 128, NULL taps, a tap that is not finite, a bank without scales; then NET_ERR_UNSUPPORTED for a
+ * capturing stream.  A refused call leaves the group unchanged.  A group with a decimator refuses
+ * net_streams_push[_f32[_tm]] with NET_ERR_INVALID, and a group without one refuses the raw push the
+ * same way.
+ * _raw_samples: host only; m above, 0 for q == 0 or when raw_pos + n_raw overflows.
+ * _push_raw_f32_tm: x is DEVICE [S][n_raw][C] float32, 4-byte aligned, n_raw <= q*max_push (hence
+ * m <= max_push); y is DEVICE [S][k][N] with k = net_streams_push_windows(bank, hop, D(P), m), rows,
+ * *n_bad and origins as net_streams_push defines them.  m == 0 is legal: only the history moves.
+ * Layer 1 (m > 0), then for K > 1 a small kernel that copies the chunk's last min(n_raw, K-1) frames
+ * to the histories, then the windows' kernel (k > 0) go on `stream`; no host sync, no allocation.
+ * Checks, all before anything is enqueued and before a position moves: a NULL group, an each-group
+ * or a group without a decimator, NET_ERR_INVALID; n_raw == 0, NET_OK and nothing done; then
+ * NET_ERR_INVALID for n_raw > q*max_push, a NULL or misaligned x, a raw position that would pass
+ * INT64_MAX, with k > 0 a NULL or misaligned y, a misaligned n_bad; then NET_ERR_UNSUPPORTED for a
+ * capturing stream.  A refused push leaves the group exactly as it was.
+ * _raw_info: info[0..3] = q (0: no decimator), K, the raw position P, the decimated position D(P).
+ * net_streams_restart on such a group also zeroes session i's history, in stream order: from then on
+ * the session is one whose frames before the restart were all zero.  Its decimated samples stay on
+ * the group's axis q*d, and its origin is the decimated position. */
+int net_streams_set_decimator(net_streams_t* st, size_t q, const float* taps, size_t K, void* stream);
+size_t net_streams_raw_samples(size_t q, size_t raw_pos, size_t n_raw);
+int net_streams_push_raw_f32_tm(net_streams_t* st, const float* x, size_t n_raw, int8_t* y, int32_t* n_bad,
+                                void* stream);
+int net_streams_raw_info(const net_streams_t* st, int64_t* info);
+
 /* ---- live streams, each session at its own pace ------------------------------------------------
  * An each-group is a stream group whose sessions each have their own position pos[s], an int64 in
  * DEVICE memory: the samples session s was given since the group was created or the session last

@@ -109,6 +109,17 @@ int mibminet_test_bank_device_copies(const net_bank_t* bank);
 typedef struct net_streams net_streams_t;
 int mibminet_test_streams_ring(const net_streams_t* st, size_t i, void* out);
 
+/* The FIR decimator of net_streams_push_raw_f32_tm before its quantiser: the device function the
+ * layer-1 kernel runs, on one session.  x: DEVICE [n_raw][R] float32, the chunk at raw position
+ * raw_pos; hist: DEVICE [K - 1][R] float32, raw frame a < raw_pos at slot a mod (K - 1) (NULL for
+ * K == 1); taps: DEVICE float32[K]; out: DEVICE [m][R] float32, m = net_streams_raw_samples(q,
+ * raw_pos, n_raw), the decimated floats as they are.  Enqueued on `stream`.  A one-ulp error would
+ * hide behind the int8 rounding without it.  NET_ERR_INVALID for R outside 1 .. 64, q outside
+ * 1 .. 16, K outside 1 .. 128, n_raw > 16 * 65,536, a raw position that would pass INT64_MAX, a NULL
+ * pointer that is needed. */
+int mibminet_test_fir_decimate(const float* x, size_t n_raw, size_t R, const float* hist, const float* taps, size_t K,
+                               size_t q, size_t raw_pos, float* out, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

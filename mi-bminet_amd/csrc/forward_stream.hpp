@@ -31,7 +31,13 @@
 // long, is stream_host.hpp's at_item.  k_forward_ring_at_feat (net_streams_windows_at_feat) is that
 // kernel writing each item's layer-4 activations as well.
 //
-// One body each: the two layer-1 kernels are layer1_ring, and the four kernels of layers 2-5 are
+// A decimator (net_streams_push_raw_f32_tm): raw float32 frames at q times the network's rate.
+// k_layer1_ring_decim is k_layer1_ring<F32TM> with another fragment source, fir_fragment: each lane
+// runs the K-tap FIR of its output sample over the chunk and the session's history of K - 1 raw
+// frames, then the quantiser, so no decimated float array exists; k_history_update behind it moves
+// the chunk's last frames into the histories; layers 2-5 are k_forward_ring as it is.
+//
+// One body each: the three layer-1 kernels are layer1_ring, and the four kernels of layers 2-5 are
 // bank::set_loop (forward_bank.hpp) over their sources RingRows, EachRows and AtRows, which say
 // where an item's rows are, whether it is valid and under which set.
 #pragma once
@@ -44,6 +50,85 @@ namespace stream {
 using bank::Range64;
 using bank::range_of;
 using bank::Scale;
+
+// ---- a decimator's fragment source (net_streams_push_raw_f32_tm) ----------------------------------
+// What layer 1 of a raw push needs beside a plain push's arguments (stream_host.hpp, PushRaw): the
+// taps and the histories in device memory, K, q, off = q D(P) - P, slot0 = P mod (K - 1) and the
+// bytes of a session's history.
+struct Decim {
+  const float* taps;   // [K]
+  const int8_t* hist;  // [S][K - 1][C] float32, frame a at slot a mod (K - 1)
+  int K, q, off, slot0;
+  unsigned per;        // 4 (K - 1) C
+};
+
+// The sixteen decimated floats of output sample dl of the push (dl counted from the push's first,
+// in block blk: 16 blk <= dl < 16 blk + 16, blk wave-uniform) for the electrodes from float column
+// col of a frame of C floats:
+//   acc = +0; for k = 0 .. K - 1: acc = RN(acc + RN(taps[k] frame(q dl + off - k)[col + i])),
+// every product and sum rounded to float32 on its own (contraction is off in this function).
+// Subnormal intermediates follow the device's float mode.  Frame rel >= 0 is the chunk's (view vc),
+// rel < 0 the history's slot (slot0 + rel) mod (K - 1) (view vh; rel >= -(K - 1)).  Both are buffer
+// views: an offset past either end (a sample past the push's last, a column past the last frame's
+// end) reads zeros, and a lane whose frame is in the other view is given an offset past the end of
+// this one (~15u: beyond any num_records here, and +48 does not wrap).  Which of the two loads a tap
+// needs at all is decided per wave from blk.  The tap is read uniformly (a scalar load).
+__device__ __forceinline__ void fir_taps16(const gen::View& vc, const gen::View& vh, const Decim& dc, int dl, int blk,
+                                           unsigned col, unsigned C, float (&acc)[16]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int i = 0; i < 16; i++) acc[i] = 0.0f;
+  const int r_lo = dc.q * 16 * blk + dc.off, r_hi = r_lo + dc.q * 15;  // the block's rel at k = 0
+  // four taps' loads in flight (a wave has few neighbours on its SIMD here); the sums of one
+  // accumulator stay in tap order.  This loop is where the time of a raw push over a plain one goes
+  // ("Raw frames")
+#pragma unroll 4
+  for (int k = 0; k < dc.K; k++) {  // wave-uniform
+    const float h = dc.taps[k];
+    const int rel = dc.q * dl + dc.off - k;
+    const bool in_chunk = rel >= 0;
+    gen::v4u f[4];
+#pragma unroll
+    for (int m = 0; m < 4; m++) f[m] = (gen::v4u){0u, 0u, 0u, 0u};
+    if (r_hi - k >= 0) {  // some lane's frame is in the chunk
+      const unsigned o = in_chunk ? 4u * ((unsigned)rel * C + col) : ~15u - 48u;
+#pragma unroll
+      for (int m = 0; m < 4; m++) f[m] = __builtin_amdgcn_raw_buffer_load_b128(vc.r, (int)(o + 16u * m), 0, 0);
+    }
+    if (r_lo - k < 0) {  // some lane's frame is in the history
+      const int sl = dc.slot0 + rel;  // >= -(K - 1) where the lane reads it
+      const unsigned o = in_chunk ? ~15u - 48u : 4u * ((unsigned)(sl < 0 ? sl + dc.K - 1 : sl) * C + col);
+#pragma unroll
+      for (int m = 0; m < 4; m++) {
+        const gen::v4u e = __builtin_amdgcn_raw_buffer_load_b128(vh.r, (int)(o + 16u * m), 0, 0);
+        f[m] |= e;  // the other view gave zeros
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+      const float p = h * __uint_as_float(f[i >> 2][i & 3]);
+      acc[i] = acc[i] + p;
+    }
+  }
+}
+
+// The A fragment of block blk of a raw push, in place of gen::l1_fetch<F32TM>: lane (j, g) owns
+// output sample 16 blk + j and the electrodes 16 c .. 16 c + 15, c = l1_chunk(g, C); the sixteen
+// floats of fir_taps16 quantised as gen::load16f quantises a frame's.
+__device__ __forceinline__ v4i fir_fragment(const gen::View& vc, const gen::View& vh, const Decim& dc, int blk, int C,
+                                            int lane, float qs, float qy) {
+  float acc[16];
+  fir_taps16(vc, vh, dc, 16 * blk + (lane & 15), blk, 16u * (unsigned)gen::l1_chunk(lane >> 4, C), (unsigned)C, acc);
+  v4i w;
+#pragma unroll
+  for (int m = 0; m < 4; m++) {
+    int q[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) q[i] = (int)wg::quantize1_f(acc[4 * m + i], qs, qy);
+    w[m] = (int)gen::pack4(q[0], q[1], q[2], q[3]);
+  }
+  return w;
+}
 
 // Layer 1 of the new samples, the body of k_layer1_ring and k_layer1_ring_each.  Items are (session
 // s, 16-sample block b of its chunk), session-major (item = s nb + b); wave g of gridDim.x NW1 takes
@@ -58,15 +143,18 @@ using bank::Scale;
 // block are not stored: their positions hold live older samples.  Where p0 is a multiple of 4 a
 // lane's four positions do not cross the seam (cap is a multiple of 4) and, when all four samples
 // exist, leave as two dwords; otherwise as bytes.
+// DEC (a raw push, L = F32TM): x holds the S chunks of n_view raw frames, n is the m decimated
+// samples they complete, and block b's fragment is fir_fragment's, from the chunk and the session's
+// history; everything after the fragment is a plain push's.
 // EACH: n and p0 are the session's own, read from its plan record (wave-uniform: one scalar load;
 // k_stream_plan validated the record, so n <= n_view = n_max and p0 < cap), and a wave skips the
 // blocks b >= ceil(n / 16); samples >= n are read inside the session's slot and not stored.
-template <int L, bool XR, bool CB, bool EACH>
+template <int L, bool XR, bool CB, bool EACH, bool DEC = false>
 __device__ __forceinline__ void layer1_ring(const gen::GenParams* __restrict__ sets, int n_sets,
                                             const int* __restrict__ set_of, const Scale* __restrict__ scales,
                                             const int8_t* __restrict__ x, int8_t* __restrict__ ring,
                                             const EachRec* __restrict__ plan, int items, int nb, int n_view, int n,
-                                            int p0, int cap) {
+                                            int p0, int cap, const Decim& dc = Decim{}) {
   __shared__ v4i stg_v[win::NW1 * 64];  // channel-major transpose staging, 1 KB per wave
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -100,7 +188,12 @@ __device__ __forceinline__ void layer1_ring(const gen::GenParams* __restrict__ s
     }
     const gen::View v = gen::make_view(x + (size_t)s * chunk, chunk);
     int y[4];
-    gen::l1_outputs<L, XR, CB>(gen::l1_fetch<L>(v, b, C, n_view, lane, qs, qy), stg, k, lane, y);
+    if constexpr (DEC) {
+      const gen::View vh = gen::make_view(dc.hist + (size_t)s * dc.per, dc.per);
+      gen::l1_outputs<L, XR, CB>(fir_fragment(v, vh, dc, b, C, lane, qs, qy), stg, k, lane, y);
+    } else {
+      gen::l1_outputs<L, XR, CB>(gen::l1_fetch<L>(v, b, C, n_view, lane, qs, qy), stg, k, lane, y);
+    }
     const unsigned w = gen::sat4(y[0], y[1], y[2], y[3]);
     int8_t* row = ring + ((size_t)s * 16 + (size_t)(lane & 15)) * (size_t)(2 * cap);
     const int t0 = 16 * b + 4 * g;  // the lane's first sample of the chunk
@@ -132,6 +225,53 @@ __global__ __launch_bounds__(win::NT1) void k_layer1_ring(const gen::GenParams* 
                                                           const int8_t* __restrict__ x, int8_t* __restrict__ ring,
                                                           int items, int nb, int n, int p0, int cap) {
   layer1_ring<L, XR, CB, false>(sets, n_sets, set_of, scales, x, ring, nullptr, items, nb, n, n, p0, cap);
+}
+
+// Layer 1 of a raw push (net_streams_push_raw_f32_tm): the S chunks of n_raw float32 frames [n_raw][C]
+// complete n decimated samples per session, which go to the rings from position p0 as a plain
+// push's do.  It reads the histories and writes none: k_history_update follows it.
+template <bool XR, bool CB>
+__global__ __launch_bounds__(win::NT1) void k_layer1_ring_decim(const gen::GenParams* __restrict__ sets, int n_sets,
+                                                                const int* __restrict__ set_of,
+                                                                const Scale* __restrict__ scales,
+                                                                const int8_t* __restrict__ x, int8_t* __restrict__ ring,
+                                                                int items, int nb, int n_raw, int n, int p0, int cap,
+                                                                Decim dc) {
+  layer1_ring<gen::F32TM, XR, CB, false, true>(sets, n_sets, set_of, scales, x, ring, nullptr, items, nb, n_raw, n, p0, cap,
+                                               dc);
+}
+
+// The second kernel of a raw push (K > 1), after layer 1 has read the old histories: the last keep =
+// min(n_raw, K - 1) frames of every session's chunk go to their history slots, frame rel of the chunk
+// (n_raw - keep <= rel < n_raw) to slot (slot0 + rel) mod (K - 1).  One thread per float, grid-stride
+// over the S keep C floats in 64 bits.
+__global__ void k_history_update(const float* __restrict__ x, float* __restrict__ hist, unsigned long long items,
+                                 unsigned C, unsigned n_raw, unsigned keep, unsigned K, unsigned slot0) {
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < items;
+       i += (unsigned long long)gridDim.x * blockDim.x) {
+    const unsigned c = (unsigned)(i % C);
+    const unsigned long long sf = i / C, s = sf / keep;
+    const unsigned rel = n_raw - keep + (unsigned)(sf - s * keep);
+    const unsigned slot = (slot0 + rel) % (K - 1);
+    hist[(s * (K - 1) + slot) * C + c] = x[(s * n_raw + rel) * C + c];
+  }
+}
+
+// test hook (mibminet_test_fir_decimate): fir_taps16 on one session's chunk x [n_raw][R] and history
+// hist [K - 1][R] (views of their sizes), one wave per 16-sample block and lane (j, g) on electrodes
+// 16 g .. 16 g + 15 as layer 1 places them at R > 32; out [m][R] float32, the bits as they are.
+__global__ void k_fir_decimate(const float* __restrict__ x, const float* __restrict__ hist, float* __restrict__ out,
+                               int n_raw, int R, int m, Decim dc) {
+  const int lane = threadIdx.x & 63, blk = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (16 * blk >= m) return;  // wave-uniform
+  const gen::View vc = gen::make_view((const int8_t*)x, 4u * (unsigned)n_raw * (unsigned)R);
+  const gen::View vh = gen::make_view((const int8_t*)hist, dc.per);
+  const int dl = 16 * blk + (lane & 15), col = 16 * (lane >> 4);
+  float acc[16];
+  fir_taps16(vc, vh, dc, dl, blk, (unsigned)col, (unsigned)R, acc);
+  if (dl < m)
+    for (int i = 0; i < 16; i++)
+      if (col + i < R) out[(size_t)dl * R + col + i] = acc[i];
 }
 
 // An each-group's layer 1 (net_streams_push_each): items are (s, b) with b < nb = ceil(n_max / 16),

@@ -53,7 +53,9 @@ using namespace mib;
 // sessions' origins and sets, of which origin and set are the host's mirrors.  pos and emitted
 // advance on the host when a push is enqueued.  An each-group (net_streams_create_each) keeps a
 // position per session on the device behind them (stream::alloc_each); its pos counts the pushes
-// enqueued.
+// enqueued.  A decimator (net_streams_set_decimator) adds q, K, the raw position and a second
+// allocation dmem (stream::alloc_decim: the taps, then every session's last K - 1 raw frames); pos
+// stays the decimated position.
 struct net_streams {
   const net_bank* bank = nullptr;
   int device = 0;
@@ -65,6 +67,10 @@ struct net_streams {
   size_t plan_at = 0, pos_at = 0;  // an each-group's records and positions in mem
   std::vector<int64_t> origin;
   std::vector<int32_t> set;
+  size_t q = 0, K = 0;  // q == 0: no decimator
+  uint64_t raw_pos = 0;
+  void* dmem = nullptr;
+  stream::AllocDecim dat{};
 };
 
 // test hook (mibminet_test_xdiv_gpu): xdiv against C division in 64 bits over e0 .. e0 + count - 1;
@@ -598,6 +604,7 @@ void streams_destroy(net_streams* g) {
     DeviceGuard guard(g->device);
     if (guard.err == hipSuccess) (void)hipDeviceSynchronize();  // no push still uses the rings
     (void)hipFree(g->mem);
+    (void)hipFree(g->dmem);
   }
   delete g;
 }
@@ -606,7 +613,7 @@ void streams_destroy(net_streams* g) {
 // the first launch and before pos moves.
 int streams_push(net_streams* g, const void* x, int arg_layout, bool f32, size_t n, int8_t* y, int32_t* n_bad,
                  void* stream) {
-  if (!g || g->each) return NET_ERR_INVALID;
+  if (!g || g->each || g->q) return NET_ERR_INVALID;
   const net_bank& b = *g->bank;
   const gen::GenParams& hg = b.sets[0];
   stream::Push p;
@@ -649,6 +656,8 @@ int streams_restart(net_streams* g, size_t i, int32_t set, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   if (capturing(st)) return NET_ERR_UNSUPPORTED;  // a replay would move the origin to a stale position
   char* mem = (char*)g->mem;
+  if (g->q && g->K > 1)  // a decimator: the session's raw frames before the restart count as zeros
+    if (const int rc = hip_err(hipMemsetAsync((char*)g->dmem + g->dat.hist + i * g->dat.per, 0, g->dat.per, st))) return rc;
   // an each-group: the session's position goes back to 0 (its origin stays -1: there is none)
   hipLaunchKernelGGL(stream::k_stream_restart, dim3(1), dim3(1), 0, st,
                      (long long*)(mem + (g->each ? g->pos_at : g->at.origin)), (int*)(mem + g->at.set), (int)i,
@@ -659,13 +668,94 @@ int streams_restart(net_streams* g, size_t i, int32_t set, void* stream) {
   return NET_OK;
 }
 
+// net_streams_set_decimator: every check, the capturing stream's last, comes before the allocation;
+// the group changes only once the taps are on the device and the histories zero.  The stream is
+// waited for, so the caller's taps are free on return.
+int streams_set_decimator(net_streams* g, size_t q, const float* taps, size_t K, void* stream) {
+  if (const int rc = stream::check_set_decimator(g != nullptr, g && g->each, g && !g->bank->scales.empty(),
+                                                 g && g->q != 0, g && g->pos != 0, q, taps, K))
+    return rc;
+  DeviceScope sc(g->device, *g->bank);
+  if (sc.rc) return sc.rc;
+  const hipStream_t st = (hipStream_t)stream;
+  if (capturing(st)) return NET_ERR_UNSUPPORTED;
+  const stream::AllocDecim a = stream::alloc_decim(g->S, (size_t)g->bank->sets[0].C, K);
+  void* mem = nullptr;
+  hipError_t e = hipMalloc(&mem, a.bytes);
+  if (e != hipSuccess) return hip_err(e);
+  e = hipMemsetAsync(mem, 0, a.bytes, st);
+  if (e == hipSuccess) e = hipMemcpyAsync((char*)mem + a.taps, taps, 4 * K, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    (void)hipFree(mem);
+    return hip_err(e);
+  }
+  g->dmem = mem;
+  g->dat = a;
+  g->q = q;
+  g->K = K;
+  return NET_OK;
+}
+
+// net_streams_push_raw_f32_tm: every check (stream::check_push_raw, then the stream's capture status)
+// comes before the first launch and before a position moves.  Layer 1 reads the histories, the
+// history kernel behind it rewrites them, the windows' kernel is a plain push's.
+int streams_push_raw(net_streams* g, const float* x, size_t n_raw, int8_t* y, int32_t* n_bad, void* stream) {
+  if (!g || g->each || !g->q) return NET_ERR_INVALID;
+  const net_bank& b = *g->bank;
+  const gen::GenParams& hg = b.sets[0];
+  stream::PushRaw r;
+  if (const int rc = stream::check_push_raw((size_t)hg.T, g->S, (size_t)hg.C, g->hop, g->max_push, g->cap, g->q, g->K,
+                                            g->raw_pos, x, !b.scales.empty(), n_raw, y, n_bad, r))
+    return rc;
+  if (n_raw == 0) return NET_OK;
+  DeviceScope sc(g->device, b);
+  if (sc.rc) return sc.rc;
+  const hipStream_t st = (hipStream_t)stream;
+  if (capturing(st)) return NET_ERR_UNSUPPORTED;
+  const BankView v = bank_view(sc, b, true);
+  int8_t* ring = (int8_t*)g->mem;
+  const long long* origin = (const long long*)(ring + g->at.origin);
+  const int* set_of = (const int*)(ring + g->at.set);
+  char* dmem = (char*)g->dmem;
+  const stream::Push& p = r.push;
+  const int rc = with_flags(hg, [&](auto rb, auto xr, auto cb) {
+    constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
+    if (r.m) {
+      const stream::Decim dc{(const float*)(dmem + g->dat.taps), (const int8_t*)(dmem + g->dat.hist), (int)g->K, (int)g->q,
+                             r.off, r.slot0, (unsigned)g->dat.per};
+      const size_t wgs = (p.l1_items + win::NW1 - 1) / win::NW1;
+      if (const int rc = launch_l1(sc.ds, stream::k_layer1_ring_decim<XR, CB>, wgs, st, v.sets, v.n_sets, set_of, v.scales,
+                                   (const int8_t*)x, ring, (int)p.l1_items, (int)p.blocks, (int)n_raw, (int)r.m, p.p0,
+                                   (int)g->cap, dc))
+        return rc;
+    }
+    if (r.keep) {
+      const size_t blocks = std::min((r.hist_items + 255) / 256, (size_t)sc.ds.cus * 8);
+      hipLaunchKernelGGL(stream::k_history_update, dim3((unsigned)blocks), dim3(256), 0, st, x,
+                         (float*)(dmem + g->dat.hist), (unsigned long long)r.hist_items, (unsigned)hg.C, (unsigned)n_raw,
+                         (unsigned)r.keep, (unsigned)g->K, (unsigned)r.slot0);
+      if (const int rc = hip_err(hipGetLastError())) return rc;
+    }
+    if (r.m == 0 || p.k == 0) return (int)NET_OK;
+    return launch_items(sc.ds, stream::k_forward_ring<RB, XR, CB>, windows_lds(hg), p.items, st, v.sets, v.n_sets,
+                        (const int8_t*)ring, origin, set_of, y, (int*)n_bad, (int)p.items, (int)p.k, p.first, p.hop,
+                        p.first_mod, (int)g->cap);
+  });
+  if (rc) return rc;
+  g->raw_pos += n_raw;
+  g->pos += r.m;
+  g->emitted += r.m ? p.k : 0;
+  return NET_OK;
+}
+
 // Both push entries of an each-group: every check comes before the first launch.  A launch that
 // fails after the plan's leaves the positions advanced (include/mibminet.h says so); nothing here
 // depends on what earlier pushes did (the positions are on the device), so the three launches are
 // the same on every call with the same arguments and may be captured; pos counts the enqueues.
 int streams_push_each(net_streams* g, const void* x, int arg_layout, bool f32, const int32_t* cnt_in, size_t n_max,
                       int8_t* y, int32_t* cnt_out, int64_t* win0, int32_t* n_bad, void* stream) {
-  if (!g || !g->each) return NET_ERR_INVALID;
+  if (!g || !g->each) return NET_ERR_INVALID;  // (an each-group has no decimator)
   const net_bank& b = *g->bank;
   const gen::GenParams& hg = b.sets[0];
   stream::PushEach p;
@@ -1120,6 +1210,25 @@ int net_streams_push_f32_tm(net_streams_t* st, const float* x, size_t n, int8_t*
 
 int net_streams_restart(net_streams_t* st, size_t i, int32_t set, void* stream) {
   return streams_restart(st, i, set, stream);
+}
+
+int net_streams_set_decimator(net_streams_t* st, size_t q, const float* taps, size_t K, void* stream) {
+  return streams_set_decimator(st, q, taps, K, stream);
+}
+
+size_t net_streams_raw_samples(size_t q, size_t raw_pos, size_t n_raw) {
+  return stream::raw_samples(q, (uint64_t)raw_pos, n_raw);
+}
+
+int net_streams_push_raw_f32_tm(net_streams_t* st, const float* x, size_t n_raw, int8_t* y, int32_t* n_bad,
+                                void* stream) {
+  return streams_push_raw(st, x, n_raw, y, n_bad, stream);
+}
+
+int net_streams_raw_info(const net_streams_t* st, int64_t* info) {
+  if (!st || !info) return NET_ERR_INVALID;
+  info[0] = (int64_t)st->q; info[1] = (int64_t)st->K; info[2] = (int64_t)st->raw_pos; info[3] = (int64_t)st->pos;
+  return NET_OK;
 }
 
 int net_streams_create_each(const net_bank_t* bank, const int32_t* sets, size_t S, size_t hop, size_t max_push,

@@ -5,9 +5,12 @@
 // a position each, the per-session plan of a push (plan_each, shared with the plan kernel of
 // forward_stream.hpp), the rows of its logits, its allocation and its checks; for a query
 // (net_streams_windows_at) which windows a ring still holds and where (at_item, shared with
-// k_forward_ring_at), the span and the checks.  HIP-free like entry_host.hpp, whose windows_count it
-// uses: included by mibminet.hip, forward_stream.hpp and three stand-alone host programs
-// (tests/stream_host_main.cpp, tests/stream_each_host_main.cpp, tests/stream_at_host_main.cpp).
+// k_forward_ring_at), the span and the checks; for a group with a decimator
+// (net_streams_set_decimator) the samples a raw push completes, the history's size and slots and
+// the checks and plan of a raw push.  HIP-free like entry_host.hpp, whose windows_count it uses:
+// included by mibminet.hip, forward_stream.hpp and four stand-alone host programs
+// (tests/stream_host_main.cpp, tests/stream_each_host_main.cpp, tests/stream_at_host_main.cpp,
+// tests/decim_host_main.cpp).
 //
 // The ring.  A session's ring holds the layer-1 output of its last cap samples, sample t at position
 // t mod cap (and again at t mod cap + cap, forward_stream.hpp).  A push of n samples at position p0
@@ -265,6 +268,107 @@ inline int check_windows_at(bool have_group, size_t W, const void* session, cons
   if (((uintptr_t)session & 3) != 0 || ((uintptr_t)onsets & 7) != 0 || ((uintptr_t)y & 3) != 0 ||
       ((uintptr_t)n_bad & 3) != 0)
     return NET_ERR_INVALID;
+  return NET_OK;
+}
+
+// ---- a decimator: raw frames at q times the network's rate (net_streams_set_decimator) ------------
+// A uniform group with a decimator is pushed raw float32 frames [n_raw][R] per session.  With P the
+// raw frames a session was given so far, decimated sample d (the FIR of raw frames q d - K + 1 .. q d)
+// exists once frame q d has arrived: D(P) = ceil(P / q) samples, and a push of n_raw frames at P adds
+// m = D(P + n_raw) - D(P).  The group's position (the ring's, the windows', the origins') stays on the
+// decimated axis, pos = D(P).
+//
+// The history.  A session's last K - 1 raw frames live in device memory, frame a at slot
+// a mod (K - 1): slots that no frame has reached yet hold zeros, which is what the frames a < 0 are.
+// Relative to the chunk's first frame P, output sample j of the push (d = D(P) + j) reads the frames
+// rel = q j + off - k, k = 0 .. K - 1, off = q D(P) - P in 0 .. q - 1: the chunk's frame rel where
+// rel >= 0, else the history's slot (slot0 + rel) mod (K - 1) with slot0 = P mod (K - 1) and
+// rel >= -(K - 1), one conditional addition.
+
+constexpr size_t MAX_Q = 16;      // the decimation factor
+constexpr size_t MAX_TAPS = 128;  // K
+
+// D(P); P / q + 1 cannot wrap for q >= 1
+inline uint64_t raw_decimated(size_t q, uint64_t P) { return P / q + (P % q != 0); }
+
+// m: the decimated samples a push of n_raw frames at raw position raw_pos completes; 0 for q == 0 or
+// when raw_pos + n_raw overflows
+inline size_t raw_samples(size_t q, uint64_t raw_pos, size_t n_raw) {
+  if (q == 0 || (uint64_t)n_raw > UINT64_MAX - raw_pos) return 0;
+  return (size_t)(raw_decimated(q, raw_pos + n_raw) - raw_decimated(q, raw_pos));
+}
+
+// the history slot of raw frame a (K >= 2)
+inline size_t hist_slot(uint64_t a, size_t K) { return (size_t)(a % (K - 1)); }
+
+// bytes of a decimator's one allocation: the taps float[K], then at a multiple of 16 the histories
+// [S][K - 1][R] float (R <= 64, K <= 128, S < 2^31: below 2^46)
+struct AllocDecim {
+  size_t taps, hist, per, bytes;  // offsets of the two; bytes per session's history; the total
+};
+inline AllocDecim alloc_decim(size_t S, size_t R, size_t K) {
+  AllocDecim a;
+  a.taps = 0;
+  a.hist = (4 * K + 15) / 16 * 16;
+  a.per = 4 * (K - 1) * R;
+  a.bytes = a.hist + S * a.per;
+  return a;
+}
+
+inline bool finite_f32(float v) { return v - v == 0.0f; }  // false for NaN and the infinities
+
+// The checks of net_streams_set_decimator before its capturing stream's, in their documented order.
+// pushed: the group has taken a push; have_decim: it has a decimator already.
+inline int check_set_decimator(bool have_group, bool each, bool have_scales, bool have_decim, bool pushed, size_t q,
+                               const float* taps, size_t K) {
+  if (!have_group) return NET_ERR_INVALID;
+  if (each) return NET_ERR_UNSUPPORTED;
+  if (have_decim || pushed) return NET_ERR_INVALID;
+  if (q < 1 || q > MAX_Q || K < 1 || K > MAX_TAPS || !taps) return NET_ERR_INVALID;
+  for (size_t k = 0; k < K; k++)
+    if (!finite_f32(taps[k])) return NET_ERR_INVALID;
+  if (!have_scales) return NET_ERR_INVALID;
+  return NET_OK;
+}
+
+// What one raw push of n_raw frames at raw position P hands to the kernels.
+struct PushRaw {
+  size_t m;             // decimated samples completed
+  uint64_t d0;          // D(P): the decimated position, the first new sample
+  int off;              // q d0 - P, in 0 .. q - 1: the chunk's frame that sample d0 ends in
+  int slot0;            // P mod (K - 1), the history's slot of the chunk's first frame (K == 1: 0)
+  size_t keep;          // min(n_raw, K - 1): the chunk's last frames that go to the history
+  size_t hist_items;    // S keep R: the floats the history kernel copies
+  Push push;            // check_push's plan of the m samples at d0 (m > 0)
+};
+
+// The checks of net_streams_push_raw_f32_tm in check_push's order, all before anything is enqueued;
+// n_raw == 0 is NET_OK with nothing to do (the caller returns before it looks at g).  d0 <= P and
+// m <= ceil(n_raw / q) <= max_push, so the decimated position passes INT64_MAX only if the raw one
+// does.  m == 0 is legal (k == 0, y unread): only the history moves.
+inline int check_push_raw(size_t T, size_t S, size_t R, size_t hop, size_t max_push, size_t cap, size_t q, size_t K,
+                          uint64_t raw_pos, const void* x, bool have_scales, size_t n_raw, const void* y,
+                          const void* n_bad, PushRaw& g) {
+  if (n_raw == 0) return NET_OK;
+  if (n_raw > q * max_push) return NET_ERR_INVALID;  // q max_push <= 2^20
+  if (!x || ((uintptr_t)x & 3) != 0) return NET_ERR_INVALID;
+  if (!have_scales) return NET_ERR_INVALID;
+  if (raw_pos > (uint64_t)INT64_MAX - n_raw) return NET_ERR_INVALID;
+  const size_t m = raw_samples(q, raw_pos, n_raw);
+  const uint64_t d0 = raw_decimated(q, raw_pos);
+  const size_t k = push_windows(T, hop, d0, m);
+  if (k && (!y || ((uintptr_t)y & 3) != 0)) return NET_ERR_INVALID;
+  if (((uintptr_t)n_bad & 3) != 0) return NET_ERR_INVALID;
+  Push p{};
+  if (m)
+    if (const int rc = check_push(T, S, hop, max_push, cap, d0, x, 0, true, have_scales, m, y, n_bad, p)) return rc;
+  g.m = m;
+  g.d0 = d0;
+  g.off = (int)(raw_pos % q == 0 ? 0 : q - raw_pos % q);  // q d0 - P without the product
+  g.slot0 = K > 1 ? (int)hist_slot(raw_pos, K) : 0;
+  g.keep = n_raw < K - 1 ? n_raw : K - 1;
+  g.hist_items = S * g.keep * R;  // S < 2^31, keep < 2^7, R <= 2^6
+  g.push = p;
   return NET_OK;
 }
 

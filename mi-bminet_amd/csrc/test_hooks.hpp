@@ -167,4 +167,24 @@ int mibminet_test_streams_ring(const net_streams_t* st, size_t i, void* out) {
   return hip_err(e);
 }
 
+int mibminet_test_fir_decimate(const float* x, size_t n_raw, size_t R, const float* hist, const float* taps, size_t K,
+                               size_t q, size_t raw_pos, float* out, int device, void* stream) {
+  if (R < 1 || R > 64 || q < 1 || q > stream::MAX_Q || K < 1 || K > stream::MAX_TAPS || !taps) return NET_ERR_INVALID;
+  if (n_raw > stream::MAX_Q * stream::MAX_PUSH || (uint64_t)raw_pos > (uint64_t)INT64_MAX - n_raw) return NET_ERR_INVALID;
+  if ((!x && n_raw) || (!hist && K > 1)) return NET_ERR_INVALID;
+  if (const int rc = check_device(device)) return rc;
+  const size_t m = stream::raw_samples(q, raw_pos, n_raw);
+  if (m == 0) return NET_OK;
+  if (!out) return NET_ERR_INVALID;
+  DeviceGuard guard(device);
+  if (guard.err != hipSuccess) return hip_err(guard.err);
+  const uint64_t d0 = stream::raw_decimated(q, raw_pos);
+  const stream::Decim dc{taps, (const int8_t*)hist, (int)K, (int)q, (int)(d0 * q - raw_pos),
+                         K > 1 ? (int)stream::hist_slot(raw_pos, K) : 0, (unsigned)(4 * (K - 1) * R)};
+  const size_t blocks = (m + 15) / 16;
+  hipLaunchKernelGGL(stream::k_fir_decimate, dim3((unsigned)((blocks + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, hist,
+                     out, (int)n_raw, (int)R, (int)m, dc);
+  return hip_err(hipGetLastError());
+}
+
 }  // extern "C"

@@ -3,6 +3,7 @@
 * ``params``: the weight ABI (net.h arrays, blob format, QuantLab -> int parameter compiler).
 * ``lib``: ctypes binding of libmibminet.so, the C ABI of include/mibminet.h (gfx950 HIP kernels);
   import it explicitly (``from mibminet import lib``).
+* ``decimate``: the FIR decimator of a stream group in NumPy (``from mibminet import decimate``).
 """
 from .params import Dims, ParamSet, pack_trials, trial_stride_bytes  # noqa: F401
 

@@ -92,6 +92,10 @@ PROTOTYPES = {
     "net_streams_push_f32": "int (ptr, ptr, size_t, ptr, ptr, ptr)",
     "net_streams_push_f32_tm": "int (ptr, ptr, size_t, ptr, ptr, ptr)",
     "net_streams_restart": "int (ptr, size_t, int32_t, ptr)",
+    "net_streams_set_decimator": "int (ptr, size_t, ptr, size_t, ptr)",
+    "net_streams_raw_samples": "size_t (size_t, size_t, size_t)",
+    "net_streams_push_raw_f32_tm": "int (ptr, ptr, size_t, ptr, ptr, ptr)",
+    "net_streams_raw_info": "int (ptr, ptr)",
     "net_streams_create_each": "int (ptr, ptr, size_t, size_t, size_t, int, ptr)",
     "net_streams_each_rows": "size_t (size_t, size_t)",
     "net_streams_push_each": "int (ptr, ptr, int, ptr, size_t, ptr, ptr, ptr, ptr, ptr)",
@@ -130,6 +134,7 @@ PROTOTYPES = {
     "mibminet_test_bank_copy": "int (ptr, size_t, ptr, size_t, ptr)",
     "mibminet_test_bank_device_copies": "int (ptr)",
     "mibminet_test_streams_ring": "int (ptr, size_t, ptr)",
+    "mibminet_test_fir_decimate": "int (ptr, size_t, size_t, ptr, ptr, size_t, size_t, size_t, ptr, int, ptr)",
 }
 EXPORTED_SYMBOLS = tuple(n for n in PROTOTYPES if n.startswith("net_"))
 NET_PATH_FLOAT, NET_PATH_EXACT, NET_PATH_GENERAL = 0, 1, 2
@@ -1202,9 +1207,51 @@ class Streams:
         return self._push(x, "_f32" if layout == "ct" else "_f32_tm", (), int(x.shape[2 if layout == "ct" else 1]), stream,
                           out)
 
+    def decimate(self, q: int, taps, stream=None) -> None:
+        """net_streams_set_decimator: once, before the first push.  From then on the group takes raw
+        float32 frames at ``q`` times the network's rate through ``push_raw`` and filters them with
+        the FIR ``taps`` (K <= 128 finite float32 values, q <= 16; decimate.firwin_taps(q) is a
+        default) inside the layer-1 kernel, bit for bit as decimate.fir_decimate states it."""
+        torch = _torch()
+        h = np.ascontiguousarray(taps, dtype=np.float32)
+        if h.ndim != 1:
+            raise ValueError("taps must be a 1-D array")
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        _check(load().net_streams_set_decimator(self.handle, q, h.ctypes.data, h.size, s.cuda_stream),
+               "net_streams_set_decimator")
+
+    def raw_info(self) -> list:
+        """net_streams_raw_info: [q (0: no decimator), K, the raw position, the decimated position]."""
+        arr = (ctypes.c_int64 * 4)()
+        _check(load().net_streams_raw_info(self.handle, arr), "net_streams_raw_info")
+        return list(arr)
+
+    def push_raw(self, frames, stream=None, out=None):
+        """net_streams_push_raw_f32_tm: ``frames`` is a CUDA/HIP float32 tensor [S][n_raw][C] at q times
+        the network's rate, at most q max_push frames.  Returns what push returns for the decimated
+        samples these frames complete (possibly none: then the logits are [S][0][N])."""
+        if not self.bank.has_scales:
+            raise ValueError("a float32 source needs a bank created with scales")
+        _check_tensor(frames, "frames", ("float32",), (self.S, "n", self.bank.dims.C))
+        torch = _torch()
+        q, _, P, D = self.raw_info()
+        n_raw, N = int(frames.shape[1]), self.bank.dims.N
+        k = int(load().net_streams_push_windows(self.bank.handle, self.hop, D, raw_samples(q, P, n_raw)))
+        s, _ = _launch(frames, stream)
+        with torch.cuda.stream(s):  # the counter's zeroing precedes the launch on its stream
+            nbad = torch.zeros((1,), dtype=torch.int32, device=frames.device)
+        if out is None:
+            out = torch.empty((self.S, k, N), dtype=torch.int8, device=frames.device)
+        else:
+            _check_tensor(out, "out", ("int8",), (self.S, k, N))
+        _check(load().net_streams_push_raw_f32_tm(self.handle, frames.data_ptr(), n_raw, out.data_ptr() if k else None,
+                                                  nbad.data_ptr(), s.cuda_stream), "net_streams_push_raw_f32_tm")
+        return out, nbad
+
     def windows_at(self, sessions, onsets, stream=None, out=None, check: bool = True, features: bool = False):
         """net_streams_windows_at: the windows of sessions ``sessions[w]`` whose first samples are
-        ``onsets[w]`` on the group's position axis, read from the rings as they are (cue-locked
+        ``onsets[w]`` on the group's position axis (the decimated one on a group with a decimator: a
+        cue at raw frame a is the onset ceil(a / q)), read from the rings as they are (cue-locked
         trials).  Device tensors (int32, int64) or sequences of ints, any order, duplicates allowed;
         sorted by session the call reloads parameters least.  Returns the logits [W][N] int8, row w
         what forward_ct_torch returns for samples onsets[w] .. + T - 1 of the session with its set
@@ -1388,6 +1435,31 @@ def streams_ring(streams, i: int) -> np.ndarray:
     StreamsEach group, [16][2 cap] int8, read after synchronising its device."""
     out = np.empty((16, 2 * streams.cap), np.int8)
     _check(load().mibminet_test_streams_ring(streams.handle, i, out.ctypes.data), "mibminet_test_streams_ring")
+    return out
+
+
+def raw_samples(q: int, raw_pos: int, n_raw: int) -> int:
+    """net_streams_raw_samples: the decimated samples that ``n_raw`` raw frames at raw position
+    ``raw_pos`` complete under factor ``q``, ceil((raw_pos + n_raw) / q) - ceil(raw_pos / q); 0 for
+    q == 0 or when the sum passes 2^64 - 1."""
+    return int(load().net_streams_raw_samples(q, raw_pos, n_raw))
+
+
+def fir_decimate_torch(x, hist, taps, q: int, raw_pos: int, stream=None):
+    """Test hook (mibminet_test_fir_decimate): the decimator's device function on one session's chunk
+    ``x`` [n_raw][R] at raw position ``raw_pos``, with the history ``hist`` [K - 1][R] in slot order
+    (frame a at slot a mod (K - 1); ignored for K == 1) and the taps [K], all float32 device
+    tensors.  Returns the decimated floats [m][R] before the quantiser."""
+    torch = _torch()
+    _check_tensor(x, "x", ("float32",), ("n", "R"))
+    _check_tensor(taps, "taps", ("float32",), ("K",))
+    n_raw, R, K = int(x.shape[0]), int(x.shape[1]), int(taps.shape[0])
+    if K > 1:
+        _check_tensor(hist, "hist", ("float32",), (K - 1, R))
+    s, dev = _launch(x, stream)
+    out = torch.empty((raw_samples(q, raw_pos, n_raw), R), dtype=torch.float32, device=x.device)
+    _check(load().mibminet_test_fir_decimate(x.data_ptr(), n_raw, R, hist.data_ptr() if K > 1 else None, taps.data_ptr(), K,
+                                             q, raw_pos, out.data_ptr(), dev, s.cuda_stream), "mibminet_test_fir_decimate")
     return out
 
 

@@ -52,6 +52,19 @@ hop 8, n 16, each candidate with a stream group of its own fed the same samples:
 Verified first in both: over six ticks every logit row of (new) equals (a)'s and (b)'s.  The three
 alternate within every warm-up round and every timed repeat.
 
+Frames at the amplifier's own rate (net_streams_push_raw_f32_tm), 1,024 sessions of 22 x 1125 under 16
+grouped sets, hop 8, 16 decimated samples per tick, i.e. 16 q raw float32 frames [S][16 q][C]:
+  f32_tm_decim    Two settings, q = 2 with K = 41 taps and q = 4 with K = 81 (decimate.firwin_taps), each with
+                  three stream groups fed the same frames.  (new) net_streams_push_raw_f32_tm: the FIR inside
+                  the layer-1 kernel, the histories on the device; (a) the caller's recipe, all timed: a kept
+                  tail of K - 1 frames, torch.cat, a strided depthwise conv1d, the transpose back to frames
+                  and net_streams_push_f32_tm; (b) net_streams_push_f32_tm alone on frames decimated
+                  beforehand.  The rings are filled with zero frames; then over six ticks of random frames
+                  every row of (new) must equal (b)'s on decimate.fir_decimate's samples (the CPU's, bit
+                  for bit what the kernel computes); (a)'s float sums are the convolution library's and its
+                  rows are compared for the record only.  The claim checked is new <= a on the medians, with no
+                  margin; new / b is reported, not judged.
+
 Cue-locked trials of live sessions (net_streams_windows_at), 1,024 sessions of 22 x 1125 under 16
 grouped sets, hop 8, n 16:
   at_cues         Every tick is a push followed by one query per session, at an onset drawn uniformly
@@ -71,7 +84,7 @@ grouped sets, hop 8, n 16:
                   also stores 16 T64 bytes of layer-4 activations per window; the three rotate their
                   order from tick to tick.  Verified first: over six ticks (feat)'s logits equal (new)'s.
 
-  python tools/bench_streams.py [--cases mmmi_64,bci_1024,bci_1024_shuffled,each_equal,each_ragged,f32_tm,f32_tm_montage,at_cues,at_feat]
+  python tools/bench_streams.py [--cases mmmi_64,bci_1024,bci_1024_shuffled,each_equal,each_ragged,f32_tm,f32_tm_montage,f32_tm_decim,at_cues,at_feat]
                                 [--limit S] [--reps 1000] [--warmup 50] [--variant canonical|plain_bn]
                                 [--out-dir profiles]
 """
@@ -95,7 +108,9 @@ F32_CASES = {  # name: (sessions, sets, C, T, N, n, source rows R): net_streams_
     "f32_tm": (1024, 16, 22, 1125, 4, 16, 22),
     "f32_tm_montage": (1024, 16, 19, 1125, 4, 16, 64),
 }
-
+DECIM_CASES = {  # name: (sessions, sets, C, T, N, decimated samples per tick, ((q, K), ...)): net_streams_push_raw_f32_tm
+    "f32_tm_decim": (1024, 16, 22, 1125, 4, 16, ((2, 41), (4, 81))),
+}
 
 AT_CASES = {  # name: (sessions, sets, C, T, N, n): net_streams_windows_at
     "at_cues": (1024, 16, 22, 1125, 4, 16),
@@ -114,6 +129,8 @@ def run_case(name, limit, reps, warmup, variant, seed=2026):
         return run_each(name, limit, reps, warmup, variant, seed)
     if name in F32_CASES:
         return run_f32(name, limit, reps, warmup, variant, seed)
+    if name in DECIM_CASES:
+        return run_decim(name, limit, reps, warmup, variant, seed)
     import numpy as np
     import torch
 
@@ -447,6 +464,99 @@ def run_f32(name, limit, reps, warmup, variant, seed=2026):
     return res
 
 
+def run_decim(name, limit, reps, warmup, variant, seed=2026):
+    import numpy as np
+    import torch
+
+    from mibminet import decimate, lib
+    from mibminet.params import ParamSet
+
+    S, n_sets, C, T, N, n, settings = DECIM_CASES[name]
+    S = min(S, limit)
+    n_sets = min(n_sets, S)
+    sets = [ParamSet.synthetic(seed=seed + s, C=C, T=T, N=N, reorder_bn=variant != "plain_bn") for s in range(n_sets)]
+    scales = [1.0 + 0.25 * s for s in range(n_sets)]
+    bank = lib.Bank(sets, scales)
+    set_of = [int(v) for v in np.sort(np.arange(S) * n_sets // S)]
+    k = n // HOP
+    lead = T % HOP
+    fill = -(-(T - lead) // n)
+    A = lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    nbad = torch.zeros((1,), dtype=torch.int32, device="cuda")
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    configs, mis_all = [], 0
+    for q, K in settings:
+        taps = decimate.firwin_taps(q, K)
+        groups = {key: lib.Streams(bank, set_of, HOP, n) for key in ("new", "a", "b")}
+        groups["new"].decimate(q, taps)
+        n_raw = q * n
+        xraw = torch.zeros((S, n_raw, C), dtype=torch.float32, device="cuda")  # the tick's frames as delivered
+        xdec = torch.zeros((S, n, C), dtype=torch.float32, device="cuda")      # (b)'s: decimated beforehand
+        tail = torch.zeros((S, K - 1, C), dtype=torch.float32, device="cuda")  # (a)'s kept frames
+        weight = torch.from_numpy(np.ascontiguousarray(taps[::-1])).cuda().view(1, 1, K).repeat(C, 1, 1)
+        y = {key: torch.empty((S, k, N), dtype=torch.int8, device="cuda") for key in groups}
+
+        def new():
+            rc = A.net_streams_push_raw_f32_tm(groups["new"].handle, xraw.data_ptr(), n_raw, y["new"].data_ptr(),
+                                               nbad.data_ptr(), stream)
+            assert rc == 0, rc
+
+        def a():  # the kept tail, the cat, the strided depthwise convolution, frames again, the push
+            with torch.no_grad():
+                cat = torch.cat((tail, xraw), dim=1)
+                tail.copy_(cat[:, n_raw:])
+                dec = torch.nn.functional.conv1d(cat.transpose(1, 2), weight, stride=q, groups=C)  # [S][C][n]
+                fr = dec.transpose(1, 2).contiguous()
+            rc = A.net_streams_push_f32_tm(groups["a"].handle, fr.data_ptr(), n, y["a"].data_ptr(), nbad.data_ptr(), stream)
+            assert rc == 0, rc
+
+        def b():
+            rc = A.net_streams_push_f32_tm(groups["b"].handle, xdec.data_ptr(), n, y["b"].data_ptr(), nbad.data_ptr(), stream)
+            assert rc == 0, rc
+
+        # zero frames until the first window is one tick away: every position is then T mod hop on the grid
+        for m in [lead] * (lead > 0) + [n] * fill:
+            groups["new"].push_raw(xraw[:, : q * m].contiguous())
+            for key in ("a", "b"):
+                groups[key].push_f32(xdec[:, :m].contiguous(), layout="tc")
+        assert all(st.info()[4] == lead + fill * n for st in groups.values())
+        state, pos = np.zeros((K - 1, S * C), np.float32), q * (lead + fill * n)
+        mis = mis_a = 0
+        for _ in range(VERIFY):
+            xraw.copy_(torch.randn((S, n_raw, C), dtype=torch.float32, device="cuda", generator=g))
+            flat = np.ascontiguousarray(xraw.cpu().numpy().transpose(1, 0, 2).reshape(n_raw, S * C))
+            dec, state = decimate.fir_decimate(flat, taps, q, state, pos)
+            pos += n_raw
+            xdec.copy_(torch.from_numpy(np.ascontiguousarray(dec.reshape(n, S, C).transpose(1, 0, 2))))
+            new()
+            a()
+            b()
+            torch.cuda.synchronize()
+            mis += int((y["new"] != y["b"]).any(dim=2).sum().item())
+            mis_a += int((y["new"] != y["a"]).any(dim=2).sum().item())
+        assert int(nbad.item()) == 0
+        ms = time_alternating({"new": new, "a": a, "b": b}, reps, warmup)
+        med = medians(ms)
+        configs.append({"q": q, "K": K, "raw_frames_per_tick": n_raw, "mismatched_rows": mis,
+                        "rows_of_recipe_that_differ": mis_a, "ms_push_raw_f32_tm": round(med["new"], 4),
+                        "ms_tail_cat_conv1d_push_f32_tm": round(med["a"], 4), "ms_push_f32_tm_alone": round(med["b"], 4),
+                        "ms_push_raw_f32_tm_min_max": min_max(ms["new"]),
+                        "ms_tail_cat_conv1d_push_f32_tm_min_max": min_max(ms["a"]),
+                        "ms_push_f32_tm_alone_min_max": min_max(ms["b"]), "new_over_a": round(med["new"] / med["a"], 4),
+                        "new_over_b": round(med["new"] / med["b"], 4), "new <= a": med["new"] <= med["a"]})
+        mis_all += mis
+        for st in groups.values():
+            st.close()
+    info = bank.info()
+    res = {"name": name, "sessions": S, "sets": n_sets, "C": C, "T": T, "N": N, "hop": HOP, "n": n, "windows_per_tick": S * k,
+           "variant": variant, "exact_division": bool(info[4]), "verified_ticks": VERIFY, "mismatched_rows": mis_all,
+           "reps": reps, "warmup": warmup, "device": torch.cuda.get_device_name(0), "configs": configs,
+           "gates": {f"new <= a (q {c['q']}, K {c['K']})": c["new <= a"] for c in configs}, "pass": mis_all == 0}
+    bank.close()
+    return res
+
+
 def run_at(name, limit, reps, warmup, variant, seed=2026):
     import numpy as np
     import torch
@@ -650,4 +760,4 @@ def b_call(A, bank, recipe, nbad, stream):
 
 
 if __name__ == "__main__":
-    main(__doc__, {**CASES, **EACH_CASES, **F32_CASES, **AT_CASES, **AT_FEAT_CASES}, run_case, "limit", "streams", lambda res: res["mismatched_rows"], reps=1000, warmup=50)
+    main(__doc__, {**CASES, **EACH_CASES, **F32_CASES, **DECIM_CASES, **AT_CASES, **AT_FEAT_CASES}, run_case, "limit", "streams", lambda res: res["mismatched_rows"], reps=1000, warmup=50)
