@@ -14,7 +14,8 @@
 //   of a replacement (net_bank_replace) included;
 // * stream_host.hpp: the HIP-free part of a stream group: ring size, per-push arithmetic, checks,
 //   an each-group's per-session plan, shared with its plan kernel, and a query's validity
-//   predicate, shared with its kernel;
+//   predicate, shared with its kernel; the group's record (net_streams, one stream::AllocEach for
+//   its allocation) and the launching entries' shared prologue (OpenGroup) are here;
 // * device_state.hpp: the loaded set, the per-device image cache and the scoped launch entry;
 // * test_hooks.hpp: include/mibminet_testing.h.
 // There is no CPU compute path: without a usable HIP device every entry point returns an error.
@@ -49,22 +50,23 @@
 using namespace mib;
 
 // A stream group (net_streams_t, include/mibminet.h): S live sessions of one bank's geometry on one
-// device.  mem is the group's one allocation (stream::alloc_of): the layer-1 rings, then the
-// sessions' origins and sets, of which origin and set are the host's mirrors.  pos and emitted
-// advance on the host when a push is enqueued.  An each-group (net_streams_create_each) keeps a
-// position per session on the device behind them (stream::alloc_each); its pos counts the pushes
-// enqueued.  A decimator (net_streams_set_decimator) adds q, K, the raw position and a second
-// allocation dmem (stream::alloc_decim: the taps, then every session's last K - 1 raw frames); pos
-// stays the decimated position.
+// device.  mem is the group's one allocation, laid out by at: at.base (stream::alloc_of) is the
+// layer-1 rings, then the sessions' origins and sets, of which origin and set are the host's
+// mirrors.  pos and emitted advance on the host when a push is enqueued.  An each-group
+// (net_streams_create_each) keeps its plan records and a position per session on the device behind
+// them (at.plan and at.pos, stream::alloc_each; unused on a uniform group); its pos counts the
+// pushes enqueued.  A decimator (net_streams_set_decimator) adds q, K, the raw position and a
+// second allocation dmem (stream::alloc_decim: the taps, then every session's last K - 1 raw
+// frames); pos stays the decimated position.  A launching entry reaches all of this through
+// OpenGroup (section "live streams").
 struct net_streams {
   const net_bank* bank = nullptr;
   int device = 0;
   size_t S = 0, hop = 0, max_push = 0, cap = 0;
   uint64_t pos = 0, emitted = 0;
   void* mem = nullptr;
-  stream::Alloc at{};
+  stream::AllocEach at{};
   bool each = false;
-  size_t plan_at = 0, pos_at = 0;  // an each-group's records and positions in mem
   std::vector<int64_t> origin;
   std::vector<int32_t> set;
   size_t q = 0, K = 0;  // q == 0: no decimator
@@ -568,15 +570,10 @@ int streams_create(const net_bank* b, const int32_t* sets, size_t S, size_t hop,
   g->hop = hop;
   g->max_push = max_push;
   g->cap = stream::ring_samples((size_t)b->sets[0].T, max_push);
-  g->at = stream::alloc_of(S, g->cap);
-  size_t bytes = g->at.bytes;
-  if (each) {
-    const stream::AllocEach a = stream::alloc_each(S, g->cap);
-    g->each = true;
-    g->plan_at = a.plan;
-    g->pos_at = a.pos;
-    bytes = a.bytes;
-  }
+  g->each = each;
+  g->at = stream::alloc_each(S, g->cap);
+  if (!each) g->at.bytes = g->at.base.bytes;  // a uniform group ends with the sets: no plan, no positions
+  const size_t bytes = g->at.bytes;
   g->origin.assign(S, each ? -1 : 0);
   g->set.assign(S, 0);
   if (sets) g->set.assign(sets, sets + S);
@@ -586,7 +583,7 @@ int streams_create(const net_bank* b, const int32_t* sets, size_t S, size_t hop,
   if (e != hipSuccess) return hip_err(e);
   e = hipMemset(g->mem, 0, bytes);
   if (e == hipSuccess && sets)
-    e = hipMemcpy((char*)g->mem + g->at.set, g->set.data(), 4 * S, hipMemcpyHostToDevice);
+    e = hipMemcpy((char*)g->mem + g->at.base.set, g->set.data(), 4 * S, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipDeviceSynchronize();  // the null stream's memset precedes every stream's push
   if (e != hipSuccess) {
     (void)hipFree(g->mem);
@@ -609,6 +606,44 @@ void streams_destroy(net_streams* g) {
   delete g;
 }
 
+// A group opened for one launching call, after the entry's argument checks: the scope on the group's
+// device and bank (which may upload the bank), the stream, the capture refusal where the entry has
+// one (REFUSE_CAPTURE: a stream that is capturing gives NET_ERR_UNSUPPORTED), the bank's view (f32:
+// with its scales) and the arrays of mem.  plan and pos are an each-group's.  rc != NET_OK: the
+// entry returns it, and nothing else here is valid.  Constructed in place: the scope holds the
+// device's lock.
+enum Capture { ALLOW_CAPTURE, REFUSE_CAPTURE };
+struct OpenGroup {
+  DeviceScope sc;
+  hipStream_t st;
+  int rc;
+  BankView v{};
+  int8_t* ring;
+  long long *origin, *pos;
+  int* set_of;
+  stream::EachRec* plan;
+  OpenGroup(const net_streams& g, void* stream, Capture capture, bool f32 = false)
+      : sc(g.device, *g.bank), st((hipStream_t)stream), rc(sc.rc), ring((int8_t*)g.mem),
+        origin((long long*)(ring + g.at.base.origin)), pos((long long*)(ring + g.at.pos)),
+        set_of((int*)(ring + g.at.base.set)), plan((stream::EachRec*)(ring + g.at.plan)) {
+    if (rc == NET_OK && capture == REFUSE_CAPTURE && capturing(st)) rc = NET_ERR_UNSUPPORTED;
+    if (rc == NET_OK) v = bank_view(sc, *g.bank, f32);
+  }
+  OpenGroup(const OpenGroup&) = delete;
+};
+
+// workgroups of a layer-1 launch over l1_items 16-sample blocks
+size_t l1_wgs(size_t l1_items) { return (l1_items + win::NW1 - 1) / win::NW1; }
+
+// The windows that end in a push, out of the rings: the launch that ends net_streams_push* and
+// net_streams_push_raw_f32_tm.
+template <bool RB, bool XR, bool CB>
+int launch_ring_windows(const OpenGroup& o, const net_streams& g, const stream::Push& p, int8_t* y, int32_t* n_bad) {
+  return launch_items(o.sc.ds, stream::k_forward_ring<RB, XR, CB>, windows_lds(g.bank->sets[0]), p.items, o.st, o.v.sets,
+                      o.v.n_sets, o.ring, o.origin, o.set_of, y, (int*)n_bad, (int)p.items, (int)p.k, p.first, p.hop,
+                      p.first_mod, (int)g.cap);
+}
+
 // Both push entries: every check (stream::check_push, then the stream's capture status) comes before
 // the first launch and before pos moves.
 int streams_push(net_streams* g, const void* x, int arg_layout, bool f32, size_t n, int8_t* y, int32_t* n_bad,
@@ -621,26 +656,17 @@ int streams_push(net_streams* g, const void* x, int arg_layout, bool f32, size_t
                                         !b.scales.empty(), n, y, n_bad, p))
     return rc;
   if (n == 0) return NET_OK;
-  DeviceScope sc(g->device, b);
-  if (sc.rc) return sc.rc;
-  const hipStream_t st = (hipStream_t)stream;
-  if (capturing(st)) return NET_ERR_UNSUPPORTED;
-  const BankView v = bank_view(sc, b, f32);
-  int8_t* ring = (int8_t*)g->mem;
-  const long long* origin = (const long long*)(ring + g->at.origin);
-  const int* set_of = (const int*)(ring + g->at.set);
+  const OpenGroup o(*g, stream, REFUSE_CAPTURE, f32);
+  if (o.rc) return o.rc;
   const int rc = with_layout<true>(f32 ? gen::float_layout(arg_layout) : arg_layout, [&](auto lc) {
     return with_flags(hg, [&](auto rb, auto xr, auto cb) {
       constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
-      const size_t wgs = (p.l1_items + win::NW1 - 1) / win::NW1;
-      if (const int rc = launch_l1(sc.ds, stream::k_layer1_ring<decltype(lc)::value, XR, CB>, wgs, st, v.sets, v.n_sets,
-                                   set_of, v.scales, (const int8_t*)x, ring, (int)p.l1_items, (int)p.blocks, (int)n, p.p0,
-                                   (int)g->cap))
+      if (const int rc = launch_l1(o.sc.ds, stream::k_layer1_ring<decltype(lc)::value, XR, CB>, l1_wgs(p.l1_items), o.st,
+                                   o.v.sets, o.v.n_sets, o.set_of, o.v.scales, (const int8_t*)x, o.ring, (int)p.l1_items,
+                                   (int)p.blocks, (int)n, p.p0, (int)g->cap))
         return rc;
       if (p.k == 0) return (int)NET_OK;
-      return launch_items(sc.ds, stream::k_forward_ring<RB, XR, CB>, windows_lds(hg), p.items, st, v.sets, v.n_sets,
-                          (const int8_t*)ring, origin, set_of, y, (int*)n_bad, (int)p.items, (int)p.k, p.first, p.hop,
-                          p.first_mod, (int)g->cap);
+      return launch_ring_windows<RB, XR, CB>(o, *g, p, y, n_bad);
     });
   });
   if (rc) return rc;
@@ -651,16 +677,13 @@ int streams_push(net_streams* g, const void* x, int arg_layout, bool f32, size_t
 
 int streams_restart(net_streams* g, size_t i, int32_t set, void* stream) {
   if (!g || i >= g->S || set < 0 || (size_t)set >= g->bank->sets.size()) return NET_ERR_INVALID;
-  DeviceScope sc(g->device, *g->bank);
-  if (sc.rc) return sc.rc;
-  const hipStream_t st = (hipStream_t)stream;
-  if (capturing(st)) return NET_ERR_UNSUPPORTED;  // a replay would move the origin to a stale position
-  char* mem = (char*)g->mem;
+  const OpenGroup o(*g, stream, REFUSE_CAPTURE);  // a replay would move the origin to a stale position
+  if (o.rc) return o.rc;
   if (g->q && g->K > 1)  // a decimator: the session's raw frames before the restart count as zeros
-    if (const int rc = hip_err(hipMemsetAsync((char*)g->dmem + g->dat.hist + i * g->dat.per, 0, g->dat.per, st))) return rc;
+    if (const int rc = hip_err(hipMemsetAsync((char*)g->dmem + g->dat.hist + i * g->dat.per, 0, g->dat.per, o.st)))
+      return rc;
   // an each-group: the session's position goes back to 0 (its origin stays -1: there is none)
-  hipLaunchKernelGGL(stream::k_stream_restart, dim3(1), dim3(1), 0, st,
-                     (long long*)(mem + (g->each ? g->pos_at : g->at.origin)), (int*)(mem + g->at.set), (int)i,
+  hipLaunchKernelGGL(stream::k_stream_restart, dim3(1), dim3(1), 0, o.st, g->each ? o.pos : o.origin, o.set_of, (int)i,
                      g->each ? 0ll : (long long)g->pos, (int)set);
   if (const int rc = hip_err(hipGetLastError())) return rc;
   if (!g->each) g->origin[i] = (int64_t)g->pos;
@@ -675,17 +698,15 @@ int streams_set_decimator(net_streams* g, size_t q, const float* taps, size_t K,
   if (const int rc = stream::check_set_decimator(g != nullptr, g && g->each, g && !g->bank->scales.empty(),
                                                  g && g->q != 0, g && g->pos != 0, q, taps, K))
     return rc;
-  DeviceScope sc(g->device, *g->bank);
-  if (sc.rc) return sc.rc;
-  const hipStream_t st = (hipStream_t)stream;
-  if (capturing(st)) return NET_ERR_UNSUPPORTED;
+  const OpenGroup o(*g, stream, REFUSE_CAPTURE);
+  if (o.rc) return o.rc;
   const stream::AllocDecim a = stream::alloc_decim(g->S, (size_t)g->bank->sets[0].C, K);
   void* mem = nullptr;
   hipError_t e = hipMalloc(&mem, a.bytes);
   if (e != hipSuccess) return hip_err(e);
-  e = hipMemsetAsync(mem, 0, a.bytes, st);
-  if (e == hipSuccess) e = hipMemcpyAsync((char*)mem + a.taps, taps, 4 * K, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  e = hipMemsetAsync(mem, 0, a.bytes, o.st);
+  if (e == hipSuccess) e = hipMemcpyAsync((char*)mem + a.taps, taps, 4 * K, hipMemcpyHostToDevice, o.st);
+  if (e == hipSuccess) e = hipStreamSynchronize(o.st);
   if (e != hipSuccess) {
     (void)hipFree(mem);
     return hip_err(e);
@@ -709,14 +730,8 @@ int streams_push_raw(net_streams* g, const float* x, size_t n_raw, int8_t* y, in
                                             g->raw_pos, x, !b.scales.empty(), n_raw, y, n_bad, r))
     return rc;
   if (n_raw == 0) return NET_OK;
-  DeviceScope sc(g->device, b);
-  if (sc.rc) return sc.rc;
-  const hipStream_t st = (hipStream_t)stream;
-  if (capturing(st)) return NET_ERR_UNSUPPORTED;
-  const BankView v = bank_view(sc, b, true);
-  int8_t* ring = (int8_t*)g->mem;
-  const long long* origin = (const long long*)(ring + g->at.origin);
-  const int* set_of = (const int*)(ring + g->at.set);
+  const OpenGroup o(*g, stream, REFUSE_CAPTURE, true);
+  if (o.rc) return o.rc;
   char* dmem = (char*)g->dmem;
   const stream::Push& p = r.push;
   const int rc = with_flags(hg, [&](auto rb, auto xr, auto cb) {
@@ -724,23 +739,20 @@ int streams_push_raw(net_streams* g, const float* x, size_t n_raw, int8_t* y, in
     if (r.m) {
       const stream::Decim dc{(const float*)(dmem + g->dat.taps), (const int8_t*)(dmem + g->dat.hist), (int)g->K, (int)g->q,
                              r.off, r.slot0, (unsigned)g->dat.per};
-      const size_t wgs = (p.l1_items + win::NW1 - 1) / win::NW1;
-      if (const int rc = launch_l1(sc.ds, stream::k_layer1_ring_decim<XR, CB>, wgs, st, v.sets, v.n_sets, set_of, v.scales,
-                                   (const int8_t*)x, ring, (int)p.l1_items, (int)p.blocks, (int)n_raw, (int)r.m, p.p0,
-                                   (int)g->cap, dc))
+      if (const int rc = launch_l1(o.sc.ds, stream::k_layer1_ring_decim<XR, CB>, l1_wgs(p.l1_items), o.st, o.v.sets,
+                                   o.v.n_sets, o.set_of, o.v.scales, (const int8_t*)x, o.ring, (int)p.l1_items, (int)p.blocks,
+                                   (int)n_raw, (int)r.m, p.p0, (int)g->cap, dc))
         return rc;
     }
     if (r.keep) {
-      const size_t blocks = std::min((r.hist_items + 255) / 256, (size_t)sc.ds.cus * 8);
-      hipLaunchKernelGGL(stream::k_history_update, dim3((unsigned)blocks), dim3(256), 0, st, x,
+      const size_t blocks = std::min((r.hist_items + 255) / 256, (size_t)o.sc.ds.cus * 8);
+      hipLaunchKernelGGL(stream::k_history_update, dim3((unsigned)blocks), dim3(256), 0, o.st, x,
                          (float*)(dmem + g->dat.hist), (unsigned long long)r.hist_items, (unsigned)hg.C, (unsigned)n_raw,
                          (unsigned)r.keep, (unsigned)g->K, (unsigned)r.slot0);
       if (const int rc = hip_err(hipGetLastError())) return rc;
     }
     if (r.m == 0 || p.k == 0) return (int)NET_OK;
-    return launch_items(sc.ds, stream::k_forward_ring<RB, XR, CB>, windows_lds(hg), p.items, st, v.sets, v.n_sets,
-                        (const int8_t*)ring, origin, set_of, y, (int*)n_bad, (int)p.items, (int)p.k, p.first, p.hop,
-                        p.first_mod, (int)g->cap);
+    return launch_ring_windows<RB, XR, CB>(o, *g, p, y, n_bad);
   });
   if (rc) return rc;
   g->raw_pos += n_raw;
@@ -762,28 +774,21 @@ int streams_push_each(net_streams* g, const void* x, int arg_layout, bool f32, c
   if (const int rc = stream::check_push_each(g->S, g->hop, g->max_push, x, arg_layout, f32, !b.scales.empty(), cnt_in,
                                              n_max, y, cnt_out, win0, n_bad, p))
     return rc;
-  DeviceScope sc(g->device, b);
-  if (sc.rc) return sc.rc;
-  const hipStream_t st = (hipStream_t)stream;
-  const BankView v = bank_view(sc, b, f32);
-  int8_t* ring = (int8_t*)g->mem;
-  const int* set_of = (const int*)(ring + g->at.set);
-  auto* plan = (stream::EachRec*)(ring + g->plan_at);
-  hipLaunchKernelGGL(stream::k_stream_plan, dim3((unsigned)((g->S + 255) / 256)), dim3(256), 0, st, (const int*)cnt_in,
-                     (long long*)(ring + g->pos_at), plan, (int*)cnt_out, (long long*)win0, (int*)n_bad, (int)g->S, hg.T,
+  const OpenGroup o(*g, stream, ALLOW_CAPTURE, f32);
+  if (o.rc) return o.rc;
+  hipLaunchKernelGGL(stream::k_stream_plan, dim3((unsigned)((g->S + 255) / 256)), dim3(256), 0, o.st, (const int*)cnt_in,
+                     o.pos, o.plan, (int*)cnt_out, (long long*)win0, (int*)n_bad, (int)g->S, hg.T,
                      (unsigned long long)g->hop, (int)g->cap, (int)n_max);
   if (const int rc = hip_err(hipGetLastError())) return rc;
   const int rc = with_layout<true>(f32 ? gen::float_layout(arg_layout) : arg_layout, [&](auto lc) {
     return with_flags(hg, [&](auto rb, auto xr, auto cb) {
       constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
-      const size_t wgs = (p.l1_items + win::NW1 - 1) / win::NW1;
-      if (const int rc = launch_l1(sc.ds, stream::k_layer1_ring_each<decltype(lc)::value, XR, CB>, wgs, st, v.sets,
-                                   v.n_sets, set_of, v.scales, (const int8_t*)x, ring, (const stream::EachRec*)plan,
+      if (const int rc = launch_l1(o.sc.ds, stream::k_layer1_ring_each<decltype(lc)::value, XR, CB>, l1_wgs(p.l1_items),
+                                   o.st, o.v.sets, o.v.n_sets, o.set_of, o.v.scales, (const int8_t*)x, o.ring, o.plan,
                                    (int)p.l1_items, (int)p.blocks, (int)n_max, (int)g->cap))
         return rc;
-      return launch_items(sc.ds, stream::k_forward_ring_each<RB, XR, CB>, windows_lds(hg), p.items, st, v.sets, v.n_sets,
-                          (const int8_t*)ring, (const stream::EachRec*)plan, set_of, y, (int)p.items, (int)p.kmax, p.hop,
-                          (int)g->cap);
+      return launch_items(o.sc.ds, stream::k_forward_ring_each<RB, XR, CB>, windows_lds(hg), p.items, o.st, o.v.sets,
+                          o.v.n_sets, o.ring, o.plan, o.set_of, y, (int)p.items, (int)p.kmax, p.hop, (int)g->cap);
     });
   });
   if (rc) return rc;
@@ -800,24 +805,18 @@ int streams_windows_at(net_streams* g, const int32_t* session, const int64_t* on
   if (W == 0) return NET_OK;
   if (with_feat)
     if (const int rc = check_feat(W, feat)) return rc;
-  const net_bank& b = *g->bank;
-  const gen::GenParams& hg = b.sets[0];
-  DeviceScope sc(g->device, b);
-  if (sc.rc) return sc.rc;
-  const hipStream_t st = (hipStream_t)stream;
-  if (!g->each && capturing(st)) return NET_ERR_UNSUPPORTED;
-  const BankView v = bank_view(sc, b, false);  // layer 1 ran at the push: no scales here
-  const int8_t* ring = (const int8_t*)g->mem;
-  const int* set_of = (const int*)(ring + g->at.set);
-  const long long* lim = (const long long*)(ring + (g->each ? g->pos_at : g->at.origin));
+  const gen::GenParams& hg = g->bank->sets[0];
+  const OpenGroup o(*g, stream, g->each ? ALLOW_CAPTURE : REFUSE_CAPTURE);  // layer 1 ran at the push: no scales
+  if (o.rc) return o.rc;
+  const long long* lim = g->each ? o.pos : o.origin;
   const long long pos = g->each ? 0ll : (long long)g->pos;
   const int pos_mod = g->each ? 0 : (int)(g->pos % g->cap);
   return with_flags(hg, [&](auto rb, auto xr, auto cb) {
     constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
     // f: nothing, or the feature rows' pointer, which the _feat kernel takes after y
     auto go = [&](auto kern, auto... f) {
-      return launch_items(sc.ds, kern, windows_lds(hg), W, st, v.sets, v.n_sets, ring, (const int*)session,
-                          (const long long*)onsets, lim, set_of, y, f..., (int*)n_bad, (int)W, (int)g->S, pos, pos_mod,
+      return launch_items(o.sc.ds, kern, windows_lds(hg), W, o.st, o.v.sets, o.v.n_sets, o.ring, (const int*)session,
+                          (const long long*)onsets, lim, o.set_of, y, f..., (int*)n_bad, (int)W, (int)g->S, pos, pos_mod,
                           (int)g->cap);
     };
     if (with_feat)
@@ -835,10 +834,9 @@ int streams_at_span(const net_streams* g, int64_t* lo, int64_t* hi) {
 
 int streams_positions(net_streams* g, int64_t* pos_out, void* stream) {
   if (!g || !g->each || !pos_out || ((uintptr_t)pos_out & 7) != 0) return NET_ERR_INVALID;
-  DeviceScope sc(g->device, *g->bank);
-  if (sc.rc) return sc.rc;
-  return hip_err(hipMemcpyAsync(pos_out, (const char*)g->mem + g->pos_at, 8 * g->S, hipMemcpyDeviceToDevice,
-                                (hipStream_t)stream));
+  const OpenGroup o(*g, stream, ALLOW_CAPTURE);
+  if (o.rc) return o.rc;
+  return hip_err(hipMemcpyAsync(pos_out, o.pos, 8 * g->S, hipMemcpyDeviceToDevice, o.st));
 }
 
 // Runs one reference-layout single-trial stage on the single-trial device.

@@ -163,7 +163,7 @@ int mibminet_test_streams_ring(const net_streams_t* st, size_t i, void* out) {
   DeviceGuard guard(st->device);
   if (guard.err != hipSuccess) return hip_err(guard.err);
   hipError_t e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out, (const char*)st->mem + i * st->at.ring, st->at.ring, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(out, (const char*)st->mem + i * st->at.base.ring, st->at.base.ring, hipMemcpyDeviceToHost);
   return hip_err(e);
 }
 

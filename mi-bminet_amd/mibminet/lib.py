@@ -255,7 +255,38 @@ def _dims():
     return _loaded.dims
 
 
-class Bank:
+class _Handle:
+    """A handle of the library's with ``close()``, usable as a context manager.  A subclass names its
+    destroy entry (``_destroy``) and what ``handle`` says once it is closed (``_closed``).  ``_h`` is
+    None until the create entry has returned, so ``__del__`` after a failed constructor is harmless."""
+
+    _h = _destroy = _closed = None
+
+    @property
+    def handle(self) -> int:
+        if self._h is None:
+            raise ValueError(self._closed)
+        return self._h
+
+    def close(self) -> None:
+        if self._h is not None:
+            getattr(load(), self._destroy)(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover - interpreter shutdown
+            pass
+
+
+class Bank(_Handle):
     """net_bank_create: many parameter sets of one geometry resident side by side, for
     forward_epochs_bank_torch and forward_bank_torch.  ``param_sets`` holds ParamSets or blobs,
     ``scales`` nothing or one input-quantiser scale per set (needed for float32 input).  Independent
@@ -263,8 +294,9 @@ class Bank:
     ``close()`` (or leaving the ``with`` block) frees the bank and its device copies after
     synchronising the devices that hold one; no call on the bank may be in flight then."""
 
+    _destroy, _closed = "net_bank_destroy", "the bank is closed"
+
     def __init__(self, param_sets, scales=None):
-        self._h = None
         blobs = [p.to_blob() if isinstance(p, ParamSet) else bytes(p) for p in param_sets]
         n = len(blobs)
         if scales is not None and len(scales) != n:
@@ -283,12 +315,6 @@ class Bank:
         info = self.info()
         self.n_sets, self.exact_division, self.has_scales = info[0], bool(info[4]), bool(info[5])
         self.dims = ParamSet.from_blob(blobs[0]).dims
-
-    @property
-    def handle(self) -> int:
-        if self._h is None:
-            raise ValueError("the bank is closed")
-        return self._h
 
     def info(self) -> list:
         """net_bank_info: [n_sets, C, T, N, exact_division, has_scales, bytes per set]."""
@@ -332,23 +358,6 @@ class Bank:
         buf = ctypes.create_string_buffer(blob, len(blob))
         _check(load().net_bank_replace(self.handle, s, buf, len(blob), 0.0 if scale is None else float(scale), device, st),
                f"net_bank_replace, set {s}")
-
-    def close(self) -> None:
-        if self._h is not None:
-            load().net_bank_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover - interpreter shutdown
-            pass
 
 
 def image_copy(which: int) -> bytes:
@@ -541,10 +550,14 @@ def _torch():
     return torch
 
 
+def _stream_on(device, stream):
+    """The stream to launch on: ``stream``, or without one the current stream of ``device``."""
+    return _torch().cuda.current_stream(device) if stream is None else stream
+
+
 def _launch(x, stream):
     """(launch stream, device index) for the device tensor ``x`` and an optional ``stream``."""
-    s = _torch().cuda.current_stream(x.device) if stream is None else stream
-    return s, x.device.index or 0
+    return _stream_on(x.device, stream), x.device.index or 0
 
 
 def _logits(x, rows: int):
@@ -1082,77 +1095,28 @@ def forward_windows_multi_bank_torch(bank, recordings, sets, hop: int, layout: s
         return _stitch(net, tensors[0], out), first
 
 
-def _streams_windows_at(group, sessions, onsets, stream, out, check: bool, features: bool = False):
-    """net_streams_windows_at on ``group`` (a Streams or a StreamsEach): the windows of sessions
-    ``sessions[w]`` that start at samples ``onsets[w]``, read from the layer-1 rings as they are.  The
-    lists are device tensors (int32 and int64, 1-D) or sequences of ints, through _index_list; their
-    device copies and the zeroed counter are made on the launch stream.  ``check`` is
-    forward_windows_at_torch's: the stream is synchronised, the count of invalid items read back and
-    a ValueError raised if it is not zero; ``check=False`` passes NULL for the counter.  Returns the
-    logits [W][N]; with ``features`` (net_streams_windows_at_feat) the pair (logits, features
-    [W][16][T64] int8), a zero feature row beside every zero logit row."""
-    torch = _torch()
-    ses = _index_list(sessions, torch.int32, "sessions")
-    ons = _index_list(onsets, torch.int64, "onsets")
-    W, N = int(ses.numel()), group.bank.dims.N
-    if int(ons.numel()) != W:
-        raise ValueError(f"{W} sessions for {int(ons.numel())} onsets")
-    dev = torch.device("cuda", group.device)
-    s = torch.cuda.current_stream(group.device) if stream is None else stream
-    with torch.cuda.stream(s):  # the lists' copies and the counter's zeroing precede the launch on its stream
-        ses, ons = ses.to(dev).contiguous(), ons.to(dev).contiguous()
-        nbad = torch.zeros((1,), dtype=torch.int32, device=dev) if check else None
-        if out is None:
-            out = torch.empty((W, N), dtype=torch.int8, device=dev)
-        d = group.bank.dims
-        feat = torch.empty((W, d.F2, d.T64), dtype=torch.int8, device=dev) if features else None
-    _check_tensor(out, "out", ("int8",), (W, N))
-    lead = (group.handle, ses.data_ptr() if W else None, ons.data_ptr() if W else None, W, out.data_ptr() if W else None)
-    tail = (nbad.data_ptr() if check else None, s.cuda_stream)
-    if features:
-        _check(load().net_streams_windows_at_feat(*lead, feat.data_ptr() if W else None, *tail),
-               "net_streams_windows_at_feat")
-    else:
-        _check(load().net_streams_windows_at(*lead, *tail), "net_streams_windows_at")
-    if check and W:
-        s.synchronize()
-        bad = int(nbad.item())
-        if bad:
-            raise ValueError(f"{bad} of {W} windows are not in the rings (their logit rows are zero)")
-    return (out, feat) if features else out
+class _StreamGroup(_Handle):
+    """What Streams and StreamsEach share: the constructor (``_create`` names the create entry), the
+    entries that take either kind of group, and the checks of a push's ``x``.  The subclasses keep
+    the docstrings that differ between the two kinds."""
 
-
-class Streams:
-    """net_streams_create: ``len(sets)`` live sessions of ``bank``'s geometry on ``device``, session i
-    decoded by set ``sets[i]`` (``sets`` an int: that many sessions under set 0), windows at every
-    ``hop``-th sample of the global grid, at most ``max_push`` samples per session and push.  The group
-    keeps a device-resident ring of layer-1 outputs per session; ``push`` runs layer 1 on the new
-    samples only and returns the windows that end in them.  All pushes and restarts of a group must
-    be ordered with respect to one another (one stream, or events).  The bank must outlive the group;
-    ``close()`` (or leaving the ``with`` block) synchronises the device and frees it."""
+    _destroy, _closed, _create = "net_streams_destroy", "the stream group is closed", None
 
     def __init__(self, bank, sets, hop: int, max_push: int, device: int = 0):
-        self._h = None
         self.bank = _require_bank(bank)
         ss = [0] * sets if isinstance(sets, int) else [int(v) for v in sets]
         if hop < 1 or max_push < 1 or not ss:
             raise ValueError("at least one session, hop and max_push at least 1")
         arr = (ctypes.c_int32 * len(ss))(*ss)
         h = ctypes.c_void_p()
-        _check(load().net_streams_create(bank.handle, arr, len(ss), hop, max_push, device, ctypes.byref(h)),
-               "net_streams_create")
+        _check(getattr(load(), self._create)(bank.handle, arr, len(ss), hop, max_push, device, ctypes.byref(h)),
+               self._create)
         self._h = h.value
         self.S, self.hop, self.max_push, self.device = len(ss), hop, max_push, device
         self.cap = self.info()[3]
 
-    @property
-    def handle(self) -> int:
-        if self._h is None:
-            raise ValueError("the stream group is closed")
-        return self._h
-
     def info(self) -> list:
-        """net_streams_info: [S, hop, max_push, cap, position, windows returned per session so far]."""
+        """net_streams_info: six int64 values."""
         arr = (ctypes.c_int64 * 6)()
         _check(load().net_streams_info(self.handle, arr), "net_streams_info")
         return list(arr)
@@ -1163,14 +1127,87 @@ class Streams:
         _check(load().net_streams_origin(self.handle, i, ctypes.byref(o), ctypes.byref(s)), "net_streams_origin")
         return o.value, s.value
 
+    def restart(self, i: int, set: int, stream=None) -> None:
+        """net_streams_restart of session ``i`` under ``set``."""
+        _check(load().net_streams_restart(self.handle, i, set, _stream_on(self.device, stream).cuda_stream),
+               "net_streams_restart")
+
+    def windows_at(self, sessions, onsets, stream=None, out=None, check: bool = True, features: bool = False):
+        """net_streams_windows_at: the windows of sessions ``sessions[w]`` that start at samples
+        ``onsets[w]``, read from the layer-1 rings as they are.  The lists are device tensors (int32 and
+        int64, 1-D) or sequences of ints, through _index_list; their device copies and the zeroed
+        counter are made on the launch stream.  ``check`` is forward_windows_at_torch's: the stream is
+        synchronised, the count of invalid items read back and a ValueError raised if it is not zero;
+        ``check=False`` passes NULL for the counter.  Returns the logits [W][N]; with ``features``
+        (net_streams_windows_at_feat) the pair (logits, features [W][16][T64] int8), a zero feature
+        row beside every zero logit row."""
+        torch = _torch()
+        ses = _index_list(sessions, torch.int32, "sessions")
+        ons = _index_list(onsets, torch.int64, "onsets")
+        d = self.bank.dims
+        W, N = int(ses.numel()), d.N
+        if int(ons.numel()) != W:
+            raise ValueError(f"{W} sessions for {int(ons.numel())} onsets")
+        dev = torch.device("cuda", self.device)
+        s = _stream_on(self.device, stream)
+        with torch.cuda.stream(s):  # the lists' copies and the counter's zeroing precede the launch on its stream
+            ses, ons = ses.to(dev).contiguous(), ons.to(dev).contiguous()
+            nbad = torch.zeros((1,), dtype=torch.int32, device=dev) if check else None
+            if out is None:
+                out = torch.empty((W, N), dtype=torch.int8, device=dev)
+            feat = torch.empty((W, d.F2, d.T64), dtype=torch.int8, device=dev) if features else None
+        _check_tensor(out, "out", ("int8",), (W, N))
+        lead = (self.handle, ses.data_ptr() if W else None, ons.data_ptr() if W else None, W, out.data_ptr() if W else None)
+        tail = (nbad.data_ptr() if check else None, s.cuda_stream)
+        if features:
+            _check(load().net_streams_windows_at_feat(*lead, feat.data_ptr() if W else None, *tail),
+                   "net_streams_windows_at_feat")
+        else:
+            _check(load().net_streams_windows_at(*lead, *tail), "net_streams_windows_at")
+        if check and W:
+            s.synchronize()
+            bad = int(nbad.item())
+            if bad:
+                raise ValueError(f"{bad} of {W} windows are not in the rings (their logit rows are zero)")
+        return (out, feat) if features else out
+
+    def _push_source(self, x, layout: str, f32: bool) -> tuple:
+        """Checks a push's ``x``, int8 or (``f32``) float32, [S][C][n] or [S][n][C] by ``layout``.  Returns
+        the entry's suffix ("", "_f32" or "_f32_tm"), the layout code as the entry takes it (the
+        float32 entries take none) and n."""
+        code = _layout_code(layout)
+        if f32 and not self.bank.has_scales:
+            raise ValueError("a float32 source needs a bank created with scales")
+        C, ct = self.bank.dims.C, layout == "ct"
+        _check_tensor(x, "x", ("float32",) if f32 else ("int8",), (self.S, C, "n") if ct else (self.S, "n", C))
+        n = int(x.shape[2 if ct else 1])
+        return ("_f32" if ct else "_f32_tm", (), n) if f32 else ("", (code,), n)
+
+
+class Streams(_StreamGroup):
+    """net_streams_create: ``len(sets)`` live sessions of ``bank``'s geometry on ``device``, session i
+    decoded by set ``sets[i]`` (``sets`` an int: that many sessions under set 0), windows at every
+    ``hop``-th sample of the global grid, at most ``max_push`` samples per session and push.  The group
+    keeps a device-resident ring of layer-1 outputs per session; ``push`` runs layer 1 on the new
+    samples only and returns the windows that end in them.  All pushes and restarts of a group must
+    be ordered with respect to one another (one stream, or events).  The bank must outlive the group;
+    ``close()`` (or leaving the ``with`` block) synchronises the device and frees it."""
+
+    _create = "net_streams_create"
+
+    def info(self) -> list:
+        """net_streams_info: [S, hop, max_push, cap, position, windows returned per session so far]."""
+        return super().info()
+
     def windows(self, n: int) -> int:
         """net_streams_push_windows: the windows per session the next push of ``n`` samples returns."""
         return int(load().net_streams_push_windows(self.bank.handle, self.hop, self.info()[4], n))
 
-    def _push(self, x, dtype: str, code, n: int, stream, out):
-        """``dtype``: the entry's suffix, "" (int8), "_f32" or "_f32_tm"."""
+    def _push(self, x, dtype: str, code, n: int, stream, out, k: Optional[int] = None):
+        """``dtype``: the entry's suffix, "" (int8), "_f32", "_f32_tm" or "_raw_f32_tm"; ``k``: the windows
+        per session, where they are not ``windows(n)``."""
         torch = _torch()
-        k, N = self.windows(n), self.bank.dims.N
+        k, N = self.windows(n) if k is None else k, self.bank.dims.N
         s, _ = _launch(x, stream)
         with torch.cuda.stream(s):  # the counter's zeroing precedes the launch on its stream
             nbad = torch.zeros((1,), dtype=torch.int32, device=x.device)
@@ -1190,33 +1227,23 @@ class Streams:
         returns for that window of session i's samples with its set loaded; the rows of windows that
         start before a session's origin are zero and counted in ``n_bad``, a device int32 tensor of one
         element (no host sync here).  ``out``: an int8 device tensor [S][k][N] to write instead."""
-        code = _layout_code(layout)
-        C = self.bank.dims.C
-        _check_tensor(x, "x", ("int8",), (self.S, C, "n") if layout == "ct" else (self.S, "n", C))
-        return self._push(x, "", (code,), int(x.shape[2 if layout == "ct" else 1]), stream, out)
+        return self._push(x, *self._push_source(x, layout, False), stream, out)
 
     def push_f32(self, x, stream=None, out=None, layout: str = "ct"):
         """net_streams_push_f32 / _f32_tm: ``x`` is a CUDA/HIP float32 tensor, "ct" = [S][C][n] or "tc" =
         [S][n][C] (frames as an amplifier delivers them); session i is quantised with the bank's scale
         of its set.  Returns what push returns."""
-        _layout_code(layout)
-        if not self.bank.has_scales:
-            raise ValueError("a float32 source needs a bank created with scales")
-        C = self.bank.dims.C
-        _check_tensor(x, "x", ("float32",), (self.S, C, "n") if layout == "ct" else (self.S, "n", C))
-        return self._push(x, "_f32" if layout == "ct" else "_f32_tm", (), int(x.shape[2 if layout == "ct" else 1]), stream,
-                          out)
+        return self._push(x, *self._push_source(x, layout, True), stream, out)
 
     def decimate(self, q: int, taps, stream=None) -> None:
         """net_streams_set_decimator: once, before the first push.  From then on the group takes raw
         float32 frames at ``q`` times the network's rate through ``push_raw`` and filters them with
         the FIR ``taps`` (K <= 128 finite float32 values, q <= 16; decimate.firwin_taps(q) is a
         default) inside the layer-1 kernel, bit for bit as decimate.fir_decimate states it."""
-        torch = _torch()
         h = np.ascontiguousarray(taps, dtype=np.float32)
         if h.ndim != 1:
             raise ValueError("taps must be a 1-D array")
-        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        s = _stream_on(self.device, stream)
         _check(load().net_streams_set_decimator(self.handle, q, h.ctypes.data, h.size, s.cuda_stream),
                "net_streams_set_decimator")
 
@@ -1233,20 +1260,10 @@ class Streams:
         if not self.bank.has_scales:
             raise ValueError("a float32 source needs a bank created with scales")
         _check_tensor(frames, "frames", ("float32",), (self.S, "n", self.bank.dims.C))
-        torch = _torch()
         q, _, P, D = self.raw_info()
-        n_raw, N = int(frames.shape[1]), self.bank.dims.N
+        n_raw = int(frames.shape[1])
         k = int(load().net_streams_push_windows(self.bank.handle, self.hop, D, raw_samples(q, P, n_raw)))
-        s, _ = _launch(frames, stream)
-        with torch.cuda.stream(s):  # the counter's zeroing precedes the launch on its stream
-            nbad = torch.zeros((1,), dtype=torch.int32, device=frames.device)
-        if out is None:
-            out = torch.empty((self.S, k, N), dtype=torch.int8, device=frames.device)
-        else:
-            _check_tensor(out, "out", ("int8",), (self.S, k, N))
-        _check(load().net_streams_push_raw_f32_tm(self.handle, frames.data_ptr(), n_raw, out.data_ptr() if k else None,
-                                                  nbad.data_ptr(), s.cuda_stream), "net_streams_push_raw_f32_tm")
-        return out, nbad
+        return self._push(frames, "_raw_f32_tm", (), n_raw, stream, out, k)
 
     def windows_at(self, sessions, onsets, stream=None, out=None, check: bool = True, features: bool = False):
         """net_streams_windows_at: the windows of sessions ``sessions[w]`` whose first samples are
@@ -1261,7 +1278,7 @@ class Streams:
         tensor [W][N] to write instead.  Ordered like a push; moves nothing.  With ``features``
         returns (logits, features [W][16][T // 64] int8): each window's layer-4 output under its
         session's set (forward_epochs_bank_torch), zeros beside a zero logit row."""
-        return _streams_windows_at(self, sessions, onsets, stream, out, check, features)
+        return super().windows_at(sessions, onsets, stream, out, check, features)
 
     def at_span(self) -> tuple:
         """net_streams_at_span: (lo, hi), the onsets whose windows are in the rings now, lo =
@@ -1275,29 +1292,10 @@ class Streams:
         """net_streams_restart: from the next push session ``i`` is decoded by ``set`` and answers no
         window that starts before the current position.  ``stream``: a torch stream (default: the
         current one of the group's device)."""
-        torch = _torch()
-        s = torch.cuda.current_stream(self.device) if stream is None else stream
-        _check(load().net_streams_restart(self.handle, i, set, s.cuda_stream), "net_streams_restart")
-
-    def close(self) -> None:
-        if self._h is not None:
-            load().net_streams_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover - interpreter shutdown
-            pass
+        super().restart(i, set, stream)
 
 
-class StreamsEach:
+class StreamsEach(_StreamGroup):
     """net_streams_create_each: a stream group whose sessions advance at their own pace.  Every
     session has its own position in device memory, a push hands session i ``counts[i]`` samples
     (0 .. n_max, 0: it skips the tick) and returns the windows of the session's own grid that end in
@@ -1307,37 +1305,15 @@ class StreamsEach:
     position copies of a group ordered with respect to one another), the bank's lifetime and
     ``close()`` are Streams'."""
 
-    def __init__(self, bank, sets, hop: int, max_push: int, device: int = 0):
-        self._h = None
-        self.bank = _require_bank(bank)
-        ss = [0] * sets if isinstance(sets, int) else [int(v) for v in sets]
-        if hop < 1 or max_push < 1 or not ss:
-            raise ValueError("at least one session, hop and max_push at least 1")
-        arr = (ctypes.c_int32 * len(ss))(*ss)
-        h = ctypes.c_void_p()
-        _check(load().net_streams_create_each(bank.handle, arr, len(ss), hop, max_push, device, ctypes.byref(h)),
-               "net_streams_create_each")
-        self._h = h.value
-        self.S, self.hop, self.max_push, self.device = len(ss), hop, max_push, device
-        self.cap = self.info()[3]
-
-    @property
-    def handle(self) -> int:
-        if self._h is None:
-            raise ValueError("the stream group is closed")
-        return self._h
+    _create = "net_streams_create_each"
 
     def info(self) -> list:
         """net_streams_info: [S, hop, max_push, cap, pushes enqueued so far, -1]."""
-        arr = (ctypes.c_int64 * 6)()
-        _check(load().net_streams_info(self.handle, arr), "net_streams_info")
-        return list(arr)
+        return super().info()
 
     def origin(self, i: int) -> tuple:
         """net_streams_origin: (-1, the set of session ``i``): an each-group keeps no origin."""
-        o, s = ctypes.c_int64(0), ctypes.c_int32(0)
-        _check(load().net_streams_origin(self.handle, i, ctypes.byref(o), ctypes.byref(s)), "net_streams_origin")
-        return o.value, s.value
+        return super().origin(i)
 
     def rows(self, n_max: int) -> int:
         """net_streams_each_rows: kmax, the rows per session of a push of at most ``n_max`` samples."""
@@ -1346,7 +1322,7 @@ class StreamsEach:
     def positions(self, stream=None):
         """net_streams_positions: the sessions' positions, an int64 device tensor [S] (no host sync)."""
         torch = _torch()
-        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        s = _stream_on(self.device, stream)
         with torch.cuda.stream(s):
             out = torch.empty((self.S,), dtype=torch.int64, device=f"cuda:{self.device}")
         _check(load().net_streams_positions(self.handle, out.data_ptr(), s.cuda_stream), "net_streams_positions")
@@ -1379,22 +1355,13 @@ class StreamsEach:
         end in this push, what forward_ct_torch returns for them with its set loaded; the other rows
         are not written.  A count outside 0 .. n_max gives cnt_out[i] = -1, moves nothing and is counted
         in n_bad.  ``out``: an int8 device tensor [S][kmax][N] to write instead."""
-        code = _layout_code(layout)
-        C = self.bank.dims.C
-        _check_tensor(x, "x", ("int8",), (self.S, C, "n") if layout == "ct" else (self.S, "n", C))
-        return self._push(x, "", (code,), int(x.shape[2 if layout == "ct" else 1]), counts, stream, out)
+        return self._push(x, *self._push_source(x, layout, False), counts, stream, out)
 
     def push_f32(self, x, counts, stream=None, out=None, layout: str = "ct"):
         """net_streams_push_each_f32 / _f32_tm: ``x`` is a CUDA/HIP float32 tensor of fixed slots, "ct" =
         [S][C][n_max] or "tc" = [S][n_max][C]; session i is quantised with the bank's scale of its
         set.  Returns what push returns."""
-        _layout_code(layout)
-        if not self.bank.has_scales:
-            raise ValueError("a float32 source needs a bank created with scales")
-        C = self.bank.dims.C
-        _check_tensor(x, "x", ("float32",), (self.S, C, "n") if layout == "ct" else (self.S, "n", C))
-        return self._push(x, "_f32" if layout == "ct" else "_f32_tm", (), int(x.shape[2 if layout == "ct" else 1]), counts,
-                          stream, out)
+        return self._push(x, *self._push_source(x, layout, True), counts, stream, out)
 
     def windows_at(self, sessions, onsets, stream=None, out=None, check: bool = True, features: bool = False):
         """net_streams_windows_at on an each-group: Streams.windows_at with every onset in its
@@ -1402,32 +1369,13 @@ class StreamsEach:
         pos - T of its position (``positions()``).  With device tensors and ``check=False`` the call
         reads nothing from the host and, after one eager call, may be captured behind a push.
         ``features``: Streams.windows_at's."""
-        return _streams_windows_at(self, sessions, onsets, stream, out, check, features)
+        return super().windows_at(sessions, onsets, stream, out, check, features)
 
     def restart(self, i: int, set: int, stream=None) -> None:
         """net_streams_restart on an each-group: session ``i`` starts again at position 0 under
         ``set``; its grid starts at its next sample.  ``stream``: a torch stream (default: the current
         one of the group's device)."""
-        torch = _torch()
-        s = torch.cuda.current_stream(self.device) if stream is None else stream
-        _check(load().net_streams_restart(self.handle, i, set, s.cuda_stream), "net_streams_restart")
-
-    def close(self) -> None:
-        if self._h is not None:
-            load().net_streams_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # pragma: no cover - interpreter shutdown
-            pass
+        super().restart(i, set, stream)
 
 
 def streams_ring(streams, i: int) -> np.ndarray:

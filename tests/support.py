@@ -243,6 +243,49 @@ def loaded():
     lib.params_unload()
 
 
+# ---- the GPU suites of the bank and stream entries --------------------------------------------------
+CAPS = (1, 3, 0)  # lib.grid_cap: one workgroup, three, and the normal grid
+GUARD = 0x5A      # the byte around and under what a call writes
+
+
+@pytest.fixture
+def capped(gpu):
+    """lib.grid_cap for the test; the cap is 0 again afterwards whatever happens."""
+    try:
+        yield lib.grid_cap
+    finally:
+        lib.grid_cap(0)
+
+
+def dev(torch, a):
+    """`a` on the device, 4 bytes off a 16-byte boundary (a copy: the shared arrays are read-only)."""
+    return at_offset(torch, np.array(a), 4)
+
+
+def same(rows, expect, what=""):
+    """Two arrays of rows, [n][N] or [n][...] (a row is everything under its first index)."""
+    assert rows.shape == expect.shape, (what, rows.shape, expect.shape)
+    bad = np.flatnonzero((rows != expect).any(axis=tuple(range(1, rows.ndim))))
+    assert bad.size == 0, f"{what}: {bad.size} of {len(expect)} rows differ, first {bad[:5]}"
+
+
+def same_each(rows, expect, what=""):
+    """Two lists of per-session arrays [k_i][N]."""
+    assert len(rows) == len(expect)
+    for i, (r, e) in enumerate(zip(rows, expect)):
+        assert r.shape == e.shape, (what, i, r.shape, e.shape)
+        bad = np.flatnonzero((r != e).any(axis=1))
+        assert bad.size == 0, f"{what} session {i}: {bad.size} of {len(e)} windows differ, first {bad[:5]}"
+
+
+def same_rows(got, expect, what=""):
+    """Two arrays [...][N] (a row is the last axis); `got` may be a list of arrays."""
+    got = np.asarray(got)
+    assert got.shape == expect.shape, (what, got.shape, expect.shape)
+    bad = np.flatnonzero((got != expect).any(axis=-1).reshape(-1))
+    assert bad.size == 0, f"{what}: {bad.size} of {expect[..., 0].size} rows differ, first {bad[:5]}"
+
+
 # ---- the stand-alone host programs under the sanitizers ---------------------------------------------
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mi-bminet_amd", "csrc")

@@ -7,7 +7,9 @@ import dataclasses
 import functools
 
 import numpy as np
+import pytest
 
+from mibminet import lib
 from mibminet.params import ParamSet
 from support import epochs_of, want
 
@@ -25,6 +27,21 @@ LAYERS = {k: tuple(f.name for f in dataclasses.fields(ParamSet) if f.name.starts
 def sets(C, T, N, **kw):
     """The five sets of a geometry (kw as ParamSet.synthetic takes it)."""
     return tuple(ParamSet.synthetic(seed=s, C=C, T=T, N=N, **kw) for s in SEEDS)
+
+
+@pytest.fixture(scope="module")
+def banks(gpu):
+    """The five-set banks of the module, by geometry, built once and closed at the end."""
+    cache = {}
+
+    def get(C, T, N):
+        if (C, T, N) not in cache:
+            cache[(C, T, N)] = lib.Bank(sets(C, T, N))
+        return cache[(C, T, N)]
+
+    yield get
+    for b in cache.values():
+        b.close()
 
 
 def _extreme(C, T, N, **kw):

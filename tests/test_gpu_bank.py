@@ -19,19 +19,9 @@ import support_bank as sb
 from mibminet import lib
 from mibminet.params import ParamSet
 from oracle import golden_np as G
-from support import _BAD, NTH, at_offset, scattered, want
+from support import _BAD, CAPS, NTH, at_offset, capped, scattered, want  # noqa: F401 (capped: a fixture)
 
 pytestmark = pytest.mark.gpu
-CAPS = (1, 3, 0)  # one workgroup, three, and the normal grid
-
-
-@pytest.fixture
-def capped(gpu):
-    """lib.grid_cap for the test; the cap is 0 again afterwards whatever happens."""
-    try:
-        yield lib.grid_cap
-    finally:
-        lib.grid_cap(0)
 
 
 @pytest.fixture(scope="module")

@@ -16,18 +16,12 @@ import support_streams as ss
 import support_streams_each as se
 from mibminet import lib
 from mibminet.params import ParamSet
-from support import SCALE, at_offset, dequant, want
+from support import SCALE, at_offset, dequant, same, want
 
 pytestmark = pytest.mark.gpu
 E, SLOT = sf.E, sf.SLOT
 UNS = lib.NET_ERR_UNSUPPORTED
 S, X = ParamSet.synthetic, ParamSet.synthetic_extreme
-
-
-def same(rows, expect, what=""):
-    assert rows.shape == expect.shape, (what, rows.shape, expect.shape)
-    bad = np.flatnonzero((rows != expect).any(axis=1))
-    assert bad.size == 0, f"{what}: {bad.size} of {len(expect)} rows differ, first {bad[:5]}"
 
 
 def _expected(C, T, N, so, new=None):

@@ -24,7 +24,7 @@ import support_streams as ss
 import support_windows_bank as swb
 from mibminet import lib
 from mibminet.params import ParamSet
-from support import at_offset, sliding_windows, want, windows_at
+from support import capped, dev, same_rows, sliding_windows, want, windows_at  # noqa: F401 (capped: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -35,15 +35,6 @@ SCALES = (0.5, 3.0, 7.25)
 HOP, MAX_PUSH = ss.HOP, ss.MAX_PUSH
 NAN, INF = float("nan"), float("inf")
 S_, X_ = ParamSet.synthetic, ParamSet.synthetic_extreme
-
-
-@pytest.fixture
-def capped(gpu):
-    """lib.grid_cap for the test; the cap is 0 again afterwards whatever happens."""
-    try:
-        yield lib.grid_cap
-    finally:
-        lib.grid_cap(0)
 
 
 # ---- inputs and references, once per geometry -----------------------------------------------------
@@ -65,11 +56,6 @@ def plant(x_tc, ends):
             x_tc[e - 1, C - 1] = kinds[i % 3]
             x_tc[e, 0] = kinds[(i + 1) % 3]
     x_tc[0, 0], x_tc[0, C - 1], x_tc[L - 1, 0], x_tc[L - 1, C - 1] = NAN, -INF, INF, NAN
-
-
-def dev(torch, a):
-    """`a` on the device, 4 bytes off a 16-byte boundary (a copy: the shared arrays are read-only)."""
-    return at_offset(torch, np.array(a), 4)
 
 
 def two_pass(x_ct, scale):
@@ -112,13 +98,6 @@ def reference(C, T, N, variant=None):
     q = np.stack([two_pass(x[i].T, SCALES[s]) for i, s in enumerate(SETS)])
     rows = [ss.rows_of(sets[s], q[i], T) for i, s in enumerate(SETS)]
     return sets, q, rows
-
-
-def same_rows(got, expect, what=""):
-    got = np.asarray(got)
-    assert got.shape == expect.shape, (what, got.shape, expect.shape)
-    bad = np.flatnonzero((got != expect).any(axis=-1).reshape(-1))
-    assert bad.size == 0, f"{what}: {bad.size} of {expect[..., 0].size} rows differ, first {bad[:5]}"
 
 
 # ---- 1. windows and windows-at: y and every workspace byte --------------------------------------------

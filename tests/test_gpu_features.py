@@ -16,30 +16,14 @@ import support_streams as ss
 import support_streams_at as sa
 import support_streams_each as se
 from mibminet import lib
-from support import SCALE, at_offset, dequant, windows_at
+from support import GUARD, SCALE, at_offset, capped, dequant, same, windows_at  # noqa: F401 (capped: a fixture)
 
 pytestmark = pytest.mark.gpu
-GUARD, FILL, LEAD = 0x5A, 0x55, 64
+FILL, LEAD = 0x55, 64
 INV = lib.NET_ERR_INVALID
 E = sf.E
 # T64 = 1 (one 16-byte row per item), 7 (odd: byte stores), 17, 64 (every layer-4 part, 16-byte stores)
 GEOMETRIES = [(8, 64, 2), (19, 480, 3), (22, 1125, 4), (4, 4096, 16)]
-
-
-@pytest.fixture
-def capped(gpu):
-    """lib.grid_cap for the test; the cap is 0 again afterwards whatever happens."""
-    try:
-        yield lib.grid_cap
-    finally:
-        lib.grid_cap(0)
-
-
-def same(rows, expect, what=""):
-    assert rows.shape == expect.shape, (what, rows.shape, expect.shape)
-    r, e = rows.reshape(len(rows), -1), expect.reshape(len(expect), -1)
-    bad = np.flatnonzero((r != e).any(axis=1))
-    assert bad.size == 0, f"{what}: {bad.size} of {len(expect)} rows differ, first {bad[:5]}"
 
 
 class Out:

@@ -24,17 +24,9 @@ from mibminet import lib
 from mibminet.params import ParamSet, pack_trials
 from support import (_BAD, NTH, SCALE, at_offset, dequant, epochs_of, float_recording, run_entries_on, sliding_windows,
                      tile_sweep, want, windows_at)
+from support import capped  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture
-def capped(gpu):
-    """lib.grid_cap for the test; the cap is 0 again afterwards whatever happens."""
-    try:
-        yield lib.grid_cap
-    finally:
-        lib.grid_cap(0)
 
 
 @contextlib.contextmanager

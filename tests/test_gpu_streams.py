@@ -19,35 +19,10 @@ import support_streams as ss
 import support_windows_bank as swb
 from mibminet import lib
 from mibminet.params import ParamSet
-from support import want
+from support import CAPS, GUARD, capped, want  # noqa: F401 (capped: a fixture)
+from support_bank import banks  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
-CAPS = (1, 3, 0)  # one workgroup, three, and the normal grid
-GUARD = 0x5A
-
-
-@pytest.fixture
-def capped(gpu):
-    """lib.grid_cap for the test; the cap is 0 again afterwards whatever happens."""
-    try:
-        yield lib.grid_cap
-    finally:
-        lib.grid_cap(0)
-
-
-@pytest.fixture(scope="module")
-def banks(gpu):
-    """The five-set banks of the module, by geometry, built once and closed at the end."""
-    cache = {}
-
-    def get(C, T, N):
-        if (C, T, N) not in cache:
-            cache[(C, T, N)] = lib.Bank(sb.sets(C, T, N))
-        return cache[(C, T, N)]
-
-    yield get
-    for b in cache.values():
-        b.close()
 
 
 class Driver:

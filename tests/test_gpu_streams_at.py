@@ -17,36 +17,12 @@ import support_streams as ss
 import support_streams_at as sa
 import support_streams_each as se
 from mibminet import lib
+from support import CAPS, GUARD, capped, same  # noqa: F401 (capped: a fixture)
+from support_bank import banks  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
-CAPS = (1, 3, 0)  # one workgroup, three, and the normal grid
-GUARD = 0x5A
 LEAD = 64         # guard bytes on either side of the logits
 INV = lib.NET_ERR_INVALID
-
-
-@pytest.fixture
-def capped(gpu):
-    """lib.grid_cap for the test; the cap is 0 again afterwards whatever happens."""
-    try:
-        yield lib.grid_cap
-    finally:
-        lib.grid_cap(0)
-
-
-@pytest.fixture(scope="module")
-def banks(gpu):
-    """The five-set banks of the module, by geometry, built once and closed at the end."""
-    cache = {}
-
-    def get(C, T, N):
-        if (C, T, N) not in cache:
-            cache[(C, T, N)] = lib.Bank(sb.sets(C, T, N))
-        return cache[(C, T, N)]
-
-    yield get
-    for b in cache.values():
-        b.close()
 
 
 def query(st, items, expect=lib.NET_OK):
@@ -68,12 +44,6 @@ def query(st, items, expect=lib.NET_OK):
     assert (y[:LEAD] == GUARD).all() and (y[LEAD + W * N:] == GUARD).all(), "bytes outside the rows were written"
     assert nbl[0] == 0 == nbl[2]
     return y[LEAD: LEAD + W * N].reshape(W, N), nbl[1]
-
-
-def same(rows, expect, what=""):
-    assert rows.shape == expect.shape, (what, rows.shape, expect.shape)
-    bad = np.flatnonzero((rows != expect).any(axis=1))
-    assert bad.size == 0, f"{what}: {bad.size} of {len(expect)} rows differ, first {bad[:5]}"
 
 
 class Feed:

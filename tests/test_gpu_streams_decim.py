@@ -13,7 +13,7 @@ import support_decim as sd
 import support_streams as ss
 from mibminet import decimate, lib
 from mibminet.params import ParamSet
-from support import at_offset, want, windows_at
+from support import capped, dev, same_rows, want, windows_at  # noqa: F401 (capped: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -22,27 +22,6 @@ GEOMETRIES = sb.GEOMETRIES[:2]  # (8, 64, 2) and (19, 480, 3)
 QK = [(2, 7), (3, 33)]
 NAN, INF = float("nan"), float("inf")
 OK, INV, UNS = lib.NET_OK, lib.NET_ERR_INVALID, lib.NET_ERR_UNSUPPORTED
-
-
-@pytest.fixture
-def capped(gpu):
-    """lib.grid_cap for the test; the cap is 0 again afterwards whatever happens."""
-    try:
-        yield lib.grid_cap
-    finally:
-        lib.grid_cap(0)
-
-
-def dev(torch, a):
-    """`a` on the device, 4 bytes off a 16-byte boundary."""
-    return at_offset(torch, np.array(a), 4)
-
-
-def same_rows(got, expect, what=""):
-    got = np.asarray(got)
-    assert got.shape == expect.shape, (what, got.shape, expect.shape)
-    bad = np.flatnonzero((got != expect).any(axis=-1).reshape(-1))
-    assert bad.size == 0, f"{what}: {bad.size} of {expect[..., 0].size} rows differ, first {bad[:5]}"
 
 
 def run_raw(torch, st, x, ns, before=None):

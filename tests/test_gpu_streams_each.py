@@ -17,38 +17,13 @@ import support_streams_each as se
 import support_windows_bank as swb
 from mibminet import lib
 from mibminet.params import ParamSet
-from support import want
+from support import CAPS, GUARD, capped, same_each, want  # noqa: F401 (capped: a fixture)
+from support_bank import banks  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
-CAPS = (1, 3, 0)  # one workgroup, three, and the normal grid
-GUARD = 0x5A
 JUNK = 0x33       # what the unused part of a slot holds
 LEAD = 64         # guard bytes in front of the first tick's rows
 INT32_MIN, INT32_MAX = -2**31, 2**31 - 1
-
-
-@pytest.fixture
-def capped(gpu):
-    """lib.grid_cap for the test; the cap is 0 again afterwards whatever happens."""
-    try:
-        yield lib.grid_cap
-    finally:
-        lib.grid_cap(0)
-
-
-@pytest.fixture(scope="module")
-def banks(gpu):
-    """The five-set banks of the module, by geometry, built once and closed at the end."""
-    cache = {}
-
-    def get(C, T, N):
-        if (C, T, N) not in cache:
-            cache[(C, T, N)] = lib.Bank(sb.sets(C, T, N))
-        return cache[(C, T, N)]
-
-    yield get
-    for b in cache.values():
-        b.close()
 
 
 def _ceil4(v):
@@ -154,14 +129,6 @@ class Driver:
         return self.st.positions().cpu().tolist()
 
 
-def _same(rows, expect, what=""):
-    assert len(rows) == len(expect)
-    for i, (r, e) in enumerate(zip(rows, expect)):
-        assert r.shape == e.shape, (what, i, r.shape, e.shape)
-        bad = np.flatnonzero((r != e).any(axis=1))
-        assert bad.size == 0, f"{what} session {i}: {bad.size} of {len(e)} windows differ, first {bad[:5]}"
-
-
 # ---- 1. every row of every push -------------------------------------------------------------------
 @pytest.mark.parametrize("cap", CAPS)
 @pytest.mark.parametrize("layout", ["ct", "tc"])
@@ -180,7 +147,7 @@ def test_every_row_of_every_push(C, T, N, layout, cap, banks, capped):
         rows, nb = d.rows()
         assert nb == [0, 0, 0]
         assert d.positions() == w.fed.tolist() == d.pos and st.info()[4:] == [len(n_max), -1]
-        _same(rows, expect)
+        same_each(rows, expect)
     assert banks(C, T, N).device_copies() == 1
 
 
@@ -260,7 +227,7 @@ def test_float_input_with_the_sets_scales(C, T, N, capped):
                 d = Driver(torch, st, xd, n_max).run(n_max, counts)
                 rows, nb = d.rows()
                 assert nb == [0, 0, 0] and d.positions() == fed.tolist()
-                _same(rows, expect, f"cap {cap}")
+                same_each(rows, expect, f"cap {cap}")
         cnt = torch.full((ss.S,), 5, dtype=torch.int32, device="cuda")
         with lib.StreamsEach(bank, ss.SETS, ss.HOP, ss.MAX_PUSH) as st:  # the Python entry
             y, cout, nbad = st.push_f32(xd[:, :, :5].contiguous(), cnt)
@@ -303,7 +270,7 @@ def test_refused_counts_move_nothing(C, T, N, banks, capped):
             rows, nb = d.rows()
             assert nb == [0, len(bad), 0]
             assert d.positions() == fed.tolist()
-            _same(rows, expect, f"cap {cap}")
+            same_each(rows, expect, f"cap {cap}")
 
 
 # ---- 5. equal counts equal the uniform group ------------------------------------------------------
@@ -318,7 +285,7 @@ def test_equal_counts_give_the_uniform_groups_rows(C, T, N, banks, gpu):
         d = Driver(torch, st, ss.chunks(C, T), ns, "ct" if C % 2 else "tc").run(ns, [[n] * ss.S for n in ns])
         rows, nb = d.rows()
         assert nb == [0, 0, 0] and d.positions() == [ss.total(T)] * ss.S
-        _same(rows, list(ss.expected(ss.table(C, T, N))))
+        same_each(rows, list(ss.expected(ss.table(C, T, N))))
         assert [t[1] for t in d.ticks] == [se.each_rows(ss.HOP, n) for n in ns]
 
 
@@ -350,7 +317,7 @@ def test_hops(hop, banks, capped):
             d = Driver(torch, st, x, ns, "tc" if cap else "ct").run(ns, counts)
             rows, nb = d.rows()
             assert nb == [0, 0, 0] and d.positions() == fed.tolist()
-            _same(rows, expect, f"hop {hop}, cap {cap}")
+            same_each(rows, expect, f"hop {hop}, cap {cap}")
 
 
 # ---- 7. restart -----------------------------------------------------------------------------------
@@ -387,7 +354,7 @@ def test_restart(C, T, N, banks, capped):
             rows, nb = d.rows()
             assert nb == [0, 0, 0], cap
             assert d.positions() == [int(v) - (p if i == i0 else 0) for i, v in enumerate(w.fed)]
-            _same(rows, expect, f"cap {cap}")
+            same_each(rows, expect, f"cap {cap}")
             L = lib.load()
             for i, s in ((ss.S, 0), (2**40, 0), (0, -1), (0, 5), (0, 2**31 - 1)):
                 assert L.net_streams_restart(st.handle, i, s, None) == lib.NET_ERR_INVALID
@@ -460,7 +427,7 @@ def test_push_replayed_from_a_captured_graph(C, T, N, banks, gpu):
         del g
         assert nb.tolist() == [0, 0, 0] and st.positions().tolist() == w.fed.tolist() == cur
         assert st.info()[4] == 2 and uni.info()[4:] == [0, 0]  # enqueues, not replays
-        _same([np.concatenate(p) for p in got], expect)
+        same_each([np.concatenate(p) for p in got], expect)
 
 
 # ---- 9. the build variants ------------------------------------------------------------------------
@@ -487,7 +454,7 @@ def test_variants(C, T, N, variant, capped):
             d = Driver(torch, st, x, ns, layout).run(ns, counts)
             rows, nb = d.rows()
             assert nb == [0, 0, 0] and d.positions() == fed.tolist()
-            _same(rows, expect, f"{variant} {layout} cap {cap}")
+            same_each(rows, expect, f"{variant} {layout} cap {cap}")
 
 
 # ---- 10. isolation and refusals -------------------------------------------------------------------
@@ -520,7 +487,7 @@ def test_an_each_group_and_a_uniform_group_on_one_bank(banks, gpu):
                 pos += m
         rows_a, nb_a = da.rows()
         assert nb_a == [0, 0, 0]
-        _same(rows_a, se.expected(tab, w.fed, T))
+        same_each(rows_a, se.expected(tab, w.fed, T))
         np.testing.assert_array_equal(torch.cat(ys, dim=1).cpu().numpy(), ss.expected(tab))
         assert bank.device_copies() == 1
         # each kind of group refuses the other's push entry, and nothing moves
@@ -625,7 +592,7 @@ def test_refused_pushes_leave_the_group_as_it_was(banks, gpu):
         # the next valid pushes still give the right rows
         rows, nbad = d.run(n_max[half:], counts[half:]).rows()
         assert nbad == [0, 0, 0] and d.positions() == w.fed.tolist()
-        _same(rows, expect)
+        same_each(rows, expect)
 
 
 def test_python_push_returns_rows_counts_and_counter(banks, gpu):
@@ -654,7 +621,7 @@ def test_python_push_returns_rows_counts_and_counter(banks, gpu):
             assert cout.tolist() == w.k[t].tolist()
             for i in range(ss.S):
                 got[i].append(y[i, : int(cout[i])].cpu().numpy())
-        _same([np.concatenate(p) for p in got], expect)
+        same_each([np.concatenate(p) for p in got], expect)
         cnt = torch.tensor([1, 2, 0, 1, 0], dtype=torch.int32, device="cuda")
         y, cout, nbad = st.push(torch.zeros((ss.S, C, 1), dtype=torch.int8, device="cuda"), cnt)
         assert cout.tolist()[1] == -1 and int(nbad.item()) == 1

@@ -18,34 +18,10 @@ import support_windows_bank as swb
 from mibminet import lib
 from mibminet.params import ParamSet
 from oracle import golden_np as G
-from support import _BAD, at_offset, want, windows_at
+from support import _BAD, CAPS, at_offset, capped, want, windows_at  # noqa: F401 (capped: a fixture)
+from support_bank import banks  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
-CAPS = (1, 3, 0)  # one workgroup, three, and the normal grid
-
-
-@pytest.fixture
-def capped(gpu):
-    """lib.grid_cap for the test; the cap is 0 again afterwards whatever happens."""
-    try:
-        yield lib.grid_cap
-    finally:
-        lib.grid_cap(0)
-
-
-@pytest.fixture(scope="module")
-def banks(gpu):
-    """The five-set banks of the module, by geometry, built once and closed at the end."""
-    cache = {}
-
-    def get(C, T, N):
-        if (C, T, N) not in cache:
-            cache[(C, T, N)] = lib.Bank(sb.sets(C, T, N))
-        return cache[(C, T, N)]
-
-    yield get
-    for b in cache.values():
-        b.close()
 
 
 _WS = {}

@@ -15,6 +15,7 @@ The cases, at the sizes of tools/bench_bank.py, bench_windows_bank.py and bench_
   ep_bank_63x288, ep_bank_63x288_shuffled, ep_bank_105x84, each plain and _feat   (bank::k_forward_ep_bank[_feat])
   windows_bank_mmmi_64, windows_bank_bci_12     (bank::k_forward_y1_bank)
   push_bci_1024, push_bci_1024_shuffled         (stream::k_layer1_ring, k_forward_ring)
+  push_raw                                      (stream::k_layer1_ring_decim, k_history_update, k_forward_ring; q 2, K 41)
   each_equal, each_ragged                       (stream::k_layer1_ring_each, k_forward_ring_each)
   at_cues, at_feat                              (stream::k_forward_ring_at, k_forward_ring_at_feat)
 One JSON document goes to stdout and to <out.json>; the exit status is 1 if any output differs (a failed
@@ -37,14 +38,15 @@ sys.path[:0] = [os.path.join(ROOT, "mi-bminet_amd"), os.path.join(ROOT, "tools")
 import numpy as np
 import torch
 
-from mibminet import lib
+from mibminet import decimate, lib
 from mibminet.params import ParamSet
 
 HOP = 8
 KEYS = ("parent", "new", "parent_again")
 NAMES = ["net_bank_create", "net_bank_destroy", "net_model_compute_epochs_bank", "net_model_compute_epochs_bank_feat",
          "net_model_compute_windows_bank", "net_streams_create", "net_streams_create_each", "net_streams_destroy",
-         "net_streams_push", "net_streams_push_each", "net_streams_windows_at", "net_streams_windows_at_feat"]
+         "net_streams_push", "net_streams_push_each", "net_streams_windows_at", "net_streams_windows_at_feat",
+         "net_streams_set_decimator", "net_streams_push_raw_f32_tm"]
 
 
 def rotate(fns, reps, warmup, before=None):
@@ -90,15 +92,16 @@ class Libs:
                   "parent_again": lib.bind(ctypes.CDLL(again), NAMES)}
         self.st = torch.cuda.current_stream().cuda_stream
 
-    def banks(self, sets):
+    def banks(self, sets, scales=None):
         blobs = [ps.to_blob() for ps in sets]
         bufs = [ctypes.create_string_buffer(b, len(b)) for b in blobs]
         ptrs = (ctypes.c_void_p * len(blobs))(*[ctypes.addressof(b) for b in bufs])
         sizes = (ctypes.c_size_t * len(blobs))(*[len(b) for b in blobs])
+        sc = None if scales is None else (ctypes.c_float * len(blobs))(*scales)
         out = {}
         for k, L in self.L.items():
             h = ctypes.c_void_p()
-            assert L.net_bank_create(ptrs, sizes, None, len(blobs), ctypes.byref(h), None) == 0
+            assert L.net_bank_create(ptrs, sizes, sc, len(blobs), ctypes.byref(h), None) == 0
             out[k] = h.value
         return out
 
@@ -188,8 +191,8 @@ def windows_bank(X, R, lo, hi, C, T, N, variant, reps, seed=2026):
     return r
 
 
-def sessions(X, S, n_sets, C, T, N, variant, shuffled=False, seed=2026):
-    banks = X.banks(synthetic(n_sets, C, T, N, variant))
+def sessions(X, S, n_sets, C, T, N, variant, shuffled=False, seed=2026, scales=None):
+    banks = X.banks(synthetic(n_sets, C, T, N, variant), scales)
     set_of = np.sort(np.arange(S) * n_sets // S)
     if shuffled:
         set_of = np.random.default_rng(seed).permutation(set_of)
@@ -221,6 +224,39 @@ def push(X, S, n_sets, C, T, N, n, shuffled, variant, reps, seed=2026):
     r = verdict(rotate({k: (lambda k=k: call(k)) for k in KEYS}, reps, 20, before))
     torch.cuda.synchronize()
     r.update({"items": S * k_, "outputs_agree": bool(ok and same(ys))})
+    X.close(banks, grp)
+    return r
+
+
+def push_raw(X, S, n_sets, C, T, N, n, q, K, variant, reps, seed=2026):
+    """One tick of S sessions through a decimator: q n raw float32 frames each, [S][q n][C], filtered by K taps
+    in layer 1, then the n / hop windows per session (bench_streams.py's f32_tm_decim)."""
+    banks, set_of = sessions(X, S, n_sets, C, T, N, variant, scales=[1.0 + 0.25 * s for s in range(n_sets)])
+    grp = X.groups(banks, set_of, HOP, n)
+    taps = decimate.firwin_taps(q, K)
+    for k in KEYS:
+        assert X.L[k].net_streams_set_decimator(grp[k], q, taps.ctypes.data, K, X.st) == 0
+    k_ = n // HOP
+    lead = T % HOP
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    xa = torch.randn((S, q * n, C), dtype=torch.float32, device="cuda", generator=g)
+    ys = {k: torch.zeros((S, k_, N), dtype=torch.int8, device="cuda") for k in KEYS}
+    nbad = torch.zeros((1,), dtype=torch.int32, device="cuda")
+
+    def call(k, m=n):  # the first q m frames of xa: a tick of m decimated samples
+        rc = X.L[k].net_streams_push_raw_f32_tm(grp[k], xa.data_ptr(), q * m, ys[k].data_ptr(), nbad.data_ptr(), X.st)
+        assert rc == 0, rc
+    for m in [lead] * (lead > 0) + [n] * (-(-(T - lead) // n) + 2):  # to the grid, then until every push returns n / hop windows
+        for k in KEYS:
+            call(k, m)
+    torch.cuda.synchronize()
+    ok = same(ys) and bool(ys["new"].any()) and int(nbad.item()) == 0
+
+    def before(r):  # new frames every tick, the same for the three
+        xa.copy_(torch.randn((S, q * n, C), dtype=torch.float32, device="cuda", generator=g))
+    r = verdict(rotate({k: (lambda k=k: call(k)) for k in KEYS}, reps, 20, before))
+    torch.cuda.synchronize()
+    r.update({"items": S * k_, "q": q, "K": K, "outputs_agree": bool(ok and same(ys))})
     X.close(banks, grp)
     return r
 
@@ -307,12 +343,14 @@ CASES = {  # name(s): the run; a pair of names: (plain, _feat)
     ("windows_bank_bci_12",): lambda X, v, r: [windows_bank(X, 12, 89000, 101000, *BCI, v, r)],
     ("push_bci_1024",): lambda X, v, r: [push(X, 1024, 16, *BCI, 16, False, v, 10 * r)],
     ("push_bci_1024_shuffled",): lambda X, v, r: [push(X, 1024, 16, *BCI, 16, True, v, 10 * r)],
+    ("push_raw",): lambda X, v, r: [push_raw(X, 1024, 16, *BCI, 16, 2, 41, v, 10 * r)],
     ("each_equal",): lambda X, v, r: [push_each(X, 1024, 16, *BCI, 16, False, v, 10 * r)],
     ("each_ragged",): lambda X, v, r: [push_each(X, 1024, 16, *BCI, 32, True, v, 10 * r)],
     ("at_cues", "at_feat"): lambda X, v, r: windows_at(X, 1024, 16, *BCI, 16, v, r),
 }
 FAMILY = {"ep_bank": "bank::k_forward_ep_bank + _feat", "windows_bank": "bank::k_forward_y1_bank",
-          "push": "stream::k_layer1_ring + k_forward_ring", "each": "stream::k_layer1_ring_each + k_forward_ring_each",
+          "push": "stream::k_layer1_ring + k_forward_ring",
+          "push_raw": "stream::k_layer1_ring_decim + k_history_update + k_forward_ring", "each": "stream::k_layer1_ring_each + k_forward_ring_each",
           "at": "stream::k_forward_ring_at + _feat"}
 
 
