@@ -769,6 +769,63 @@ int net_streams_push_each_f32_tm(net_streams_t* st, const float* x, const int32_
  * no unanswered window.  A capturing stream is refused, as for a uniform group. */
 int net_streams_positions(net_streams_t* st, int64_t* pos_out, void* stream);
 
+/* ---- live streams: raw frames at each session's own pace, FIR-decimated ---------------------------
+ * An each-group may be given a decimator too (q, K taps h, as net_streams_set_decimator defines
+ * them; one q and one filter for the whole group).  Every session then has, beside pos[s], its own
+ * RAW position P[s] (int64, DEVICE memory: the raw frames it was given since creation or its last
+ * restart), its own phase off = q*D(P[s]) - P[s] and its own history of K-1 raw frames, and a raw
+ * push hands session s cnt_in[s] raw frames of its own.  All of it is planned on the device, so the
+ * raw push reads nothing from the host and IS CAPTURABLE as net_streams_push_each is.
+ * Per session the contract is the uniform raw push's: a push of cnt frames at P completes
+ * m = D(P+cnt) - D(P) decimated samples, D(P) = ceil(P/q); sample d is the sum stated above (each
+ * product and each sum rounded to float32 on its own, raw_s[a] = 0 for a < 0); the m floats are
+ * quantised under the session's set's scale, and from there on the push IS
+ * net_streams_push_each_f32_tm of m samples at position D(P[s]).  Over any sequence of pushes a
+ * session's rows are byte-identical to net_model_compute_windows_bank on the quantised decimation
+ * of the concatenation of its raw chunks.  pos[s] = D(P[s]) after every push, so
+ * net_streams_positions and net_streams_windows_at[_feat] stay on the session's DECIMATED axis: a
+ * cue at raw frame a of session s is the onset ceil(a/q).  m == 0 is legal and usual (one frame off
+ * the grid): only the history and P[s] move.
+ *
+ * _set_decimator_each: each-groups only; a NULL or a uniform group is NET_ERR_INVALID.  Then the
+ * checks of net_streams_set_decimator in its order: NET_ERR_INVALID for a group that has a decimator
+ * or has been pushed to, q outside 1 .. 16, K outside 1 .. 128, NULL taps, a tap that is not finite,
+ * a bank without scales; then NET_ERR_UNSUPPORTED for a capturing stream.  One allocation, zeroed,
+ * none afterwards: the taps, the histories [S][K-1][C] float32, the raw positions int64[S] and one
+ * 16-byte raw record per session.  The call waits for `stream`; a refused call leaves the group
+ * unchanged.  (net_streams_set_decimator on an each-group stays NET_ERR_UNSUPPORTED.)  An each-group
+ * with a decimator refuses net_streams_push_each[_f32[_tm]] with NET_ERR_INVALID, and one without
+ * refuses the raw push the same way.  On such a group net_streams_raw_info returns q, K, -1, -1: the
+ * positions are on the device.
+ * _each_raw_rows: host only; net_streams_each_rows(hop, ceil(n_raw_max/q)), the rows per session of
+ * y below.  0 for hop == 0, q outside 1 .. 16 or ceil(n_raw_max/q) outside 1 .. 65,536.
+ * _push_each_raw_f32_tm: x is DEVICE [S][n_raw_max][C] float32 in fixed slots, 4-byte aligned,
+ * 1 <= n_raw_max <= q*max_push; session s uses the first cnt_in[s] frames of its slot, 0 skips the
+ * tick.  The rest of a slot must be mapped and never influences a stored byte, NaN included: an
+ * answered sample d <= D(P+cnt) - 1 has q*d <= P + cnt - 1, so it reads no frame at or past cnt (the
+ * kernel's view of a slot ends with its cnt-th frame).  y, cnt_out, win0, n_bad, their alignments and
+ * their NULL rules are those of net_streams_push_each_f32_tm with
+ * kmax = net_streams_each_raw_rows(hop, q, n_raw_max).  A count is compared unsigned before anything
+ * is formed from it: one outside 0 .. n_raw_max, or one that would take P[s] past INT64_MAX - 2^20,
+ * stores nothing, moves neither position nor the history, sets cnt_out[s] = -1 and counts once in
+ * *n_bad.  Four kernels go on `stream`: the plan (one thread per session: both records, cnt_out,
+ * win0, *n_bad, P[s] and pos[s]), layer 1 with the FIR, for K > 1 the history update (also when no
+ * session completes a sample), the windows.  No host sync, no allocation: after one eager call the
+ * same enqueue may be captured and replayed, on the one stream the caller passes.  Checks, all before
+ * anything is enqueued: a NULL group, a uniform group or a group without a decimator,
+ * NET_ERR_INVALID; then NET_ERR_INVALID for n_raw_max outside 1 .. q*max_push, then the checks of
+ * net_streams_push_each_f32_tm in its order.  A HIP error of a launch is no refusal (see there).
+ * _raw_positions: a stream-ordered copy of the raw positions to raw_pos_out (DEVICE int64[S], 8-byte
+ * aligned).  NET_ERR_INVALID as net_streams_positions refuses, and for a group without a decimator.
+ * net_streams_restart on such a group sets pos[i] = 0, P[i] = 0 and the set and zeroes session i's
+ * history, in stream order: the session is a fresh one on its own axis.  A capturing stream is
+ * refused.  Not offered: a q or taps per session, IIR filters, rational resampling. */
+int net_streams_set_decimator_each(net_streams_t* st, size_t q, const float* taps, size_t K, void* stream);
+size_t net_streams_each_raw_rows(size_t hop, size_t q, size_t n_raw_max);
+int net_streams_push_each_raw_f32_tm(net_streams_t* st, const float* x, const int32_t* cnt_in, size_t n_raw_max,
+                                     int8_t* y, int32_t* cnt_out, int64_t* win0, int32_t* n_bad, void* stream);
+int net_streams_raw_positions(net_streams_t* st, int64_t* raw_pos_out, void* stream);
+
 /* ---- live streams: windows at given onsets, read from the rings ---------------------------------
  * The live counterpart of net_model_compute_windows_at, for cue-locked trials of a recording that is
  * still arriving ("Cue-locked trials").  One entry serves both kinds of group.

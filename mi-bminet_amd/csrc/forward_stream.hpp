@@ -37,7 +37,14 @@
 // frames, then the quantiser, so no decimated float array exists; k_history_update behind it moves
 // the chunk's last frames into the histories; layers 2-5 are k_forward_ring as it is.
 //
-// One body each: the three layer-1 kernels are layer1_ring, and the four kernels of layers 2-5 are
+// An each-group's decimator (net_streams_push_each_raw_f32_tm): every session has its own raw
+// position, phase and history slot in device memory.  k_stream_plan_raw turns raw count and raw
+// position into the session's EachRec and a second record, RawRec (plan_each_raw, stream_host.hpp),
+// and advances both positions; k_layer1_ring_each_decim is layer1_ring with EACH and DEC, off and
+// slot0 read per session from that record; k_history_update_each moves each session's last frames;
+// layers 2-5 are k_forward_ring_each as it is.  Four launches that read nothing from the host.
+//
+// One body each: the four layer-1 kernels are layer1_ring, and the four kernels of layers 2-5 are
 // bank::set_loop (forward_bank.hpp) over their sources RingRows, EachRows and AtRows, which say
 // where an item's rows are, whether it is valid and under which set.
 #pragma once
@@ -149,12 +156,18 @@ __device__ __forceinline__ v4i fir_fragment(const gen::View& vc, const gen::View
 // EACH: n and p0 are the session's own, read from its plan record (wave-uniform: one scalar load;
 // k_stream_plan validated the record, so n <= n_view = n_max and p0 < cap), and a wave skips the
 // blocks b >= ceil(n / 16); samples >= n are read inside the session's slot and not stored.
+// EACH and DEC (an each-group's raw push): x holds the S fixed slots of n_view raw frames, n is the
+// session's m, and off and slot0 are the session's own, read from its raw record (wave-uniform: one
+// more scalar load per item) into the item's copy of dc, so fir_taps16's r_lo and r_hi stay
+// wave-uniform: a wave's item is one session's block.  The chunk's view ends with the session's
+// n_raw-th frame: the rest of its slot is never read.
 template <int L, bool XR, bool CB, bool EACH, bool DEC = false>
 __device__ __forceinline__ void layer1_ring(const gen::GenParams* __restrict__ sets, int n_sets,
                                             const int* __restrict__ set_of, const Scale* __restrict__ scales,
                                             const int8_t* __restrict__ x, int8_t* __restrict__ ring,
                                             const EachRec* __restrict__ plan, int items, int nb, int n_view, int n,
-                                            int p0, int cap, const Decim& dc = Decim{}) {
+                                            int p0, int cap, const Decim& dc = Decim{},
+                                            const RawRec* __restrict__ raw = nullptr) {
   __shared__ v4i stg_v[win::NW1 * 64];  // channel-major transpose staging, 1 KB per wave
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -188,7 +201,15 @@ __device__ __forceinline__ void layer1_ring(const gen::GenParams* __restrict__ s
     }
     const gen::View v = gen::make_view(x + (size_t)s * chunk, chunk);
     int y[4];
-    if constexpr (DEC) {
+    if constexpr (DEC && EACH) {
+      const RawRec rr = raw[s];
+      Decim ds = dc;
+      ds.off = rr.off;
+      ds.slot0 = rr.slot0;
+      const gen::View vs = gen::make_view(x + (size_t)s * chunk, 4u * (unsigned)C * (unsigned)rr.n_raw);
+      const gen::View vh = gen::make_view(dc.hist + (size_t)s * dc.per, dc.per);
+      gen::l1_outputs<L, XR, CB>(fir_fragment(vs, vh, ds, b, C, lane, qs, qy), stg, k, lane, y);
+    } else if constexpr (DEC) {
       const gen::View vh = gen::make_view(dc.hist + (size_t)s * dc.per, dc.per);
       gen::l1_outputs<L, XR, CB>(fir_fragment(v, vh, dc, b, C, lane, qs, qy), stg, k, lane, y);
     } else {
@@ -284,6 +305,64 @@ __global__ __launch_bounds__(win::NT1) void k_layer1_ring_each(const gen::GenPar
                                                                const EachRec* __restrict__ plan, int items, int nb,
                                                                int n_max, int cap) {
   layer1_ring<L, XR, CB, true>(sets, n_sets, set_of, scales, x, ring, plan, items, nb, n_max, 0, 0, cap);
+}
+
+// Layer 1 of an each-group's raw push (net_streams_push_each_raw_f32_tm): items are (s, b) with
+// b < nb = ceil(ceil(n_raw_max / q) / 16), x the S fixed slots of n_raw_max float32 frames [n_raw_max][C].
+// Session s's m samples, ring position, phase and history slot come from its two records; dc's off
+// and slot0 are unused.  It reads the histories and writes none: k_history_update_each follows it.
+template <bool XR, bool CB>
+__global__ __launch_bounds__(win::NT1) void k_layer1_ring_each_decim(
+    const gen::GenParams* __restrict__ sets, int n_sets, const int* __restrict__ set_of, const Scale* __restrict__ scales,
+    const int8_t* __restrict__ x, int8_t* __restrict__ ring, const EachRec* __restrict__ plan,
+    const RawRec* __restrict__ raw, int items, int nb, int n_raw_max, int cap, Decim dc) {
+  layer1_ring<gen::F32TM, XR, CB, true, true>(sets, n_sets, set_of, scales, x, ring, plan, items, nb, n_raw_max, 0, 0, cap, dc,
+                                              raw);
+}
+
+// The history kernel of an each-group's raw push (K > 1), after layer 1 has read the old histories:
+// the last keep[s] = min(n_raw[s], K - 1) frames of session s's slot go to its history slots, frame
+// rel (n_raw - keep <= rel < n_raw) to slot (slot0[s] + rel) mod (K - 1).  Grid-stride over the
+// S keep_max C floats in 64 bits, keep_max = min(n_raw_max, K - 1); an index at or past its session's
+// keep is passed over, so a refused or skipped session (keep = 0) moves nothing.  It runs when no
+// session completed a sample too.
+__global__ void k_history_update_each(const float* __restrict__ x, float* __restrict__ hist,
+                                      const RawRec* __restrict__ raw, unsigned long long items, unsigned C,
+                                      unsigned n_raw_max, unsigned keep_max, unsigned K) {
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < items;
+       i += (unsigned long long)gridDim.x * blockDim.x) {
+    const unsigned c = (unsigned)(i % C);
+    const unsigned long long sf = i / C, s = sf / keep_max;
+    const unsigned j = (unsigned)(sf - s * keep_max);
+    const RawRec r = raw[s];
+    if (j >= (unsigned)r.keep) continue;
+    const unsigned rel = (unsigned)(r.n_raw - r.keep) + j;  // < n_raw <= n_raw_max
+    const unsigned slot = ((unsigned)r.slot0 + rel) % (K - 1);
+    hist[(s * (K - 1) + slot) * C + c] = x[(s * n_raw_max + rel) * C + c];
+  }
+}
+
+// The first kernel of an each-group's raw push: one thread per session.  It reads cnt_in[s] and the
+// raw position P[s], writes both of the session's records (plan_each_raw, stream_host.hpp: the count
+// is validated there, unsigned, before anything is formed from it), cnt_out[s] (the windows
+// completed, -1 for a refused count), win0[s] and *n_bad, and advances P[s] and pos[s] = D(P[s]).
+// The kernels after it read only the records, never cnt_in, P or pos.
+__global__ void k_stream_plan_raw(const int* __restrict__ cnt_in, long long* __restrict__ raw_pos,
+                                  long long* __restrict__ pos, EachRec* __restrict__ plan, RawRec* __restrict__ raw,
+                                  int* __restrict__ cnt_out, long long* __restrict__ win0, int* __restrict__ n_bad, int S,
+                                  int T, unsigned long long hop, int cap, int q, int K, int n_raw_max) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+  const long long P = raw_pos[s];
+  const EachRawPlan e = plan_each_raw((unsigned)T, hop, (unsigned)cap, (unsigned)q, (unsigned)K, P, cnt_in[s],
+                                      (unsigned)n_raw_max);
+  plan[s] = e.each.rec;
+  raw[s] = e.raw;
+  cnt_out[s] = e.each.ok ? e.each.rec.k : -1;
+  if (win0) win0[s] = e.each.W0;
+  if (!e.each.ok && n_bad) atomicAdd(n_bad, 1);
+  raw_pos[s] = P + e.raw.n_raw;
+  pos[s] = pos[s] + e.each.rec.n;
 }
 
 // The first kernel of an each-group's push: one thread per session.  It reads cnt_in[s] and pos[s],

@@ -57,8 +57,10 @@ using namespace mib;
 // them (at.plan and at.pos, stream::alloc_each; unused on a uniform group); its pos counts the
 // pushes enqueued.  A decimator (net_streams_set_decimator) adds q, K, the raw position and a
 // second allocation dmem (stream::alloc_decim: the taps, then every session's last K - 1 raw
-// frames); pos stays the decimated position.  A launching entry reaches all of this through
-// OpenGroup (section "live streams").
+// frames); pos stays the decimated position.  An each-group's decimator
+// (net_streams_set_decimator_each) lays dmem out by dea (stream::alloc_decim_each, whose base is
+// dat): behind the histories come the sessions' raw positions and raw records, and raw_pos stays 0.
+// A launching entry reaches all of this through OpenGroup (section "live streams").
 struct net_streams {
   const net_bank* bank = nullptr;
   int device = 0;
@@ -73,6 +75,7 @@ struct net_streams {
   uint64_t raw_pos = 0;
   void* dmem = nullptr;
   stream::AllocDecim dat{};
+  stream::AllocDecimEach dea{};
 };
 
 // test hook (mibminet_test_xdiv_gpu): xdiv against C division in 64 bits over e0 .. e0 + count - 1;
@@ -682,6 +685,8 @@ int streams_restart(net_streams* g, size_t i, int32_t set, void* stream) {
   if (g->q && g->K > 1)  // a decimator: the session's raw frames before the restart count as zeros
     if (const int rc = hip_err(hipMemsetAsync((char*)g->dmem + g->dat.hist + i * g->dat.per, 0, g->dat.per, o.st)))
       return rc;
+  if (g->q && g->each)  // an each-group's decimator: the session's raw position goes back to 0 too
+    if (const int rc = hip_err(hipMemsetAsync((char*)g->dmem + g->dea.raw_pos + 8 * i, 0, 8, o.st))) return rc;
   // an each-group: the session's position goes back to 0 (its origin stays -1: there is none)
   hipLaunchKernelGGL(stream::k_stream_restart, dim3(1), dim3(1), 0, o.st, g->each ? o.pos : o.origin, o.set_of, (int)i,
                      g->each ? 0ll : (long long)g->pos, (int)set);
@@ -694,13 +699,18 @@ int streams_restart(net_streams* g, size_t i, int32_t set, void* stream) {
 // net_streams_set_decimator: every check, the capturing stream's last, comes before the allocation;
 // the group changes only once the taps are on the device and the histories zero.  The stream is
 // waited for, so the caller's taps are free on return.
-int streams_set_decimator(net_streams* g, size_t q, const float* taps, size_t K, void* stream) {
-  if (const int rc = stream::check_set_decimator(g != nullptr, g && g->each, g && !g->bank->scales.empty(),
+// each: net_streams_set_decimator_each, the same on an each-group (whose pos counts its pushes); its
+// allocation holds the raw positions and raw records too, zeroed with the rest.
+int streams_set_decimator(net_streams* g, size_t q, const float* taps, size_t K, void* stream, bool each = false) {
+  if (each && (!g || !g->each)) return NET_ERR_INVALID;
+  if (const int rc = stream::check_set_decimator(g != nullptr, g && g->each && !each, g && !g->bank->scales.empty(),
                                                  g && g->q != 0, g && g->pos != 0, q, taps, K))
     return rc;
   const OpenGroup o(*g, stream, REFUSE_CAPTURE);
   if (o.rc) return o.rc;
-  const stream::AllocDecim a = stream::alloc_decim(g->S, (size_t)g->bank->sets[0].C, K);
+  const stream::AllocDecimEach ea = stream::alloc_decim_each(g->S, (size_t)g->bank->sets[0].C, K);
+  stream::AllocDecim a = ea.base;
+  if (each) a.bytes = ea.bytes;
   void* mem = nullptr;
   hipError_t e = hipMalloc(&mem, a.bytes);
   if (e != hipSuccess) return hip_err(e);
@@ -712,7 +722,8 @@ int streams_set_decimator(net_streams* g, size_t q, const float* taps, size_t K,
     return hip_err(e);
   }
   g->dmem = mem;
-  g->dat = a;
+  g->dat = ea.base;
+  g->dea = ea;
   g->q = q;
   g->K = K;
   return NET_OK;
@@ -767,7 +778,7 @@ int streams_push_raw(net_streams* g, const float* x, size_t n_raw, int8_t* y, in
 // the same on every call with the same arguments and may be captured; pos counts the enqueues.
 int streams_push_each(net_streams* g, const void* x, int arg_layout, bool f32, const int32_t* cnt_in, size_t n_max,
                       int8_t* y, int32_t* cnt_out, int64_t* win0, int32_t* n_bad, void* stream) {
-  if (!g || !g->each) return NET_ERR_INVALID;  // (an each-group has no decimator)
+  if (!g || !g->each || g->q) return NET_ERR_INVALID;  // (with a decimator: the raw push below)
   const net_bank& b = *g->bank;
   const gen::GenParams& hg = b.sets[0];
   stream::PushEach p;
@@ -790,6 +801,53 @@ int streams_push_each(net_streams* g, const void* x, int arg_layout, bool f32, c
       return launch_items(o.sc.ds, stream::k_forward_ring_each<RB, XR, CB>, windows_lds(hg), p.items, o.st, o.v.sets,
                           o.v.n_sets, o.ring, o.plan, o.set_of, y, (int)p.items, (int)p.kmax, p.hop, (int)g->cap);
     });
+  });
+  if (rc) return rc;
+  g->pos++;
+  return NET_OK;
+}
+
+// net_streams_push_each_raw_f32_tm: every check comes before the first launch.  Four launches that
+// read nothing from the host: the plan (k_stream_plan_raw: both records, both positions), layer 1
+// with the FIR from the session's slot and history, the history update (K > 1; also when no session
+// completes a sample), the windows (k_forward_ring_each as it is).  Capturable as
+// streams_push_each is, on the caller's one stream.
+int streams_push_each_raw(net_streams* g, const float* x, const int32_t* cnt_in, size_t n_raw_max, int8_t* y,
+                          int32_t* cnt_out, int64_t* win0, int32_t* n_bad, void* stream) {
+  if (!g || !g->each || !g->q) return NET_ERR_INVALID;
+  const net_bank& b = *g->bank;
+  const gen::GenParams& hg = b.sets[0];
+  stream::PushEachRaw r;
+  if (const int rc = stream::check_push_each_raw(g->S, (size_t)hg.C, g->hop, g->max_push, g->q, g->K, x, !b.scales.empty(),
+                                                 cnt_in, n_raw_max, y, cnt_out, win0, n_bad, r))
+    return rc;
+  const OpenGroup o(*g, stream, ALLOW_CAPTURE, true);
+  if (o.rc) return o.rc;
+  char* dmem = (char*)g->dmem;
+  auto* raw = (stream::RawRec*)(dmem + g->dea.rec);
+  const stream::PushEach& p = r.each;
+  hipLaunchKernelGGL(stream::k_stream_plan_raw, dim3((unsigned)((g->S + 255) / 256)), dim3(256), 0, o.st,
+                     (const int*)cnt_in, (long long*)(dmem + g->dea.raw_pos), o.pos, o.plan, raw, (int*)cnt_out,
+                     (long long*)win0, (int*)n_bad, (int)g->S, hg.T, (unsigned long long)g->hop, (int)g->cap, (int)g->q,
+                     (int)g->K, (int)n_raw_max);
+  if (const int rc = hip_err(hipGetLastError())) return rc;
+  const int rc = with_flags(hg, [&](auto rb, auto xr, auto cb) {
+    constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
+    const stream::Decim dc{(const float*)(dmem + g->dat.taps), (const int8_t*)(dmem + g->dat.hist), (int)g->K, (int)g->q, 0, 0,
+                           (unsigned)g->dat.per};
+    if (const int rc = launch_l1(o.sc.ds, stream::k_layer1_ring_each_decim<XR, CB>, l1_wgs(p.l1_items), o.st, o.v.sets,
+                                 o.v.n_sets, o.set_of, o.v.scales, (const int8_t*)x, o.ring, o.plan,
+                                 (const stream::RawRec*)raw, (int)p.l1_items, (int)p.blocks, (int)n_raw_max, (int)g->cap, dc))
+      return rc;
+    if (r.keep_max) {
+      const size_t blocks = std::min((r.hist_items + 255) / 256, (size_t)o.sc.ds.cus * 8);
+      hipLaunchKernelGGL(stream::k_history_update_each, dim3((unsigned)blocks), dim3(256), 0, o.st, x,
+                         (float*)(dmem + g->dat.hist), (const stream::RawRec*)raw, (unsigned long long)r.hist_items,
+                         (unsigned)hg.C, (unsigned)n_raw_max, (unsigned)r.keep_max, (unsigned)g->K);
+      if (const int rc = hip_err(hipGetLastError())) return rc;
+    }
+    return launch_items(o.sc.ds, stream::k_forward_ring_each<RB, XR, CB>, windows_lds(hg), p.items, o.st, o.v.sets,
+                        o.v.n_sets, o.ring, o.plan, o.set_of, y, (int)p.items, (int)p.kmax, p.hop, (int)g->cap);
   });
   if (rc) return rc;
   g->pos++;
@@ -837,6 +895,13 @@ int streams_positions(net_streams* g, int64_t* pos_out, void* stream) {
   const OpenGroup o(*g, stream, ALLOW_CAPTURE);
   if (o.rc) return o.rc;
   return hip_err(hipMemcpyAsync(pos_out, o.pos, 8 * g->S, hipMemcpyDeviceToDevice, o.st));
+}
+
+int streams_raw_positions(net_streams* g, int64_t* raw_pos_out, void* stream) {
+  if (!g || !g->each || !raw_pos_out || ((uintptr_t)raw_pos_out & 7) != 0 || !g->q) return NET_ERR_INVALID;
+  const OpenGroup o(*g, stream, ALLOW_CAPTURE);
+  if (o.rc) return o.rc;
+  return hip_err(hipMemcpyAsync(raw_pos_out, (char*)g->dmem + g->dea.raw_pos, 8 * g->S, hipMemcpyDeviceToDevice, o.st));
 }
 
 // Runs one reference-layout single-trial stage on the single-trial device.
@@ -1226,7 +1291,25 @@ int net_streams_push_raw_f32_tm(net_streams_t* st, const float* x, size_t n_raw,
 int net_streams_raw_info(const net_streams_t* st, int64_t* info) {
   if (!st || !info) return NET_ERR_INVALID;
   info[0] = (int64_t)st->q; info[1] = (int64_t)st->K; info[2] = (int64_t)st->raw_pos; info[3] = (int64_t)st->pos;
+  if (st->each && st->q) info[2] = info[3] = -1;  // the positions are on the device
   return NET_OK;
+}
+
+int net_streams_set_decimator_each(net_streams_t* st, size_t q, const float* taps, size_t K, void* stream) {
+  return streams_set_decimator(st, q, taps, K, stream, true);
+}
+
+size_t net_streams_each_raw_rows(size_t hop, size_t q, size_t n_raw_max) {
+  return stream::each_raw_rows(hop, q, n_raw_max);
+}
+
+int net_streams_push_each_raw_f32_tm(net_streams_t* st, const float* x, const int32_t* cnt_in, size_t n_raw_max, int8_t* y,
+                                     int32_t* cnt_out, int64_t* win0, int32_t* n_bad, void* stream) {
+  return streams_push_each_raw(st, x, cnt_in, n_raw_max, y, cnt_out, win0, n_bad, stream);
+}
+
+int net_streams_raw_positions(net_streams_t* st, int64_t* raw_pos_out, void* stream) {
+  return streams_raw_positions(st, raw_pos_out, stream);
 }
 
 int net_streams_create_each(const net_bank_t* bank, const int32_t* sets, size_t S, size_t hop, size_t max_push,

@@ -7,10 +7,12 @@
 // (net_streams_windows_at) which windows a ring still holds and where (at_item, shared with
 // k_forward_ring_at), the span and the checks; for a group with a decimator
 // (net_streams_set_decimator) the samples a raw push completes, the history's size and slots and
-// the checks and plan of a raw push.  HIP-free like entry_host.hpp, whose windows_count it uses:
-// included by mibminet.hip, forward_stream.hpp and four stand-alone host programs
+// the checks and plan of a raw push; for an each-group with a decimator
+// (net_streams_set_decimator_each) the per-session plan of a raw push (plan_each_raw, shared with its
+// plan kernel), its allocation and its checks.  HIP-free like entry_host.hpp, whose windows_count it
+// uses: included by mibminet.hip, forward_stream.hpp and five stand-alone host programs
 // (tests/stream_host_main.cpp, tests/stream_each_host_main.cpp, tests/stream_at_host_main.cpp,
-// tests/decim_host_main.cpp).
+// tests/decim_host_main.cpp, tests/decim_each_host_main.cpp).
 //
 // The ring.  A session's ring holds the layer-1 output of its last cap samples, sample t at position
 // t mod cap (and again at t mod cap + cap, forward_stream.hpp).  A push of n samples at position p0
@@ -369,6 +371,102 @@ inline int check_push_raw(size_t T, size_t S, size_t R, size_t hop, size_t max_p
   g.keep = n_raw < K - 1 ? n_raw : K - 1;
   g.hist_items = S * g.keep * R;  // S < 2^31, keep < 2^7, R <= 2^6
   g.push = p;
+  return NET_OK;
+}
+
+// ---- an each-group's decimator (net_streams_set_decimator_each) -----------------------------------
+// Every session has its own raw position P[s] (int64, device memory) beside its decimated position
+// pos[s] = D(P[s]), its own phase off = q D(P) - P and its own history slot: the plan of a raw push
+// is made per session on the device (k_stream_plan_raw, forward_stream.hpp) with plan_each_raw
+// below, which the host tests run too (tests/decim_each_host_main.cpp).
+
+// a raw position may not pass this: a count is at most q MAX_PUSH <= 2^20, so P + cnt and D(P) stay
+// int64 without a check on the host, and D(P) + m <= P + cnt stays below EACH_POS_LIMIT
+constexpr long long EACH_RAW_LIMIT = INT64_MAX - (1ll << 20);
+static_assert(MAX_Q * MAX_PUSH <= (1u << 20) && EACH_RAW_LIMIT <= EACH_POS_LIMIT, "the raw limit covers every count");
+
+// rows of y per session of a raw push of at most n_raw_max frames: each_rows(hop, ceil(n_raw_max / q));
+// 0 for hop == 0, q outside 1 .. MAX_Q or ceil(n_raw_max / q) outside 1 .. MAX_PUSH
+inline size_t each_raw_rows(size_t hop, size_t q, size_t n_raw_max) {
+  if (q < 1 || q > MAX_Q) return 0;
+  return each_rows(hop, n_raw_max / q + (n_raw_max % q != 0));
+}
+
+// The raw part of a session's record of one raw push (16 bytes, one scalar load), beside its EachRec:
+// the first n_raw frames of its slot are new, output sample j reads the frames q j + off - k of the
+// slot, the slot's first frame has history slot slot0, and the slot's last keep frames go to the
+// history.
+struct RawRec {
+  int n_raw, off, slot0, keep;
+};
+struct EachRawPlan {
+  EachPlan each;  // plan_each of the m decimated samples at D(P); ok: the raw count's verdict
+  RawRec raw;
+  int m;          // the decimated samples the count completes
+};
+
+// The plan of a session at raw position P (0 <= P <= EACH_RAW_LIMIT) that is handed cnt frames of a
+// raw push of at most n_raw_max (<= q max_push), under factor q in 1 .. MAX_Q and K in 1 .. MAX_TAPS
+// taps.  cnt is compared unsigned before anything is formed from it; a count outside 0 .. n_raw_max,
+// or one that would take P past EACH_RAW_LIMIT, is refused: n_raw = m = k = keep = 0, nothing is
+// stored and neither position moves.  m = D(P + cnt) - D(P) <= ceil(cnt / q) <= ceil(n_raw_max / q);
+// where m > 0, q (m - 1) + off = q (D(P + cnt) - 1) - P <= cnt - 1: no answered sample reads a frame
+// at or past cnt.
+MIB_HD inline EachRawPlan plan_each_raw(unsigned T, unsigned long long hop, unsigned cap, unsigned q, unsigned K,
+                                        long long P, int cnt, unsigned n_raw_max) {
+  EachRawPlan e;
+  const bool ok = (unsigned)cnt <= n_raw_max && P <= EACH_RAW_LIMIT - (long long)(unsigned)cnt;
+  const unsigned n = ok ? (unsigned)cnt : 0u;
+  const unsigned long long p = (unsigned long long)P, p1 = p + n;
+  const unsigned long long d0 = p / q + (p % q != 0), d1 = p1 / q + (p1 % q != 0);
+  e.m = (int)(d1 - d0);
+  e.raw.n_raw = (int)n;
+  e.raw.off = (int)(p % q == 0 ? 0 : q - p % q);
+  e.raw.slot0 = K > 1 ? (int)(p % (K - 1)) : 0;
+  e.raw.keep = (int)(n < K - 1 ? n : K - 1);
+  e.each = plan_each(T, hop, cap, (long long)d0, e.m, n_raw_max / q + (n_raw_max % q != 0));
+  e.each.ok = ok;  // (plan_each refuses nothing here: m is within its bound and D(P) + m within its limit)
+  return e;
+}
+
+// bytes of an each-group's decimator's one allocation: a uniform group's (the taps, then the
+// histories), then at multiples of 16 the raw positions int64[S] and the raw records RawRec[S]
+struct AllocDecimEach {
+  AllocDecim base;
+  size_t raw_pos, rec, bytes;
+};
+inline AllocDecimEach alloc_decim_each(size_t S, size_t R, size_t K) {
+  AllocDecimEach a;
+  a.base = alloc_decim(S, R, K);
+  a.raw_pos = (a.base.bytes + 15) / 16 * 16;
+  a.rec = (a.raw_pos + 8 * S + 15) / 16 * 16;
+  a.bytes = a.rec + sizeof(RawRec) * S;
+  return a;
+}
+
+// What one raw push of an each-group hands to the kernels.
+struct PushEachRaw {
+  size_t n_max;       // ceil(n_raw_max / q): the most decimated samples a session completes
+  size_t keep_max;    // min(n_raw_max, K - 1): the most frames a session moves to its history
+  size_t hist_items;  // S keep_max R: the floats the history kernel walks
+  PushEach each;      // check_push_each's plan of at most n_max samples per session
+};
+
+// The checks of net_streams_push_each_raw_f32_tm in their documented order (the group itself, NULL,
+// uniform or without a decimator, is the caller's first check): n_raw_max in 1 .. q max_push, then
+// those of net_streams_push_each_f32_tm, whose n_max = ceil(n_raw_max / q) is then in 1 .. max_push.
+inline int check_push_each_raw(size_t S, size_t R, size_t hop, size_t max_push, size_t q, size_t K, const void* x,
+                               bool have_scales, const void* cnt_in, size_t n_raw_max, const void* y,
+                               const void* cnt_out, const void* win0, const void* n_bad, PushEachRaw& g) {
+  if (n_raw_max < 1 || n_raw_max > q * max_push) return NET_ERR_INVALID;  // q max_push <= 2^20
+  const size_t n_max = n_raw_max / q + (n_raw_max % q != 0);
+  PushEach p{};
+  if (const int rc = check_push_each(S, hop, max_push, x, 0, true, have_scales, cnt_in, n_max, y, cnt_out, win0, n_bad, p))
+    return rc;
+  g.n_max = n_max;
+  g.keep_max = n_raw_max < K - 1 ? n_raw_max : K - 1;
+  g.hist_items = S * g.keep_max * R;  // S < 2^31, keep_max < 2^7, R <= 2^6
+  g.each = p;
   return NET_OK;
 }
 

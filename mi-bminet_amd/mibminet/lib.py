@@ -102,6 +102,10 @@ PROTOTYPES = {
     "net_streams_push_each_f32": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr, ptr, ptr)",
     "net_streams_push_each_f32_tm": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr, ptr, ptr)",
     "net_streams_positions": "int (ptr, ptr, ptr)",
+    "net_streams_set_decimator_each": "int (ptr, size_t, ptr, size_t, ptr)",
+    "net_streams_each_raw_rows": "size_t (size_t, size_t, size_t)",
+    "net_streams_push_each_raw_f32_tm": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr, ptr, ptr)",
+    "net_streams_raw_positions": "int (ptr, ptr, ptr)",
     "net_streams_windows_at": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr)",
     "net_streams_windows_at_feat": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr, ptr)",
     "net_streams_at_span": "int (ptr, ptr, ptr)",
@@ -1171,6 +1175,23 @@ class _StreamGroup(_Handle):
                 raise ValueError(f"{bad} of {W} windows are not in the rings (their logit rows are zero)")
         return (out, feat) if features else out
 
+    _set_decimator = None  # the subclass's entry
+
+    def decimate(self, q: int, taps, stream=None) -> None:
+        """``_set_decimator`` (net_streams_set_decimator or _each) with the taps as float32[K]."""
+        h = np.ascontiguousarray(taps, dtype=np.float32)
+        if h.ndim != 1:
+            raise ValueError("taps must be a 1-D array")
+        s = _stream_on(self.device, stream)
+        _check(getattr(load(), self._set_decimator)(self.handle, q, h.ctypes.data, h.size, s.cuda_stream),
+               self._set_decimator)
+
+    def raw_info(self) -> list:
+        """net_streams_raw_info: four int64 values."""
+        arr = (ctypes.c_int64 * 4)()
+        _check(load().net_streams_raw_info(self.handle, arr), "net_streams_raw_info")
+        return list(arr)
+
     def _push_source(self, x, layout: str, f32: bool) -> tuple:
         """Checks a push's ``x``, int8 or (``f32``) float32, [S][C][n] or [S][n][C] by ``layout``.  Returns
         the entry's suffix ("", "_f32" or "_f32_tm"), the layout code as the entry takes it (the
@@ -1193,7 +1214,7 @@ class Streams(_StreamGroup):
     be ordered with respect to one another (one stream, or events).  The bank must outlive the group;
     ``close()`` (or leaving the ``with`` block) synchronises the device and frees it."""
 
-    _create = "net_streams_create"
+    _create, _set_decimator = "net_streams_create", "net_streams_set_decimator"
 
     def info(self) -> list:
         """net_streams_info: [S, hop, max_push, cap, position, windows returned per session so far]."""
@@ -1240,18 +1261,11 @@ class Streams(_StreamGroup):
         float32 frames at ``q`` times the network's rate through ``push_raw`` and filters them with
         the FIR ``taps`` (K <= 128 finite float32 values, q <= 16; decimate.firwin_taps(q) is a
         default) inside the layer-1 kernel, bit for bit as decimate.fir_decimate states it."""
-        h = np.ascontiguousarray(taps, dtype=np.float32)
-        if h.ndim != 1:
-            raise ValueError("taps must be a 1-D array")
-        s = _stream_on(self.device, stream)
-        _check(load().net_streams_set_decimator(self.handle, q, h.ctypes.data, h.size, s.cuda_stream),
-               "net_streams_set_decimator")
+        super().decimate(q, taps, stream)
 
     def raw_info(self) -> list:
         """net_streams_raw_info: [q (0: no decimator), K, the raw position, the decimated position]."""
-        arr = (ctypes.c_int64 * 4)()
-        _check(load().net_streams_raw_info(self.handle, arr), "net_streams_raw_info")
-        return list(arr)
+        return super().raw_info()
 
     def push_raw(self, frames, stream=None, out=None):
         """net_streams_push_raw_f32_tm: ``frames`` is a CUDA/HIP float32 tensor [S][n_raw][C] at q times
@@ -1305,7 +1319,7 @@ class StreamsEach(_StreamGroup):
     position copies of a group ordered with respect to one another), the bank's lifetime and
     ``close()`` are Streams'."""
 
-    _create = "net_streams_create_each"
+    _create, _set_decimator = "net_streams_create_each", "net_streams_set_decimator_each"
 
     def info(self) -> list:
         """net_streams_info: [S, hop, max_push, cap, pushes enqueued so far, -1]."""
@@ -1319,22 +1333,44 @@ class StreamsEach(_StreamGroup):
         """net_streams_each_rows: kmax, the rows per session of a push of at most ``n_max`` samples."""
         return int(load().net_streams_each_rows(self.hop, n_max))
 
-    def positions(self, stream=None):
-        """net_streams_positions: the sessions' positions, an int64 device tensor [S] (no host sync)."""
+    def _positions(self, name: str, stream):
         torch = _torch()
         s = _stream_on(self.device, stream)
         with torch.cuda.stream(s):
             out = torch.empty((self.S,), dtype=torch.int64, device=f"cuda:{self.device}")
-        _check(load().net_streams_positions(self.handle, out.data_ptr(), s.cuda_stream), "net_streams_positions")
+        _check(getattr(load(), name)(self.handle, out.data_ptr(), s.cuda_stream), name)
         return out
 
-    def _push(self, x, dtype: str, code, n_max: int, counts, stream, out):
-        """``dtype``: the entry's suffix, "" (int8), "_f32" or "_f32_tm"."""
+    def positions(self, stream=None):
+        """net_streams_positions: the sessions' positions, an int64 device tensor [S] (no host sync).
+        On a group with a decimator they are the decimated ones, ceil(raw_positions() / q)."""
+        return self._positions("net_streams_positions", stream)
+
+    def raw_positions(self, stream=None):
+        """net_streams_raw_positions: the raw frames every session of a group with a decimator was
+        given since its creation or last restart, an int64 device tensor [S] (no host sync)."""
+        return self._positions("net_streams_raw_positions", stream)
+
+    def decimate(self, q: int, taps, stream=None) -> None:
+        """net_streams_set_decimator_each: once, before the first push.  From then on the group takes
+        raw float32 frames at ``q`` times the network's rate through ``push_raw``, every session at
+        its own pace and phase, filtered as Streams.decimate says; ``push`` and ``push_f32`` are
+        refused."""
+        super().decimate(q, taps, stream)
+
+    def raw_info(self) -> list:
+        """net_streams_raw_info: [q (0: no decimator), K, -1, -1] (the positions are on the device:
+        ``raw_positions()`` and ``positions()``); without a decimator [0, 0, 0, pushes enqueued]."""
+        return super().raw_info()
+
+    def _push(self, x, dtype: str, code, n_max: int, counts, stream, out, kmax: Optional[int] = None):
+        """``dtype``: the entry's suffix, "" (int8), "_f32", "_f32_tm" or "_raw_f32_tm"; ``kmax``: the rows
+        per session, where they are not ``rows(n_max)``."""
         torch = _torch()
         _check_tensor(counts, "counts", ("int32",), (self.S,))
         if counts.device != x.device:
             raise ValueError("counts must be on x's device")
-        kmax, N = self.rows(n_max), self.bank.dims.N
+        kmax, N = self.rows(n_max) if kmax is None else kmax, self.bank.dims.N
         s, _ = _launch(x, stream)
         with torch.cuda.stream(s):  # the counter's zeroing precedes the launch on its stream
             nbad = torch.zeros((1,), dtype=torch.int32, device=x.device)
@@ -1362,6 +1398,19 @@ class StreamsEach(_StreamGroup):
         [S][C][n_max] or "tc" = [S][n_max][C]; session i is quantised with the bank's scale of its
         set.  Returns what push returns."""
         return self._push(x, *self._push_source(x, layout, True), counts, stream, out)
+
+    def push_raw(self, frames, counts, stream=None, out=None):
+        """net_streams_push_each_raw_f32_tm: ``frames`` is a CUDA/HIP float32 tensor of fixed slots
+        [S][n_raw_max][C] at q times the network's rate, n_raw_max at most q max_push; ``counts`` an
+        int32 device tensor [S], the frames of each slot that are new (the rest of a slot is never
+        used).  Returns what push returns, with kmax = each_raw_rows(hop, q, n_raw_max): the windows
+        that end in the decimated samples each session's frames complete (often none)."""
+        if not self.bank.has_scales:
+            raise ValueError("a float32 source needs a bank created with scales")
+        _check_tensor(frames, "frames", ("float32",), (self.S, "n", self.bank.dims.C))
+        n_raw_max = int(frames.shape[1])
+        kmax = each_raw_rows(self.hop, self.raw_info()[0], n_raw_max)
+        return self._push(frames, "_raw_f32_tm", (), n_raw_max, counts, stream, out, kmax)
 
     def windows_at(self, sessions, onsets, stream=None, out=None, check: bool = True, features: bool = False):
         """net_streams_windows_at on an each-group: Streams.windows_at with every onset in its
@@ -1391,6 +1440,13 @@ def raw_samples(q: int, raw_pos: int, n_raw: int) -> int:
     ``raw_pos`` complete under factor ``q``, ceil((raw_pos + n_raw) / q) - ceil(raw_pos / q); 0 for
     q == 0 or when the sum passes 2^64 - 1."""
     return int(load().net_streams_raw_samples(q, raw_pos, n_raw))
+
+
+def each_raw_rows(hop: int, q: int, n_raw_max: int) -> int:
+    """net_streams_each_raw_rows: the rows per session of an each-group's raw push of at most
+    ``n_raw_max`` frames under factor ``q``, ceil(ceil(n_raw_max / q) / hop); 0 for hop == 0, q outside
+    1 .. 16 or ceil(n_raw_max / q) outside 1 .. 65,536."""
+    return int(load().net_streams_each_raw_rows(hop, q, n_raw_max))
 
 
 def fir_decimate_torch(x, hist, taps, q: int, raw_pos: int, stream=None):

@@ -65,6 +65,26 @@ grouped sets, hop 8, 16 decimated samples per tick, i.e. 16 q raw float32 frames
                   rows are compared for the record only.  The claim checked is new <= a on the medians, with no
                   margin; new / b is reported, not judged.
 
+Raw frames at each session's own pace (net_streams_push_each_raw_f32_tm), 1,024 sessions of 22 x 1125
+under 16 grouped sets, hop 8, with (q, K) = (2, 41) and (4, 81) from decimate.firwin_taps; the rings are
+filled with zero frames at equal counts, then six ticks of random frames are verified, then timed:
+  each_raw_equal  every count 16 q = n_raw_max.  (new) net_streams_push_each_raw_f32_tm against (u)
+                  net_streams_push_raw_f32_tm of a uniform group on the same frames (new / u is what
+                  the plan launch and the two records cost: set it beside each_equal's e / u from the
+                  same run) and against (b) net_streams_push_each_f32_tm on frames decimated beforehand.
+                  Verified first: every row of (new) equals (u)'s and (b)'s on decimate.fir_decimate's
+                  samples.  Report only.
+  each_raw_ragged counts drawn uniformly from 0 .. 32 q = n_raw_max.  (new) against (a) the caller's
+                  recipe, all timed: per-session kept tails of K - 1 frames, torch.cat, a stride-1
+                  depthwise conv1d over tail plus slot, a gather of each session's phase (and of its
+                  new tail), the positions' arithmetic on the device, then
+                  net_streams_push_each_f32_tm; and (b) as above.  Verified first: every completed
+                  row of (new) equals (b)'s on the CPU's samples, session by session; (a)'s float sums
+                  are the convolution library's and its rows are compared for the record only.  The
+                  claim checked is new <= a on the medians, with no margin.
+In both, (new) is also captured into a graph once and replayed, (g), in a round of its own beside
+the eager call, as each_equal does.
+
 Cue-locked trials of live sessions (net_streams_windows_at), 1,024 sessions of 22 x 1125 under 16
 grouped sets, hop 8, n 16:
   at_cues         Every tick is a push followed by one query per session, at an onset drawn uniformly
@@ -84,7 +104,7 @@ grouped sets, hop 8, n 16:
                   also stores 16 T64 bytes of layer-4 activations per window; the three rotate their
                   order from tick to tick.  Verified first: over six ticks (feat)'s logits equal (new)'s.
 
-  python tools/bench_streams.py [--cases mmmi_64,bci_1024,bci_1024_shuffled,each_equal,each_ragged,f32_tm,f32_tm_montage,f32_tm_decim,at_cues,at_feat]
+  python tools/bench_streams.py [--cases mmmi_64,bci_1024,bci_1024_shuffled,each_equal,each_ragged,f32_tm,f32_tm_montage,f32_tm_decim,each_raw_equal,each_raw_ragged,at_cues,at_feat]
                                 [--limit S] [--reps 1000] [--warmup 50] [--variant canonical|plain_bn]
                                 [--out-dir profiles]
 """
@@ -111,6 +131,10 @@ F32_CASES = {  # name: (sessions, sets, C, T, N, n, source rows R): net_streams_
 DECIM_CASES = {  # name: (sessions, sets, C, T, N, decimated samples per tick, ((q, K), ...)): net_streams_push_raw_f32_tm
     "f32_tm_decim": (1024, 16, 22, 1125, 4, 16, ((2, 41), (4, 81))),
 }
+EACH_RAW_CASES = {  # name: (sessions, sets, C, T, N, most decimated samples per tick, ragged, ((q, K), ...))
+    "each_raw_equal": (1024, 16, 22, 1125, 4, 16, False, ((2, 41), (4, 81))),
+    "each_raw_ragged": (1024, 16, 22, 1125, 4, 32, True, ((2, 41), (4, 81))),
+}
 
 AT_CASES = {  # name: (sessions, sets, C, T, N, n): net_streams_windows_at
     "at_cues": (1024, 16, 22, 1125, 4, 16),
@@ -131,6 +155,8 @@ def run_case(name, limit, reps, warmup, variant, seed=2026):
         return run_f32(name, limit, reps, warmup, variant, seed)
     if name in DECIM_CASES:
         return run_decim(name, limit, reps, warmup, variant, seed)
+    if name in EACH_RAW_CASES:
+        return run_each_raw(name, limit, reps, warmup, variant, seed)
     import numpy as np
     import torch
 
@@ -557,6 +583,169 @@ def run_decim(name, limit, reps, warmup, variant, seed=2026):
     return res
 
 
+def run_each_raw(name, limit, reps, warmup, variant, seed=2026):
+    import numpy as np
+    import torch
+
+    from mibminet import decimate, lib
+    from mibminet.params import ParamSet
+
+    S, n_sets, C, T, N, n, ragged, settings = EACH_RAW_CASES[name]
+    S = min(S, limit)
+    n_sets = min(n_sets, S)
+    sets = [ParamSet.synthetic(seed=seed + s, C=C, T=T, N=N, reorder_bn=variant != "plain_bn") for s in range(n_sets)]
+    scales = [1.0 + 0.25 * s for s in range(n_sets)]
+    bank = lib.Bank(sets, scales)
+    set_of = [int(v) for v in np.sort(np.arange(S) * n_sets // S)]
+    k = n // HOP
+    lead = T % HOP
+    fill = -(-(T - lead) // n)
+    A = lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    nbad = torch.zeros((1,), dtype=torch.int32, device="cuda")
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    rng = np.random.default_rng(seed)
+    configs, mis_all, rows_all = [], 0, 0
+    for q, K in settings:
+        taps = decimate.firwin_taps(q, K)
+        n_raw = q * n  # n_raw_max
+        groups = {key: lib.StreamsEach(bank, set_of, HOP, n) for key in ("new", "a", "b")}
+        groups["new"].decimate(q, taps)
+        uni = None if ragged else lib.Streams(bank, set_of, HOP, n)
+        if uni is not None:
+            uni.decimate(q, taps)
+        kmax = groups["b"].rows(n)
+        assert kmax == lib.each_raw_rows(HOP, q, n_raw)
+        xraw = torch.zeros((S, n_raw, C), dtype=torch.float32, device="cuda")  # the tick's slots as delivered
+        xdec = torch.zeros((S, n, C), dtype=torch.float32, device="cuda")      # (b)'s: decimated beforehand
+        cin = torch.full((S,), n_raw, dtype=torch.int32, device="cuda")        # raw counts
+        mb = torch.full((S,), n, dtype=torch.int32, device="cuda")             # (b)'s decimated counts
+        ma = torch.zeros((S,), dtype=torch.int32, device="cuda")               # (a)'s, computed in the recipe
+        tail = torch.zeros((S, K - 1, C), dtype=torch.float32, device="cuda")  # (a)'s kept frames per session
+        Pa = torch.zeros((S,), dtype=torch.int64, device="cuda")               # (a)'s raw positions
+        weight = torch.from_numpy(np.ascontiguousarray(taps[::-1])).cuda().view(1, 1, K).repeat(C, 1, 1)
+        jj = q * torch.arange(n, dtype=torch.int64, device="cuda").view(1, n)
+        kk = torch.arange(K - 1, dtype=torch.int64, device="cuda").view(1, K - 1)
+        y = {key: torch.zeros((S, kmax, N), dtype=torch.int8, device="cuda") for key in groups}
+        cout = {key: torch.zeros((S,), dtype=torch.int32, device="cuda") for key in groups}
+        yu = torch.zeros((S, k, N), dtype=torch.int8, device="cuda")
+
+        def new(st=stream):
+            rc = A.net_streams_push_each_raw_f32_tm(groups["new"].handle, xraw.data_ptr(), cin.data_ptr(), n_raw,
+                                                    y["new"].data_ptr(), cout["new"].data_ptr(), None, nbad.data_ptr(), st)
+            assert rc == 0, rc
+
+        def a():  # tails, cat, stride-1 depthwise conv1d, each session's phase gathered, the new tails, the push
+            with torch.no_grad():
+                cat = torch.cat((tail, xraw), dim=1)  # [S][K - 1 + n_raw][C]
+                full = torch.nn.functional.conv1d(cat.transpose(1, 2), weight, groups=C)  # [S][C][n_raw]: output j ends in frame j
+                cnt = cin.to(torch.int64)
+                off = (-Pa) % q
+                ma.copy_((Pa + cnt + (q - 1)) // q - (Pa + (q - 1)) // q)
+                idx = (off.view(S, 1) + jj).clamp_(max=n_raw - 1)
+                fr = full.gather(2, idx.view(S, 1, n).expand(S, C, n)).transpose(1, 2).contiguous()  # [S][n][C]
+                tail.copy_(cat.gather(1, (cnt.view(S, 1) + kk).view(S, K - 1, 1).expand(S, K - 1, C)))
+                Pa.add_(cnt)
+            rc = A.net_streams_push_each_f32_tm(groups["a"].handle, fr.data_ptr(), ma.data_ptr(), n, y["a"].data_ptr(),
+                                                cout["a"].data_ptr(), None, nbad.data_ptr(), stream)
+            assert rc == 0, rc
+
+        def b():
+            rc = A.net_streams_push_each_f32_tm(groups["b"].handle, xdec.data_ptr(), mb.data_ptr(), n, y["b"].data_ptr(),
+                                                cout["b"].data_ptr(), None, nbad.data_ptr(), stream)
+            assert rc == 0, rc
+
+        def u():
+            rc = A.net_streams_push_raw_f32_tm(uni.handle, xraw.data_ptr(), n_raw, yu.data_ptr(), nbad.data_ptr(), stream)
+            assert rc == 0, rc
+
+        # zero frames at equal counts until the first window is one tick away
+        for m in [lead] * (lead > 0) + [n] * fill:
+            cin.fill_(q * m)
+            mb.fill_(m)
+            new()
+            a()
+            b()
+            if uni is not None:
+                uni.push_raw(xraw[:, : q * m].contiguous())
+        torch.cuda.synchronize()
+        P = np.full(S, q * (lead + fill * n), np.int64)
+        assert groups["new"].raw_positions().tolist() == P.tolist() == Pa.tolist()
+        assert groups["new"].positions().tolist() == groups["b"].positions().tolist() == [lead + fill * n] * S
+        state = [np.zeros((K - 1, C), np.float32) for _ in range(S)]
+        mis = mis_a = rows = 0
+        for _ in range(VERIFY):
+            cnt = rng.integers(0, n_raw + 1, size=S).astype(np.int32) if ragged else np.full(S, n_raw, np.int32)
+            xraw.copy_(torch.randn((S, n_raw, C), dtype=torch.float32, device="cuda", generator=g))
+            xh = xraw.cpu().numpy()
+            dec, mh = np.zeros((S, n, C), np.float32), np.zeros(S, np.int32)
+            for s in range(S):
+                d, state[s] = decimate.fir_decimate(np.ascontiguousarray(xh[s, : cnt[s]]), taps, q, state[s], int(P[s]))
+                dec[s, : len(d)], mh[s] = d, len(d)
+            P += cnt
+            xdec.copy_(torch.from_numpy(dec))
+            mb.copy_(torch.from_numpy(mh))
+            cin.copy_(torch.from_numpy(cnt))
+            new()
+            a()
+            b()
+            if uni is not None:
+                u()
+            torch.cuda.synchronize()
+            kc = cout["new"].cpu().numpy()
+            assert (kc == cout["b"].cpu().numpy()).all() and (kc == cout["a"].cpu().numpy()).all() and ma.cpu().tolist() == mh.tolist()
+            live = torch.arange(kmax, device="cuda").view(1, kmax) < cout["new"].view(S, 1)
+            mis += int(((y["new"] != y["b"]).any(dim=2) & live).sum().item())
+            mis_a += int(((y["new"] != y["a"]).any(dim=2) & live).sum().item())
+            if uni is not None:
+                assert (kc == k).all()
+                mis += int((y["new"][:, :k] != yu).any(dim=2).sum().item())
+            rows += int(kc.sum())
+        assert int(nbad.item()) == 0 and groups["new"].raw_positions().tolist() == P.tolist()
+        # (g): the same enqueue captured once on one stream; two rounds, as run_each times them
+        graph = torch.cuda.CUDAGraph()
+        side = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(graph, stream=side):
+                new(side.cuda_stream)
+        fns = {"new": new, "a": a, "b": b} if ragged else {"new": new, "u": u, "b": b}
+        ms = time_alternating(fns, reps, warmup)
+        ms.update(time_alternating({"new2": new, "g": graph.replay}, reps, warmup))
+        med = medians(ms)
+        assert int(nbad.item()) == 0
+        c = {"q": q, "K": K, "n_raw_max": n_raw, "mean_count": round(float(cnt.mean()), 2), "rows_verified": rows,
+             "mismatched_rows": mis, "rows_of_recipe_that_differ": mis_a,
+             "ms_push_each_raw": round(med["new"], 4), "ms_push_each_raw_min_max": min_max(ms["new"]),
+             "ms_push_each_f32_tm_decimated_beforehand": round(med["b"], 4), "new_over_b": round(med["new"] / med["b"], 4),
+             "ms_push_each_raw_beside_graph": round(med["new2"], 4), "ms_push_each_raw_graph": round(med["g"], 4),
+             "graph_over_eager": round(med["g"] / med["new2"], 4)}
+        if ragged:
+            c.update({"ms_tails_cat_conv1d_gather_push_each_f32_tm": round(med["a"], 4),
+                      "ms_tails_cat_conv1d_gather_push_each_f32_tm_min_max": min_max(ms["a"]),
+                      "new_over_a": round(med["new"] / med["a"], 4), "new <= a": med["new"] <= med["a"]})
+        else:
+            c.update({"ms_push_raw_f32_tm_uniform": round(med["u"], 4), "ms_push_raw_f32_tm_uniform_min_max": min_max(ms["u"]),
+                      "new_over_u": round(med["new"] / med["u"], 4)})
+        configs.append(c)
+        mis_all += mis
+        rows_all += rows
+        del graph
+        for st in groups.values():
+            st.close()
+        if uni is not None:
+            uni.close()
+    info = bank.info()
+    res = {"name": name, "sessions": S, "sets": n_sets, "C": C, "T": T, "N": N, "hop": HOP,
+           "counts": "uniform 0 .. n_raw_max" if ragged else "all n_raw_max", "rows_per_session": kmax, "variant": variant,
+           "exact_division": bool(info[4]), "verified_ticks": VERIFY, "rows_verified": rows_all, "mismatched_rows": mis_all,
+           "reps": reps, "warmup": warmup, "device": torch.cuda.get_device_name(0), "configs": configs,
+           "gates": {f"new <= a (q {c['q']}, K {c['K']})": c["new <= a"] for c in configs} if ragged else "none: report only",
+           "pass": mis_all == 0 and rows_all > 0}
+    bank.close()
+    return res
+
+
 def run_at(name, limit, reps, warmup, variant, seed=2026):
     import numpy as np
     import torch
@@ -760,4 +949,4 @@ def b_call(A, bank, recipe, nbad, stream):
 
 
 if __name__ == "__main__":
-    main(__doc__, {**CASES, **EACH_CASES, **F32_CASES, **DECIM_CASES, **AT_CASES, **AT_FEAT_CASES}, run_case, "limit", "streams", lambda res: res["mismatched_rows"], reps=1000, warmup=50)
+    main(__doc__, {**CASES, **EACH_CASES, **F32_CASES, **DECIM_CASES, **EACH_RAW_CASES, **AT_CASES, **AT_FEAT_CASES}, run_case, "limit", "streams", lambda res: res["mismatched_rows"], reps=1000, warmup=50)
