@@ -819,12 +819,65 @@ int net_streams_positions(net_streams_t* st, int64_t* pos_out, void* stream);
  * aligned).  NET_ERR_INVALID as net_streams_positions refuses, and for a group without a decimator.
  * net_streams_restart on such a group sets pos[i] = 0, P[i] = 0 and the set and zeroes session i's
  * history, in stream order: the session is a fresh one on its own axis.  A capturing stream is
- * refused.  Not offered: a q or taps per session, IIR filters, rational resampling. */
+ * refused.  Not offered: a q or taps per session, rational resampling. */
 int net_streams_set_decimator_each(net_streams_t* st, size_t q, const float* taps, size_t K, void* stream);
 size_t net_streams_each_raw_rows(size_t hop, size_t q, size_t n_raw_max);
 int net_streams_push_each_raw_f32_tm(net_streams_t* st, const float* x, const int32_t* cnt_in, size_t n_raw_max,
                                      int8_t* y, int32_t* cnt_out, int64_t* win0, int32_t* n_bad, void* stream);
 int net_streams_raw_positions(net_streams_t* st, int64_t* raw_pos_out, void* stream);
+
+/* ---- live streams: an IIR prefilter (biquad cascade) ahead of the FIR decimator ---------------------
+ * A group that has a decimator, uniform or each, and has not been pushed to may be given a prefilter:
+ * M second-order sections, 1 <= M <= 8, sos[M][5] = {b0, b1, b2, a1, a2} float32, section j being
+ * H(z) = (b0 + b1 z^-1 + b2 z^-2) / (1 + a1 z^-1 + a2 z^-2) with a0 = 1, scipy's sign convention.
+ * Every raw frame then passes the cascade, per session and electrode, with state the group owns,
+ * before the decimator sees it: a DC offset, electrode drift and mains hum need a low-order IIR
+ * (a Butterworth high-pass and a notch), which no FIR of K <= 128 taps at the raw rate replaces.  For
+ * IIR at the network's own rate use q = 1, K = 1, h = {1.0f}.
+ * Arithmetic, bit for bit.  Per session s and electrode r, per raw frame in arrival order, sections
+ * j = 0 .. M-1 ascending, transposed direct form II; with v the section's input (the raw sample for
+ * j = 0, the previous section's w otherwise):
+ *     w   = RN(RN(b0*v) + z1)
+ *     z1' = RN(RN(RN(b1*v) - RN(a1*w)) + z2)
+ *     z2' = RN(RN(b2*v) - RN(a2*w))
+ * with every product and every sum or difference rounded to float32 on its own; nothing is contracted
+ * into an fma.  All states start at +0.0f.  In exact arithmetic this is scipy.signal.sosfilt; it
+ * does not depend on how the frames are split into pushes.  SUBNORMAL intermediates follow the
+ * device's float mode and are outside the contract, as for the FIR.  From there on the push IS the
+ * raw push of the filtered frames: the FIR, the histories (which then hold filtered frames), the
+ * quantiser, the rings, the rows, n_bad and the positions are as net_streams_push_raw_f32_tm and
+ * net_streams_push_each_raw_f32_tm define them.
+ * Electrodes are independent.  A NaN or an infinity on an electrode enters that electrode's state
+ * alone and stays there until the session restarts.  An unselected electrode of a widened set may
+ * therefore still carry anything: its filtered value is quantised to a finite int8 and meets a zero
+ * weight.  ON A SELECTED ELECTRODE A NON-FINITE SAMPLE NOW POISONS THE SESSION UNTIL ITS RESTART (the
+ * FIR alone forgets it after K frames).  Stability of the filter is the caller's business and is not
+ * checked.
+ * _set_prefilter: one entry for both kinds of group.  sos: HOST float32[M][5].  One allocation, none
+ * afterwards: the states [S][M][2][C] float32, zeroed, a session's contiguous, and the scratch
+ * [S][q*max_push][C] float32 that holds the filtered frames of one push (5.8 MB for 1,024 sessions of
+ * 22 electrodes at q = 4 and max_push = 16).  The coefficients travel in the kernel's arguments, so
+ * they survive in a captured graph.  The call waits for `stream`.  Checks, in this order, all before
+ * the allocation: a NULL group, NET_ERR_INVALID; then NET_ERR_INVALID for a group without a
+ * decimator, a group that has a prefilter or has been pushed to, M outside 1 .. 8, NULL sos, a
+ * coefficient that is not finite; then NET_ERR_UNSUPPORTED for a capturing stream.  A refused call
+ * leaves the group unchanged.
+ * A raw push of such a group enqueues one kernel more, ahead of layer 1 (an each-group: after the
+ * plan, its trip counts from the plan's records, so a refused count moves no state, the rest of a
+ * slot is never read, and the five launches stay capturable after one eager call); no host read is
+ * added.  Without a prefilter a raw push enqueues exactly what it did.  Every CHECK of a raw push
+ * still comes before anything is enqueued.  A HIP error of a launch (NET_ERR_HIP and below) is no
+ * refusal, here as for an each-group's push: the prefilter goes out first, so if a later launch of
+ * the same push fails, the states have moved past frames whose layer 1 never ran, on a uniform group
+ * although its positions have not moved.  Treat such a group as lost: destroy it, or restart every
+ * session.
+ * net_streams_restart on such a group additionally zeroes session i's states in stream order: the
+ * session is one whose earlier frames were all zero (zero state is the steady state of zero input).
+ * _prefilter_info: info[0..2] = M (0: none), the scratch's frames per session, the bytes allocated.
+ * NET_ERR_INVALID for a NULL group or info.
+ * Not offered: coefficients per session or electrode, zero-phase filtering. */
+int net_streams_set_prefilter(net_streams_t* st, const float* sos, size_t M, void* stream);
+int net_streams_prefilter_info(const net_streams_t* st, int64_t* info);
 
 /* ---- live streams: windows at given onsets, read from the rings ---------------------------------
  * The live counterpart of net_model_compute_windows_at, for cue-locked trials of a recording that is

@@ -120,6 +120,16 @@ int mibminet_test_streams_ring(const net_streams_t* st, size_t i, void* out);
 int mibminet_test_fir_decimate(const float* x, size_t n_raw, size_t R, const float* hist, const float* taps, size_t K,
                                size_t q, size_t raw_pos, float* out, int device, void* stream);
 
+/* The prefilter of net_streams_set_prefilter before the FIR and the quantiser: the kernel a raw push
+ * runs, on one session.  x: DEVICE [n][R] float32, the chunk in arrival order; sos: HOST float32[M][5]
+ * = {b0, b1, b2, a1, a2}; state_in: DEVICE [M][2][R] float32 (z1 then z2 of a section), the state
+ * before the chunk; out: DEVICE [n][R] float32, the filtered floats as they are; state_out: DEVICE
+ * [M][2][R], the state after it (it may be state_in).  Enqueued on `stream`.  A one-ulp error would
+ * hide behind the FIR and the int8 rounding without it.  n == 0 copies the state.  NET_ERR_INVALID
+ * for R outside 1 .. 64, M outside 1 .. 8, n > 16 * 65,536, a NULL pointer that is needed. */
+int mibminet_test_sos_filter(const float* x, size_t n, size_t R, const float* sos, size_t M, const float* state_in,
+                             float* out, float* state_out, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

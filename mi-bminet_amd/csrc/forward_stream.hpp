@@ -44,6 +44,11 @@
 // slot0 read per session from that record; k_history_update_each moves each session's last frames;
 // layers 2-5 are k_forward_ring_each as it is.  Four launches that read nothing from the host.
 //
+// A prefilter (net_streams_set_prefilter): M second-order sections that every raw frame passes, per
+// session and electrode, before the FIR.  k_prefilter runs ahead of layer 1 (an each-group: after the
+// plan, its trip counts from the raw records) and writes the filtered frames to a scratch of the
+// group's; the layer-1 and history kernels above then take the scratch where they took x.
+//
 // One body each: the four layer-1 kernels are layer1_ring, and the four kernels of layers 2-5 are
 // bank::set_loop (forward_bank.hpp) over their sources RingRows, EachRows and AtRows, which say
 // where an item's rows are, whether it is valid and under which set.
@@ -339,6 +344,90 @@ __global__ void k_history_update_each(const float* __restrict__ x, float* __rest
     const unsigned rel = (unsigned)(r.n_raw - r.keep) + j;  // < n_raw <= n_raw_max
     const unsigned slot = ((unsigned)r.slot0 + rel) % (K - 1);
     hist[(s * (K - 1) + slot) * C + c] = x[(s * n_raw_max + rel) * C + c];
+  }
+}
+
+// ---- a prefilter: an IIR cascade ahead of the decimator (net_streams_set_prefilter) ----------------
+// One raw sample v of one electrode through the M sections, ascending, transposed direct form II
+// with z[j] = {z1, z2} of section j:
+//   w = RN(RN(b0 v) + z1);  z1' = RN(RN(RN(b1 v) - RN(a1 w)) + z2);  z2' = RN(RN(b2 v) - RN(a2 w))
+// and w the next section's v.  Every product and every sum or difference is a float32 operation of
+// its own (contraction is off in this function).  The coefficients are kernel arguments, indexed by
+// constants: scalar registers.
+template <int M>
+__device__ __forceinline__ float sos_sample(const Sos& c, float (&z)[M][2], float v) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < M; j++) {
+    const float p0 = c.c[j][0] * v;
+    const float w = p0 + z[j][0];
+    const float p1 = c.c[j][1] * v, q1 = c.c[j][3] * w;
+    const float d1 = p1 - q1;
+    const float p2 = c.c[j][2] * v, q2 = c.c[j][4] * w;
+    z[j][0] = d1 + z[j][1];
+    z[j][1] = p2 - q2;
+    v = w;
+  }
+  return v;
+}
+
+constexpr int PF_AHEAD = 8;  // frames whose loads are issued ahead of the recurrence
+
+// One lane's electrode over its session's n frames, in arrival order.  x and y point at the lane's
+// float of the session's first frame (frames R floats apart), st at its float of the session's state
+// [M][2][R].  The 2 M states stay in registers from the first frame to the last.  The loads of the
+// next PF_AHEAD frames are issued before the current ones go through the recurrence: they do not
+// depend on it, and a wave has few neighbours on its SIMD here to hide them behind.  A frame at or
+// past n is neither read nor written.
+template <int M>
+__device__ __forceinline__ void sos_lane(const float* __restrict__ x, float* __restrict__ y, float* __restrict__ st,
+                                         size_t R, int n, const Sos& c) {
+  float z[M][2];
+#pragma unroll
+  for (int j = 0; j < M; j++) {
+    z[j][0] = st[(size_t)(2 * j) * R];
+    z[j][1] = st[(size_t)(2 * j + 1) * R];
+  }
+  float cur[PF_AHEAD], nxt[PF_AHEAD];
+#pragma unroll
+  for (int u = 0; u < PF_AHEAD; u++) cur[u] = u < n ? x[(size_t)u * R] : 0.0f;
+  for (int t = 0; t < n; t += PF_AHEAD) {
+#pragma unroll
+    for (int u = 0; u < PF_AHEAD; u++) nxt[u] = t + PF_AHEAD + u < n ? x[(size_t)(t + PF_AHEAD + u) * R] : 0.0f;
+#pragma unroll
+    for (int u = 0; u < PF_AHEAD; u++)
+      if (t + u < n) y[(size_t)(t + u) * R] = sos_sample<M>(c, z, cur[u]);
+#pragma unroll
+    for (int u = 0; u < PF_AHEAD; u++) cur[u] = nxt[u];
+  }
+#pragma unroll
+  for (int j = 0; j < M; j++) {
+    st[(size_t)(2 * j) * R] = z[j][0];
+    st[(size_t)(2 * j + 1) * R] = z[j][1];
+  }
+}
+
+// The prefilter of a raw push, ahead of layer 1: one lane per (session, electrode), flat index
+// i = s R + r over lanes = S R (64 bits; grid-stride), so the lanes of a session read the 4 R
+// contiguous bytes of a frame.  x: the S chunks (EACH: fixed slots) of n_view raw frames [n_view][R];
+// y: the scratch, the same frames filtered at the same stride; state: [S][M][2][R].  A session's
+// trip count is n_view, or (EACH) its RawRec.n_raw, which k_stream_plan_raw validated (compared with
+// n_view all the same): a refused or skipped session (n_raw = 0) moves no state, and the rest of a
+// slot is never read.  Offsets are formed in 64 bits: S n_view R 4 can pass 2^32.  No LDS, no
+// scratch memory.  The recurrence is serial in time by contract: the parallelism is the S R lanes.
+// It is also the kernel of the test hook (mibminet_test_sos_filter), with S = 1.
+template <bool EACH, int M>
+__global__ __launch_bounds__(64) void k_prefilter(const float* __restrict__ x, float* __restrict__ y,
+                                                  float* __restrict__ state, const RawRec* __restrict__ raw,
+                                                  unsigned long long lanes, unsigned R, unsigned n_view, Sos c) {
+  for (unsigned long long i = (unsigned long long)blockIdx.x * 64u + threadIdx.x; i < lanes;
+       i += (unsigned long long)gridDim.x * 64u) {
+    const unsigned long long s = i / R;
+    const unsigned r = (unsigned)(i - s * R);
+    unsigned n = n_view;
+    if constexpr (EACH) n = min((unsigned)raw[s].n_raw, n_view);
+    const size_t at = (size_t)s * n_view * R + r;
+    sos_lane<M>(x + at, y + at, state + (size_t)s * (2 * M) * R + r, R, (int)n, c);
   }
 }
 

@@ -60,6 +60,8 @@ using namespace mib;
 // frames); pos stays the decimated position.  An each-group's decimator
 // (net_streams_set_decimator_each) lays dmem out by dea (stream::alloc_decim_each, whose base is
 // dat): behind the histories come the sessions' raw positions and raw records, and raw_pos stays 0.
+// A prefilter (net_streams_set_prefilter) adds M, the sections and a third allocation pmem
+// (stream::alloc_prefilter: the states, then the scratch of one push's filtered frames).
 // A launching entry reaches all of this through OpenGroup (section "live streams").
 struct net_streams {
   const net_bank* bank = nullptr;
@@ -76,6 +78,10 @@ struct net_streams {
   void* dmem = nullptr;
   stream::AllocDecim dat{};
   stream::AllocDecimEach dea{};
+  size_t M = 0;  // M == 0: no prefilter
+  stream::Sos sos{};
+  void* pmem = nullptr;
+  stream::AllocPrefilter pat{};
 };
 
 // test hook (mibminet_test_xdiv_gpu): xdiv against C division in 64 bits over e0 .. e0 + count - 1;
@@ -605,6 +611,7 @@ void streams_destroy(net_streams* g) {
     if (guard.err == hipSuccess) (void)hipDeviceSynchronize();  // no push still uses the rings
     (void)hipFree(g->mem);
     (void)hipFree(g->dmem);
+    (void)hipFree(g->pmem);
   }
   delete g;
 }
@@ -685,6 +692,9 @@ int streams_restart(net_streams* g, size_t i, int32_t set, void* stream) {
   if (g->q && g->K > 1)  // a decimator: the session's raw frames before the restart count as zeros
     if (const int rc = hip_err(hipMemsetAsync((char*)g->dmem + g->dat.hist + i * g->dat.per, 0, g->dat.per, o.st)))
       return rc;
+  if (g->M)  // a prefilter: zero state is the steady state of zero input
+    if (const int rc = hip_err(hipMemsetAsync((char*)g->pmem + g->pat.state + i * g->pat.per_state, 0, g->pat.per_state, o.st)))
+      return rc;
   if (g->q && g->each)  // an each-group's decimator: the session's raw position goes back to 0 too
     if (const int rc = hip_err(hipMemsetAsync((char*)g->dmem + g->dea.raw_pos + 8 * i, 0, 8, o.st))) return rc;
   // an each-group: the session's position goes back to 0 (its origin stays -1: there is none)
@@ -729,6 +739,63 @@ int streams_set_decimator(net_streams* g, size_t q, const float* taps, size_t K,
   return NET_OK;
 }
 
+// net_streams_set_prefilter, on either kind of group: every check, the capturing stream's last, comes
+// before the allocation; the group changes only once the states are zero.  The sections travel by
+// value in the prefilter kernel's arguments, so the device holds no copy of them.  The stream is
+// waited for, as streams_set_decimator waits.
+int streams_set_prefilter(net_streams* g, const float* sos, size_t M, void* stream) {
+  if (const int rc = stream::check_set_prefilter(g != nullptr, g && g->q != 0, g && g->M != 0,
+                                                 g && (g->pos != 0 || g->raw_pos != 0), sos, M))
+    return rc;
+  const OpenGroup o(*g, stream, REFUSE_CAPTURE);
+  if (o.rc) return o.rc;
+  const stream::AllocPrefilter a = stream::alloc_prefilter(g->S, (size_t)g->bank->sets[0].C, M, g->q, g->max_push);
+  void* mem = nullptr;
+  hipError_t e = hipMalloc(&mem, a.bytes);
+  if (e != hipSuccess) return hip_err(e);
+  e = hipMemsetAsync(mem, 0, a.scratch, o.st);  // the states; the scratch is written before it is read
+  if (e == hipSuccess) e = hipStreamSynchronize(o.st);
+  if (e != hipSuccess) {
+    (void)hipFree(mem);
+    return hip_err(e);
+  }
+  g->pmem = mem;
+  g->pat = a;
+  std::memcpy(g->sos.c, sos, 5 * sizeof(float) * M);
+  g->M = M;
+  return NET_OK;
+}
+
+// calls f with M as a std::integral_constant (M in 1 .. stream::MAX_SECTIONS)
+template <class F>
+int with_sections(size_t M, F&& f) {
+  switch (M) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+  }
+  return NET_ERR_INVALID;
+}
+
+// The prefilter's launch (stream::k_prefilter) over S sessions of R electrodes and n_view frames each
+// (EACH: at most, the trip counts from raw): one lane per (session, electrode) in waves of their own,
+// at most 32 per CU, grid-stride beyond that.
+template <bool EACH>
+int launch_prefilter(const DeviceState& ds, hipStream_t st, const float* x, float* y, float* state,
+                     const stream::RawRec* raw, size_t S, size_t R, size_t n_view, size_t M, const stream::Sos& sos) {
+  const size_t lanes = S * R;  // S < 2^31, R <= 2^6
+  return with_sections(M, [&](auto m) {
+    hipLaunchKernelGGL((stream::k_prefilter<EACH, decltype(m)::value>), dim3((unsigned)capped_grid(ds, (lanes + 63) / 64, 32)),
+                       dim3(64), 0, st, x, y, state, raw, (unsigned long long)lanes, (unsigned)R, (unsigned)n_view, sos);
+    return hip_err(hipGetLastError());
+  });
+}
+
 // net_streams_push_raw_f32_tm: every check (stream::check_push_raw, then the stream's capture status)
 // comes before the first launch and before a position moves.  Layer 1 reads the histories, the
 // history kernel behind it rewrites them, the windows' kernel is a plain push's.
@@ -745,6 +812,13 @@ int streams_push_raw(net_streams* g, const float* x, size_t n_raw, int8_t* y, in
   if (o.rc) return o.rc;
   char* dmem = (char*)g->dmem;
   const stream::Push& p = r.push;
+  if (g->M) {  // a prefilter: the kernels below take the filtered frames where they took x
+    float* const f = (float*)((char*)g->pmem + g->pat.scratch);
+    if (const int rc = launch_prefilter<false>(o.sc.ds, o.st, x, f, (float*)((char*)g->pmem + g->pat.state), nullptr, g->S,
+                                               (size_t)hg.C, n_raw, g->M, g->sos))
+      return rc;
+    x = f;
+  }
   const int rc = with_flags(hg, [&](auto rb, auto xr, auto cb) {
     constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
     if (r.m) {
@@ -831,6 +905,13 @@ int streams_push_each_raw(net_streams* g, const float* x, const int32_t* cnt_in,
                      (long long*)win0, (int*)n_bad, (int)g->S, hg.T, (unsigned long long)g->hop, (int)g->cap, (int)g->q,
                      (int)g->K, (int)n_raw_max);
   if (const int rc = hip_err(hipGetLastError())) return rc;
+  if (g->M) {  // a prefilter, its trip counts from the raw records: the kernels below take the filtered slots
+    float* const f = (float*)((char*)g->pmem + g->pat.scratch);
+    if (const int rc = launch_prefilter<true>(o.sc.ds, o.st, x, f, (float*)((char*)g->pmem + g->pat.state), raw, g->S,
+                                              (size_t)hg.C, n_raw_max, g->M, g->sos))
+      return rc;
+    x = f;
+  }
   const int rc = with_flags(hg, [&](auto rb, auto xr, auto cb) {
     constexpr bool RB = decltype(rb)::value, XR = decltype(xr)::value, CB = decltype(cb)::value;
     const stream::Decim dc{(const float*)(dmem + g->dat.taps), (const int8_t*)(dmem + g->dat.hist), (int)g->K, (int)g->q, 0, 0,
@@ -1297,6 +1378,18 @@ int net_streams_raw_info(const net_streams_t* st, int64_t* info) {
 
 int net_streams_set_decimator_each(net_streams_t* st, size_t q, const float* taps, size_t K, void* stream) {
   return streams_set_decimator(st, q, taps, K, stream, true);
+}
+
+int net_streams_set_prefilter(net_streams_t* st, const float* sos, size_t M, void* stream) {
+  return streams_set_prefilter(st, sos, M, stream);
+}
+
+int net_streams_prefilter_info(const net_streams_t* st, int64_t* info) {
+  if (!st || !info) return NET_ERR_INVALID;
+  info[0] = (int64_t)st->M;
+  info[1] = st->M ? (int64_t)(st->q * st->max_push) : 0;
+  info[2] = st->M ? (int64_t)st->pat.bytes : 0;
+  return NET_OK;
 }
 
 size_t net_streams_each_raw_rows(size_t hop, size_t q, size_t n_raw_max) {

@@ -9,10 +9,11 @@
 // (net_streams_set_decimator) the samples a raw push completes, the history's size and slots and
 // the checks and plan of a raw push; for an each-group with a decimator
 // (net_streams_set_decimator_each) the per-session plan of a raw push (plan_each_raw, shared with its
-// plan kernel), its allocation and its checks.  HIP-free like entry_host.hpp, whose windows_count it
-// uses: included by mibminet.hip, forward_stream.hpp and five stand-alone host programs
-// (tests/stream_host_main.cpp, tests/stream_each_host_main.cpp, tests/stream_at_host_main.cpp,
-// tests/decim_host_main.cpp, tests/decim_each_host_main.cpp).
+// plan kernel), its allocation and its checks; for a prefilter (net_streams_set_prefilter) the
+// sections as the kernel takes them, the checks and the allocation.  HIP-free like entry_host.hpp,
+// whose windows_count it uses: included by mibminet.hip, forward_stream.hpp and six stand-alone host
+// programs (tests/stream_host_main.cpp, tests/stream_each_host_main.cpp, tests/stream_at_host_main.cpp,
+// tests/decim_host_main.cpp, tests/decim_each_host_main.cpp, tests/prefilter_host_main.cpp).
 //
 // The ring.  A session's ring holds the layer-1 output of its last cap samples, sample t at position
 // t mod cap (and again at t mod cap + cap, forward_stream.hpp).  A push of n samples at position p0
@@ -468,6 +469,52 @@ inline int check_push_each_raw(size_t S, size_t R, size_t hop, size_t max_push, 
   g.hist_items = S * g.keep_max * R;  // S < 2^31, keep_max < 2^7, R <= 2^6
   g.each = p;
   return NET_OK;
+}
+
+// ---- a prefilter: an IIR cascade ahead of the decimator (net_streams_set_prefilter) ----------------
+// A group with a decimator, uniform or each, may be given M second-order sections that every raw
+// frame passes, per session and electrode, before the FIR sees it (k_prefilter, forward_stream.hpp).
+// The group owns the states [S][M][2][R] float32 (z1 then z2 of a section, a session's contiguous)
+// and a scratch [S][q max_push][R] float32 that holds the filtered frames of one push.
+
+constexpr size_t MAX_SECTIONS = 8;  // M
+
+// The sections as the kernel takes them, by value in its arguments (160 bytes): {b0, b1, b2, a1, a2}
+// of section j, a0 = 1.  Rows at and past M are unread.
+struct Sos {
+  float c[MAX_SECTIONS][5];
+};
+
+// The checks of net_streams_set_prefilter before its capturing stream's, in their documented order.
+// have_decim: the group has a decimator; pushed: it has taken a push; have_prefilter: it has a
+// prefilter already.  Of the flags check_set_decimator takes, two are not taken here because they
+// could decide nothing: `each` (either kind of group may have a prefilter) and `have_scales` (a group
+// has a decimator only if its bank has scales).  No coefficient is read before M is known to be in
+// range.
+inline int check_set_prefilter(bool have_group, bool have_decim, bool have_prefilter, bool pushed, const float* sos,
+                               size_t M) {
+  if (!have_group) return NET_ERR_INVALID;
+  if (!have_decim || have_prefilter || pushed) return NET_ERR_INVALID;
+  if (M < 1 || M > MAX_SECTIONS || !sos) return NET_ERR_INVALID;
+  for (size_t i = 0; i < 5 * M; i++)
+    if (!finite_f32(sos[i])) return NET_ERR_INVALID;
+  return NET_OK;
+}
+
+// bytes of a prefilter's one allocation: the states, then at a multiple of 256 the scratch.
+// S max_push <= MAX_ITEMS < 2^31 (check_create), q <= 2^4, R <= 2^6, M <= 2^3: both products stay
+// below 2^45.
+struct AllocPrefilter {
+  size_t state, per_state, scratch, per_scratch, bytes;  // offsets of the two, bytes per session of each, the total
+};
+inline AllocPrefilter alloc_prefilter(size_t S, size_t R, size_t M, size_t q, size_t max_push) {
+  AllocPrefilter a;
+  a.state = 0;
+  a.per_state = 4 * 2 * M * R;
+  a.scratch = (S * a.per_state + 255) / 256 * 256;
+  a.per_scratch = 4 * q * max_push * R;
+  a.bytes = a.scratch + S * a.per_scratch;
+  return a;
 }
 
 }  // namespace stream

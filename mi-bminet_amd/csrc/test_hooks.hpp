@@ -187,4 +187,23 @@ int mibminet_test_fir_decimate(const float* x, size_t n_raw, size_t R, const flo
   return hip_err(hipGetLastError());
 }
 
+int mibminet_test_sos_filter(const float* x, size_t n, size_t R, const float* sos, size_t M, const float* state_in,
+                             float* out, float* state_out, int device, void* stream) {
+  if (R < 1 || R > 64 || n > stream::MAX_Q * stream::MAX_PUSH || !state_in || !state_out) return NET_ERR_INVALID;
+  if (M < 1 || M > stream::MAX_SECTIONS || !sos || (n && (!x || !out))) return NET_ERR_INVALID;
+  if (const int rc = check_device(device)) return rc;
+  DeviceState& ds = g_devs[device];
+  std::lock_guard<std::mutex> lk(ds.mu);
+  DeviceGuard guard(device);
+  if (guard.err != hipSuccess) return hip_err(guard.err);
+  if (const int rc = ensure_cus(ds, device)) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  if (state_out != state_in)
+    if (const int rc = hip_err(hipMemcpyAsync(state_out, state_in, 8 * M * R, hipMemcpyDeviceToDevice, st))) return rc;
+  if (n == 0) return NET_OK;
+  stream::Sos c{};
+  std::memcpy(c.c, sos, 5 * sizeof(float) * M);
+  return launch_prefilter<false>(ds, st, x, out, state_out, nullptr, 1, R, n, M, c);
+}
+
 }  // extern "C"

@@ -106,6 +106,8 @@ PROTOTYPES = {
     "net_streams_each_raw_rows": "size_t (size_t, size_t, size_t)",
     "net_streams_push_each_raw_f32_tm": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr, ptr, ptr)",
     "net_streams_raw_positions": "int (ptr, ptr, ptr)",
+    "net_streams_set_prefilter": "int (ptr, ptr, size_t, ptr)",
+    "net_streams_prefilter_info": "int (ptr, ptr)",
     "net_streams_windows_at": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr)",
     "net_streams_windows_at_feat": "int (ptr, ptr, ptr, size_t, ptr, ptr, ptr, ptr)",
     "net_streams_at_span": "int (ptr, ptr, ptr)",
@@ -139,6 +141,7 @@ PROTOTYPES = {
     "mibminet_test_bank_device_copies": "int (ptr)",
     "mibminet_test_streams_ring": "int (ptr, size_t, ptr)",
     "mibminet_test_fir_decimate": "int (ptr, size_t, size_t, ptr, ptr, size_t, size_t, size_t, ptr, int, ptr)",
+    "mibminet_test_sos_filter": "int (ptr, size_t, size_t, ptr, size_t, ptr, ptr, ptr, int, ptr)",
 }
 EXPORTED_SYMBOLS = tuple(n for n in PROTOTYPES if n.startswith("net_"))
 NET_PATH_FLOAT, NET_PATH_EXACT, NET_PATH_GENERAL = 0, 1, 2
@@ -1192,6 +1195,29 @@ class _StreamGroup(_Handle):
         _check(load().net_streams_raw_info(self.handle, arr), "net_streams_raw_info")
         return list(arr)
 
+    def prefilter(self, sos, stream=None) -> np.ndarray:
+        """net_streams_set_prefilter: once, after the decimator and before the first push.  ``sos`` is
+        [M][5] = {b0, b1, b2, a1, a2} (a0 = 1) or scipy's [M][6] = {b0, b1, b2, a0, a1, a2}, which is
+        divided by a0 in float64 and then rounded to float32.  From then on every raw frame passes the
+        cascade, per session and electrode, ahead of the FIR, bit for bit as decimate.sos_filter
+        states it.  Returns the float32 [M][5] that was handed over."""
+        c = np.asarray(sos, dtype=np.float64)
+        if c.ndim != 2 or c.shape[1] not in (5, 6):
+            raise ValueError("sos must be an array [M][5] or [M][6]")
+        if c.shape[1] == 6:
+            c = np.concatenate([c[:, :3], c[:, 4:]], axis=1) / c[:, 3:4]
+        c = np.ascontiguousarray(c, dtype=np.float32)
+        s = _stream_on(self.device, stream)
+        _check(load().net_streams_set_prefilter(self.handle, c.ctypes.data, c.shape[0], s.cuda_stream),
+               "net_streams_set_prefilter")
+        return c
+
+    def prefilter_info(self) -> list:
+        """net_streams_prefilter_info: [M (0: none), the scratch's frames per session, bytes allocated]."""
+        arr = (ctypes.c_int64 * 3)()
+        _check(load().net_streams_prefilter_info(self.handle, arr), "net_streams_prefilter_info")
+        return list(arr)
+
     def _push_source(self, x, layout: str, f32: bool) -> tuple:
         """Checks a push's ``x``, int8 or (``f32``) float32, [S][C][n] or [S][n][C] by ``layout``.  Returns
         the entry's suffix ("", "_f32" or "_f32_tm"), the layout code as the entry takes it (the
@@ -1465,6 +1491,25 @@ def fir_decimate_torch(x, hist, taps, q: int, raw_pos: int, stream=None):
     _check(load().mibminet_test_fir_decimate(x.data_ptr(), n_raw, R, hist.data_ptr() if K > 1 else None, taps.data_ptr(), K,
                                              q, raw_pos, out.data_ptr(), dev, s.cuda_stream), "mibminet_test_fir_decimate")
     return out
+
+
+def sos_filter_torch(x, sos, state, stream=None):
+    """Test hook (mibminet_test_sos_filter): the prefilter's kernel on one session's chunk ``x`` [n][R]
+    with the state ``state`` [M][2][R] before it (float32 device tensors) and the sections ``sos``
+    [M][5] (a host array, float32).  Returns (the filtered floats [n][R], the new state [M][2][R])."""
+    torch = _torch()
+    c = np.ascontiguousarray(sos, dtype=np.float32)
+    if c.ndim != 2 or c.shape[1] != 5:
+        raise ValueError("sos must be an array [M][5]")
+    _check_tensor(x, "x", ("float32",), ("n", "R"))
+    n, R, M = int(x.shape[0]), int(x.shape[1]), c.shape[0]
+    _check_tensor(state, "state", ("float32",), (M, 2, R))
+    s, dev = _launch(x, stream)
+    out, new = torch.empty_like(x), torch.empty_like(state)
+    _check(load().mibminet_test_sos_filter(x.data_ptr() if n else None, n, R, c.ctypes.data, M, state.data_ptr(),
+                                           out.data_ptr() if n else None, new.data_ptr(), dev, s.cuda_stream),
+           "mibminet_test_sos_filter")
+    return out, new
 
 
 def quantize_input_torch(x, scale: float, stream=None):

@@ -85,6 +85,23 @@ filled with zero frames at equal counts, then six ticks of random frames are ver
 In both, (new) is also captured into a graph once and replayed, (g), in a round of its own beside
 the eager call, as each_equal does.
 
+An IIR prefilter ahead of the decimator (net_streams_set_prefilter), 1,024 sessions of 22 x 1125 under
+16 grouped sets, hop 8, 16 decimated samples per tick, (q, K) = (2, 41) and (4, 81); the prefilter is
+M = 3: decimate.butter_sos(4, 0.5 Hz, high-pass) plus decimate.biquad("notch", 50 Hz, Q 30) at
+fs = 250 q; the frames are unit noise on a DC offset of 100:
+  f32_tm_prefilter    a uniform group.  (new) net_streams_push_raw_f32_tm with the prefilter; (p) the
+                      same push on a twin group without one and the same frames (new - p is what the
+                      prefilter costs per tick: recorded, not bounded); (a) the caller's recipe, all
+                      timed: the same recursion frame by frame in torch ops on [S][C] device tensors
+                      with carried state, then the raw push of the result.  Verified first, from zero
+                      state until past the first windows: every completed row of (new) equals (p)'s on
+                      decimate.sos_filter's frames (the CPU's, bit for bit the contract).  The claim
+                      checked is new <= a on the medians, with no margin, in every setting of both
+                      cases: the tool exits non-zero where it fails.
+  each_raw_prefilter  the same on an each-group, once with every count n_raw_max and once with counts
+                      drawn uniformly from 0 .. n_raw_max ((a) then masks its state updates per
+                      session), and (new) captured into a graph and replayed beside its eager call.
+
 Cue-locked trials of live sessions (net_streams_windows_at), 1,024 sessions of 22 x 1125 under 16
 grouped sets, hop 8, n 16:
   at_cues         Every tick is a push followed by one query per session, at an onset drawn uniformly
@@ -104,7 +121,7 @@ grouped sets, hop 8, n 16:
                   also stores 16 T64 bytes of layer-4 activations per window; the three rotate their
                   order from tick to tick.  Verified first: over six ticks (feat)'s logits equal (new)'s.
 
-  python tools/bench_streams.py [--cases mmmi_64,bci_1024,bci_1024_shuffled,each_equal,each_ragged,f32_tm,f32_tm_montage,f32_tm_decim,each_raw_equal,each_raw_ragged,at_cues,at_feat]
+  python tools/bench_streams.py [--cases mmmi_64,bci_1024,bci_1024_shuffled,each_equal,each_ragged,f32_tm,f32_tm_montage,f32_tm_decim,each_raw_equal,each_raw_ragged,f32_tm_prefilter,each_raw_prefilter,at_cues,at_feat]
                                 [--limit S] [--reps 1000] [--warmup 50] [--variant canonical|plain_bn]
                                 [--out-dir profiles]
 """
@@ -136,6 +153,10 @@ EACH_RAW_CASES = {  # name: (sessions, sets, C, T, N, most decimated samples per
     "each_raw_ragged": (1024, 16, 22, 1125, 4, 32, True, ((2, 41), (4, 81))),
 }
 
+PREFILTER_CASES = {  # name: (sessions, sets, C, T, N, decimated samples per tick, each-group, ((q, K), ...))
+    "f32_tm_prefilter": (1024, 16, 22, 1125, 4, 16, False, ((2, 41), (4, 81))),
+    "each_raw_prefilter": (1024, 16, 22, 1125, 4, 16, True, ((2, 41), (4, 81))),
+}
 AT_CASES = {  # name: (sessions, sets, C, T, N, n): net_streams_windows_at
     "at_cues": (1024, 16, 22, 1125, 4, 16),
 }
@@ -157,6 +178,8 @@ def run_case(name, limit, reps, warmup, variant, seed=2026):
         return run_decim(name, limit, reps, warmup, variant, seed)
     if name in EACH_RAW_CASES:
         return run_each_raw(name, limit, reps, warmup, variant, seed)
+    if name in PREFILTER_CASES:
+        return run_prefilter(name, limit, reps, warmup, variant, seed)
     import numpy as np
     import torch
 
@@ -746,6 +769,147 @@ def run_each_raw(name, limit, reps, warmup, variant, seed=2026):
     return res
 
 
+def run_prefilter(name, limit, reps, warmup, variant, seed=2026):
+    import numpy as np
+    import torch
+
+    from mibminet import decimate, lib
+    from mibminet.params import ParamSet
+
+    S, n_sets, C, T, N, n, each, settings = PREFILTER_CASES[name]
+    S = min(S, limit)
+    n_sets = min(n_sets, S)
+    sets = [ParamSet.synthetic(seed=seed + s, C=C, T=T, N=N, reorder_bn=variant != "plain_bn") for s in range(n_sets)]
+    scales = [1.0 + 0.25 * s for s in range(n_sets)]
+    bank = lib.Bank(sets, scales)
+    set_of = [int(v) for v in np.sort(np.arange(S) * n_sets // S)]
+    Group = lib.StreamsEach if each else lib.Streams
+    A = lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    nbad = torch.zeros((1,), dtype=torch.int32, device="cuda")
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    rng = np.random.default_rng(seed)
+    configs, mis_all, rows_all = [], 0, 0
+    for q, K in settings:
+        for ragged in ((False, True) if each else (False,)):
+            taps, fs = decimate.firwin_taps(q, K), 250.0 * q
+            sos = np.concatenate([decimate.butter_sos(4, 0.5, fs, "highpass"), decimate.biquad("notch", 50.0, fs, 30.0)])
+            M, n_raw = len(sos), q * n
+            groups = {key: Group(bank, set_of, HOP, n) for key in ("new", "p", "a")}
+            for st in groups.values():
+                st.decimate(q, taps)
+            groups["new"].prefilter(sos)
+            kmax = lib.each_raw_rows(HOP, q, n_raw) if each else -(-n // HOP)
+            xraw = torch.zeros((S, n_raw, C), dtype=torch.float32, device="cuda")  # the tick's frames as delivered
+            xfil = torch.zeros((S, n_raw, C), dtype=torch.float32, device="cuda")  # (p)'s and (a)'s: filtered beforehand
+            cin = torch.full((S,), n_raw, dtype=torch.int32, device="cuda")
+            y = {key: torch.zeros((S, kmax, N), dtype=torch.int8, device="cuda") for key in groups}
+            cout = {key: torch.zeros((S,), dtype=torch.int32, device="cuda") for key in groups}
+            za = torch.zeros((M, 2, S, C), dtype=torch.float32, device="cuda")     # (a)'s carried state
+            coef = [[float(v) for v in row] for row in sos]
+            tt = torch.arange(n_raw, dtype=torch.int32, device="cuda")
+
+            def push(key, x, st=stream):
+                h = groups[key].handle
+                if each:
+                    rc = A.net_streams_push_each_raw_f32_tm(h, x.data_ptr(), cin.data_ptr(), n_raw, y[key].data_ptr(),
+                                                            cout[key].data_ptr(), None, nbad.data_ptr(), st)
+                else:
+                    rc = A.net_streams_push_raw_f32_tm(h, x.data_ptr(), n_raw, y[key].data_ptr(), nbad.data_ptr(), st)
+                assert rc == 0, rc
+
+            def new(st=stream):
+                push("new", xraw, st)
+
+            def p():  # the parent's path: the raw push alone, on the same frames
+                push("p", xraw)
+
+            def a():  # the caller's recipe: the recursion frame by frame in torch ops on [S][C], then the raw push
+                with torch.no_grad():
+                    for t in range(n_raw):
+                        v = xraw[:, t]
+                        live = (cin > t).view(S, 1) if ragged else None
+                        for j, (b0, b1, b2, a1, a2) in enumerate(coef):
+                            w = b0 * v + za[j, 0]
+                            z1 = (b1 * v - a1 * w) + za[j, 1]
+                            z2 = b2 * v - a2 * w
+                            if ragged:
+                                z1, z2 = torch.where(live, z1, za[j, 0]), torch.where(live, z2, za[j, 1])
+                            za[j, 0], za[j, 1] = z1, z2
+                            v = w
+                        xfil[:, t] = v
+                push("a", xfil)
+
+            state = np.zeros((M, 2, S * C), np.float32)
+            mis = rows = 0
+            # the first windows complete on the way (ragged counts advance a session by n / 2 per tick on average)
+            ticks = int((2.5 if ragged else 1.0) * -(-T // n)) + VERIFY
+            for _ in range(ticks):
+                cnt = rng.integers(0, n_raw + 1, size=S).astype(np.int32) if ragged else np.full(S, n_raw, np.int32)
+                xraw.copy_(100.0 + torch.randn((S, n_raw, C), dtype=torch.float32, device="cuda", generator=g))  # a DC offset
+                xh, fil = xraw.cpu().numpy(), np.zeros((S, n_raw, C), np.float32)
+                st3 = state.reshape(M, 2, S, C)
+                for c in np.unique(cnt):  # the sessions of one count side by side, as the R of one call
+                    who = np.flatnonzero(cnt == c)
+                    if c == 0:
+                        continue
+                    flat = np.ascontiguousarray(xh[who, :c].transpose(1, 0, 2).reshape(c, -1))
+                    yf, z = decimate.sos_filter(flat, sos, np.ascontiguousarray(st3[:, :, who].reshape(M, 2, -1)))
+                    fil[who, :c] = yf.reshape(c, len(who), C).transpose(1, 0, 2)
+                    st3[:, :, who] = z.reshape(M, 2, len(who), C)
+                cin.copy_(torch.from_numpy(cnt))
+                xfil.copy_(torch.from_numpy(fil))
+                new()
+                push("p", xfil)
+                torch.cuda.synchronize()
+                if each:
+                    assert torch.equal(cout["new"], cout["p"])
+                    live = torch.arange(kmax, device="cuda").view(1, kmax) < cout["new"].view(S, 1)
+                    mis += int(((y["new"] != y["p"]).any(dim=2) & live).sum().item())
+                    rows += int(cout["new"].sum().item())
+                else:
+                    k = lib.load().net_streams_push_windows(bank.handle, HOP, groups["new"].info()[4] - n, n)
+                    mis += int((y["new"][:, :k] != y["p"][:, :k]).any(dim=2).sum().item())
+                    rows += S * int(k)
+            assert int(nbad.item()) == 0, (q, K, ragged, int(nbad.item()), cout["new"].min().item())
+            assert rows > 0, (q, K, ragged, groups["new"].info())
+            fns = {"new": new, "p": p, "a": a}
+            ms = time_alternating(fns, reps, warmup)
+            if each:
+                graph, side = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+                torch.cuda.synchronize()
+                with torch.cuda.stream(side):
+                    with torch.cuda.graph(graph, stream=side):
+                        new(side.cuda_stream)
+                ms.update(time_alternating({"new2": new, "g": graph.replay}, reps, warmup))
+            med = medians(ms)
+            c = {"q": q, "K": K, "M": M, "raw_frames_per_tick": n_raw, "counts": "uniform 0 .. n_raw_max" if ragged else "all n_raw_max",
+                 "rows_verified": rows, "mismatched_rows": mis, "ms_raw_push_with_prefilter": round(med["new"], 4),
+                 "ms_raw_push_with_prefilter_min_max": min_max(ms["new"]), "ms_raw_push_alone": round(med["p"], 4),
+                 "ms_raw_push_alone_min_max": min_max(ms["p"]), "ms_prefilter_cost_per_tick": round(med["new"] - med["p"], 4),
+                 "ms_torch_recursion_then_raw_push": round(med["a"], 4), "ms_torch_recursion_then_raw_push_min_max": min_max(ms["a"]),
+                 "new_over_a": round(med["new"] / med["a"], 4), "new <= a": med["new"] <= med["a"],
+                 "prefilter_info": groups["new"].prefilter_info()}
+            if each:
+                c.update({"ms_eager_beside_graph": round(med["new2"], 4), "ms_graph_replay": round(med["g"], 4),
+                          "graph_over_eager": round(med["g"] / med["new2"], 4)})
+                del graph
+            configs.append(c)
+            mis_all += mis
+            rows_all += rows
+            for st in groups.values():
+                st.close()
+    info = bank.info()
+    res = {"name": name, "sessions": S, "sets": n_sets, "C": C, "T": T, "N": N, "hop": HOP, "n": n, "variant": variant,
+           "prefilter": "butter_sos(4, 0.5 Hz, highpass) + biquad(notch, 50 Hz, Q 30) at fs = 250 q", "exact_division": bool(info[4]),
+           "rows_verified": rows_all, "mismatched_rows": mis_all, "reps": reps, "warmup": warmup,
+           "device": torch.cuda.get_device_name(0), "configs": configs,
+           "gates": {f"new <= a (q {c['q']}, K {c['K']}, {c['counts']})": c["new <= a"] for c in configs},
+           "pass": mis_all == 0 and rows_all > 0 and all(c["new <= a"] for c in configs)}
+    bank.close()
+    return res
+
+
 def run_at(name, limit, reps, warmup, variant, seed=2026):
     import numpy as np
     import torch
@@ -949,4 +1113,4 @@ def b_call(A, bank, recipe, nbad, stream):
 
 
 if __name__ == "__main__":
-    main(__doc__, {**CASES, **EACH_CASES, **F32_CASES, **DECIM_CASES, **EACH_RAW_CASES, **AT_CASES, **AT_FEAT_CASES}, run_case, "limit", "streams", lambda res: res["mismatched_rows"], reps=1000, warmup=50)
+    main(__doc__, {**CASES, **EACH_CASES, **F32_CASES, **DECIM_CASES, **EACH_RAW_CASES, **PREFILTER_CASES, **AT_CASES, **AT_FEAT_CASES}, run_case, "limit", "streams", lambda res: res["mismatched_rows"] + (res["name"] in PREFILTER_CASES and not res["pass"]), reps=1000, warmup=50)
