@@ -109,6 +109,29 @@ int mibminet_test_bank_device_copies(const net_bank_t* bank);
 typedef struct net_streams net_streams_t;
 int mibminet_test_streams_ring(const net_streams_t* st, size_t i, void* out);
 
+/* Places a fresh stream group at a position, so that its kernels can be run where a session is
+ * after days: the group behaves from then on as one whose samples before the position were all
+ * zero frames (net_streams_restart's definition of what a session does not remember).  pos: S HOST
+ * entries, raw positions if the group has a decimator, else sample positions; origin: NULL or S
+ * HOST entries, for a uniform group only.  Call it after net_streams_set_decimator[_each] and
+ * net_streams_set_prefilter, which refuse a group that is no longer at 0, and before the first push
+ * or restart.
+ *   A uniform group: the entries of pos are all equal, P.  Its position becomes P, or with a
+ * decimator its raw position P and its position D(P) = ceil(P / q); the windows returned so far
+ * stay 0; every session's origin, on the host and on the device, becomes origin[s] if given, else
+ * the new (decimated) position, so that with the default every window that starts before the seek
+ * is a zero row counted in n_bad, exactly as after a restart.
+ *   An each-group: the device's position of session s becomes pos[s], or with a decimator its raw
+ * position pos[s] and its position D(pos[s]).  The count of pushes enqueued (net_streams_info) stays 0.
+ *   Rings, histories and prefilter states stay as creation left them, all zero.  Synchronous: the
+ * group's device is synchronised and the values are copied with plain copies; no kernel runs.
+ * NET_ERR_INVALID, the group unchanged, for: a NULL group or pos; a group that has taken a push, a
+ * restart or a seek; a negative entry; on an each-group an entry above INT64_MAX - 65,536 (with a
+ * decimator: INT64_MAX - 2^20, the limits its plan keeps; a uniform group's bound is INT64_MAX
+ * itself); entries of a uniform group that are not all equal; origin given for an each-group; an
+ * origin outside 0 .. D(P) (D(P) = P without a decimator). */
+int mibminet_test_streams_seek(net_streams_t* st, const int64_t* pos, const int64_t* origin);
+
 /* The FIR decimator of net_streams_push_raw_f32_tm before its quantiser: the device function the
  * layer-1 kernel runs, on one session.  x: DEVICE [n_raw][R] float32, the chunk at raw position
  * raw_pos; hist: DEVICE [K - 1][R] float32, raw frame a < raw_pos at slot a mod (K - 1) (NULL for

@@ -62,6 +62,9 @@ using namespace mib;
 // dat): behind the histories come the sessions' raw positions and raw records, and raw_pos stays 0.
 // A prefilter (net_streams_set_prefilter) adds M, the sections and a third allocation pmem
 // (stream::alloc_prefilter: the states, then the scratch of one push's filtered frames).
+// restarted and seeked record that a session was restarted or that the test hook
+// mibminet_test_streams_seek placed the group: a seek wants a group that has seen neither, and a
+// seeked group counts as pushed to the two setters above.
 // A launching entry reaches all of this through OpenGroup (section "live streams").
 struct net_streams {
   const net_bank* bank = nullptr;
@@ -82,6 +85,7 @@ struct net_streams {
   stream::Sos sos{};
   void* pmem = nullptr;
   stream::AllocPrefilter pat{};
+  bool restarted = false, seeked = false;
 };
 
 // test hook (mibminet_test_xdiv_gpu): xdiv against C division in 64 bits over e0 .. e0 + count - 1;
@@ -703,6 +707,7 @@ int streams_restart(net_streams* g, size_t i, int32_t set, void* stream) {
   if (const int rc = hip_err(hipGetLastError())) return rc;
   if (!g->each) g->origin[i] = (int64_t)g->pos;
   g->set[i] = set;
+  g->restarted = true;
   return NET_OK;
 }
 
@@ -714,7 +719,7 @@ int streams_restart(net_streams* g, size_t i, int32_t set, void* stream) {
 int streams_set_decimator(net_streams* g, size_t q, const float* taps, size_t K, void* stream, bool each = false) {
   if (each && (!g || !g->each)) return NET_ERR_INVALID;
   if (const int rc = stream::check_set_decimator(g != nullptr, g && g->each && !each, g && !g->bank->scales.empty(),
-                                                 g && g->q != 0, g && g->pos != 0, q, taps, K))
+                                                 g && g->q != 0, g && (g->pos != 0 || g->seeked), q, taps, K))
     return rc;
   const OpenGroup o(*g, stream, REFUSE_CAPTURE);
   if (o.rc) return o.rc;
@@ -745,7 +750,7 @@ int streams_set_decimator(net_streams* g, size_t q, const float* taps, size_t K,
 // waited for, as streams_set_decimator waits.
 int streams_set_prefilter(net_streams* g, const float* sos, size_t M, void* stream) {
   if (const int rc = stream::check_set_prefilter(g != nullptr, g && g->q != 0, g && g->M != 0,
-                                                 g && (g->pos != 0 || g->raw_pos != 0), sos, M))
+                                                 g && (g->pos != 0 || g->raw_pos != 0 || g->seeked), sos, M))
     return rc;
   const OpenGroup o(*g, stream, REFUSE_CAPTURE);
   if (o.rc) return o.rc;

@@ -10,7 +10,8 @@
 // the checks and plan of a raw push; for an each-group with a decimator
 // (net_streams_set_decimator_each) the per-session plan of a raw push (plan_each_raw, shared with its
 // plan kernel), its allocation and its checks; for a prefilter (net_streams_set_prefilter) the
-// sections as the kernel takes them, the checks and the allocation.  HIP-free like entry_host.hpp,
+// sections as the kernel takes them, the checks and the allocation; for the test hook that places a
+// fresh group at a position (mibminet_test_streams_seek) its checks.  HIP-free like entry_host.hpp,
 // whose windows_count it uses: included by mibminet.hip, forward_stream.hpp and six stand-alone host
 // programs (tests/stream_host_main.cpp, tests/stream_each_host_main.cpp, tests/stream_at_host_main.cpp,
 // tests/decim_host_main.cpp, tests/decim_each_host_main.cpp, tests/prefilter_host_main.cpp).
@@ -468,6 +469,29 @@ inline int check_push_each_raw(size_t S, size_t R, size_t hop, size_t max_push, 
   g.keep_max = n_raw_max < K - 1 ? n_raw_max : K - 1;
   g.hist_items = S * g.keep_max * R;  // S < 2^31, keep_max < 2^7, R <= 2^6
   g.each = p;
+  return NET_OK;
+}
+
+// ---- a fresh group placed at a position (mibminet_test_streams_seek, include/mibminet_testing.h) ----
+// The test hook's checks, in their documented order.  fresh: the group has taken no push, no restart
+// and no seek.  pos: S entries, raw positions on a group with a decimator (q != 0), else sample
+// positions; origin: null or S entries, a uniform group's only.  An entry is refused when negative
+// or, on an each-group, above the limit its plan keeps (EACH_RAW_LIMIT with a decimator, else
+// EACH_POS_LIMIT; a uniform group's bound, INT64_MAX, is the type's); a uniform group's entries must
+// all be equal; an origin must lie in 0 .. D(pos), D(pos) = pos without a decimator.
+inline int check_seek(bool have_group, bool each, bool fresh, size_t S, size_t q, const int64_t* pos,
+                      const int64_t* origin) {
+  if (!have_group || !pos) return NET_ERR_INVALID;
+  if (!fresh) return NET_ERR_INVALID;
+  if (each && origin) return NET_ERR_INVALID;
+  const int64_t limit = !each ? INT64_MAX : q ? EACH_RAW_LIMIT : EACH_POS_LIMIT;
+  for (size_t s = 0; s < S; s++)
+    if (pos[s] < 0 || pos[s] > limit || (!each && pos[s] != pos[0])) return NET_ERR_INVALID;
+  if (origin)
+    for (size_t s = 0; s < S; s++) {
+      const uint64_t d = q ? raw_decimated(q, (uint64_t)pos[s]) : (uint64_t)pos[s];
+      if (origin[s] < 0 || (uint64_t)origin[s] > d) return NET_ERR_INVALID;
+    }
   return NET_OK;
 }
 

@@ -167,6 +167,34 @@ int mibminet_test_streams_ring(const net_streams_t* st, size_t i, void* out) {
   return hip_err(e);
 }
 
+int mibminet_test_streams_seek(net_streams_t* st, const int64_t* pos, const int64_t* origin) {
+  if (!st) return NET_ERR_INVALID;
+  DeviceState& ds = g_devs[st->device];
+  std::lock_guard<std::mutex> lk(ds.mu);
+  const bool fresh = st->pos == 0 && st->raw_pos == 0 && !st->restarted && !st->seeked;
+  if (const int rc = stream::check_seek(true, st->each, fresh, st->S, st->q, pos, origin)) return rc;
+  DeviceGuard guard(st->device);
+  if (guard.err != hipSuccess) return hip_err(guard.err);
+  const size_t S = st->S, q = st->q;
+  auto D = [q](int64_t P) { return q ? (int64_t)stream::raw_decimated(q, (uint64_t)P) : P; };
+  // what the device gets: a uniform group's origins, an each-group's (decimated) positions
+  std::vector<int64_t> v(S);
+  for (size_t s = 0; s < S; s++) v[s] = st->each ? D(pos[s]) : origin ? origin[s] : D(pos[0]);
+  char* const to = (char*)st->mem + (st->each ? st->at.pos : st->at.base.origin);
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess && st->each && q)  // the raw positions first: a failure leaves the pair as it was or unread
+    e = hipMemcpy((char*)st->dmem + st->dea.raw_pos, pos, 8 * S, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(to, v.data(), 8 * S, hipMemcpyHostToDevice);
+  if (e != hipSuccess) return hip_err(e);
+  if (!st->each) {
+    st->raw_pos = q ? (uint64_t)pos[0] : 0;
+    st->pos = (uint64_t)D(pos[0]);
+    st->origin = v;
+  }
+  st->seeked = true;
+  return NET_OK;
+}
+
 int mibminet_test_fir_decimate(const float* x, size_t n_raw, size_t R, const float* hist, const float* taps, size_t K,
                                size_t q, size_t raw_pos, float* out, int device, void* stream) {
   if (R < 1 || R > 64 || q < 1 || q > stream::MAX_Q || K < 1 || K > stream::MAX_TAPS || !taps) return NET_ERR_INVALID;

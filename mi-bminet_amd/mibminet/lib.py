@@ -140,6 +140,7 @@ PROTOTYPES = {
     "mibminet_test_bank_copy": "int (ptr, size_t, ptr, size_t, ptr)",
     "mibminet_test_bank_device_copies": "int (ptr)",
     "mibminet_test_streams_ring": "int (ptr, size_t, ptr)",
+    "mibminet_test_streams_seek": "int (ptr, ptr, ptr)",
     "mibminet_test_fir_decimate": "int (ptr, size_t, size_t, ptr, ptr, size_t, size_t, size_t, ptr, int, ptr)",
     "mibminet_test_sos_filter": "int (ptr, size_t, size_t, ptr, size_t, ptr, ptr, ptr, int, ptr)",
 }
@@ -1459,6 +1460,19 @@ def streams_ring(streams, i: int) -> np.ndarray:
     out = np.empty((16, 2 * streams.cap), np.int8)
     _check(load().mibminet_test_streams_ring(streams.handle, i, out.ctypes.data), "mibminet_test_streams_ring")
     return out
+
+
+def streams_seek(streams, pos, origin=None) -> None:
+    """Test hook (mibminet_test_streams_seek): places the fresh Streams or StreamsEach group at the
+    positions ``pos`` (S ints; raw ones on a group with a decimator), a uniform group's origins at
+    ``origin`` (S ints) or, by default, at the new position.  After ``decimate`` and ``prefilter``,
+    before the first push or restart."""
+    def arr(v):
+        return None if v is None else (ctypes.c_int64 * len(v))(*[int(e) for e in v])
+
+    if len(pos) != streams.S or (origin is not None and len(origin) != streams.S):
+        raise ValueError(f"one position (and origin) for each of the {streams.S} sessions")
+    _check(load().mibminet_test_streams_seek(streams.handle, arr(pos), arr(origin)), "mibminet_test_streams_seek")
 
 
 def raw_samples(q: int, raw_pos: int, n_raw: int) -> int:

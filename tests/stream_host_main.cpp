@@ -2,7 +2,8 @@
 // a stand-alone program (tests/test_streams_host_sanitizers.py builds it with
 // -fsanitize=address,undefined and runs it).  It walks the edges where a sum, a product or a
 // conversion could wrap: positions near 2^63 and 2^64, S k at the item limit, max_push at both
-// bounds, hops past INT64_MAX.  Every value is printed, one case per line, and the Python side
+// bounds, hops past INT64_MAX, and the checks of the test hook that places a group (check_seek) at
+// both ends of each kind's range.  Every value is printed, one case per line, and the Python side
 // compares each with its own restatement; an overflow that the header's arithmetic performed would
 // be an UndefinedBehaviorSanitizer report.  Prints "cases <n>" last; exits 0 when every check here held.
 #include <cinttypes>
@@ -73,6 +74,18 @@ static void create_case(bool bank, size_t n_sets, const std::vector<int32_t>* se
   g_cases++;
 }
 
+// one seek check (the test hook's): the lists are printed, so the Python side restates the verdict
+static void seek_case(bool group, bool each, bool fresh, size_t q, const std::vector<int64_t>* pos,
+                      const std::vector<int64_t>* origin) {
+  const size_t S = pos ? pos->size() : origin ? origin->size() : 3;
+  const int rc = stream::check_seek(group, each, fresh, S, q, pos ? pos->data() : nullptr, origin ? origin->data() : nullptr);
+  std::printf("seek %d %d %d %zu %zu %d %d", (int)group, (int)each, (int)fresh, q, S, (int)(pos != nullptr), (int)(origin != nullptr));
+  if (pos) for (int64_t v : *pos) std::printf(" %" PRId64, v);
+  if (origin) for (int64_t v : *origin) std::printf(" %" PRId64, v);
+  std::printf(" : %d\n", rc);
+  g_cases++;
+}
+
 int main() {
   const uint64_t I63 = (uint64_t)INT64_MAX;
   for (size_t T : {(size_t)64, (size_t)1125, (size_t)4096})
@@ -133,6 +146,41 @@ int main() {
   for (size_t mp : {(size_t)1, (size_t)37, (size_t)65536})
     for (size_t S : {stream::MAX_ITEMS / mp - 1, stream::MAX_ITEMS / mp, stream::MAX_ITEMS / mp + 1, SIZE_MAX / mp, SIZE_MAX})
       create_case(true, 5, nullptr, S, 3, mp, 0, true);
+  // seek: positions at both ends of each kind's range and around 2^31, 2^32 and 2^53, with and
+  // without a decimator, origins at both ends of 0 .. D(pos) and one past them
+  {
+    using V = std::vector<int64_t>;
+    const int64_t top = INT64_MAX, lim = stream::EACH_POS_LIMIT, raw = stream::EACH_RAW_LIMIT;
+    const V edges = {0, 1, ((int64_t)1 << 31) - 1, (int64_t)1 << 31, ((int64_t)1 << 32) - 1, (int64_t)1 << 32,
+                     ((int64_t)1 << 53) + 3 * ((int64_t)1 << 32) + 7, raw - 1, raw, raw + 1, lim - 1, lim, lim + 1, top - 1, top,
+                     -1, INT64_MIN};
+    for (size_t q : {(size_t)0, (size_t)1, (size_t)3, (size_t)16})
+      for (int64_t p : edges) {
+        const V same = {p, p, p}, mixed = {5, p, 5}, last = {p, p, p - (p > 0) + (p <= 0)};
+        for (int each = 0; each < 2; each++) {
+          seek_case(true, each, true, q, &same, nullptr);
+          seek_case(true, each, true, q, &mixed, nullptr);
+          seek_case(true, each, true, q, &last, nullptr);
+        }
+        if (p < 0) continue;
+        const int64_t d = q ? (int64_t)stream::raw_decimated(q, (uint64_t)p) : p;
+        const V o_lo = {0, 0, 0}, o_hi = {d, 0, d}, o_neg = {0, -1, 0}, o_min = {INT64_MIN, 0, 0};
+        for (const V* o : {&o_lo, &o_hi, &o_neg, &o_min}) seek_case(true, false, true, q, &same, o);
+        if (d < top) {
+          const V o_past = {0, 0, d + 1};
+          seek_case(true, false, true, q, &same, &o_past);
+        }
+        seek_case(true, true, true, q, &same, &o_lo);  // an each-group takes no origin
+      }
+    const V ok = {7, 7, 7}, zero = {0, 0, 0};
+    for (int each = 0; each < 2; each++) {
+      seek_case(false, each, true, 0, &ok, nullptr);
+      seek_case(true, each, false, 0, &ok, nullptr);
+      seek_case(true, each, true, 0, nullptr, nullptr);
+      seek_case(true, each, true, 2, nullptr, &zero);
+      seek_case(true, each, true, 2, &zero, nullptr);
+    }
+  }
   std::printf("cases %d\n", g_cases);
   if (g_bad) std::printf("%d checks failed\n", g_bad);
   return g_bad ? 1 : 0;

@@ -50,9 +50,10 @@ def schedule(T, q, K, max_push=MAX_PUSH):
     return tuple(ns)
 
 
-def plan(T, q, ns, hop=HOP):
-    """Per raw push: (raw position, n_raw, decimated position, m, k, the k onsets)."""
-    out, P = [], 0
+def plan(T, q, ns, hop=HOP, raw=0):
+    """Per raw push of the list ns from raw position raw: (raw position, n_raw, decimated position, m,
+    k, the k onsets)."""
+    out, P = [], raw
     for n in ns:
         d0, d1 = decimate.raw_decimated(q, P), decimate.raw_decimated(q, P + n)
         k, W0 = ss.push_windows(T, hop, d0, d1 - d0), ss.windows_count(T, d0, hop)
@@ -99,15 +100,17 @@ def reference(C, T, N, q, K):
     return sets, h, [b[0] for b in both], [b[1] for b in both]
 
 
-def check_rings(st, sets, qd, set_of=SETS, skip=()):
+def check_rings(st, sets, qd, set_of=SETS, skip=(), base=0):
     """Every ring (but those of the sessions `skip`) holds, twice, the oracle's layer 1 of the session's
-    last cap decimated samples."""
+    last cap decimated samples.  base: the position of qd's first sample on the group's axis (an int,
+    or one per session), where the group did not start at 0."""
     c = st.cap
     for i, s in enumerate(set_of):
         if i in skip:
             continue
         Ld = qd[i].shape[1]
         t = np.arange(max(0, Ld - c), Ld)
+        at = ((base if isinstance(base, int) else int(base[i])) % c + t) % c
         ring = lib.streams_ring(st, i)
         np.testing.assert_array_equal(ring[:, :c], ring[:, c:], err_msg=f"the two copies, session {i}")
-        np.testing.assert_array_equal(ring[:, t % c], swb.layer1_of(sets[s], qd[i][:, t]), err_msg=f"session {i}")
+        np.testing.assert_array_equal(ring[:, at], swb.layer1_of(sets[s], qd[i][:, t]), err_msg=f"session {i}")

@@ -43,15 +43,17 @@ def plan_each_raw(T, hop, cap, q, K, P, cnt, n_raw_max):
 
 class Walk:
     """The plan of every tick of a schedule: arrays [ticks][S] of the raw position before the tick, m,
-    off, slot0, k and W0, and fed [S], the raw totals."""
+    off, slot0, k, W0 and ok, and fed [S], the raw totals.  start: the sessions' raw positions before
+    the first tick (0)."""
 
-    def __init__(self, T, q, K, n_raw_max, counts, hop=HOP, max_push=MAX_PUSH):
+    def __init__(self, T, q, K, n_raw_max, counts, hop=HOP, max_push=MAX_PUSH, start=None):
         cap = ss.cap(T, max_push)
         counts = np.asarray(counts, np.int64)
         ticks, n_s = counts.shape
         self.cap, self.q, self.n_raw_max, self.counts = cap, q, tuple(int(v) for v in n_raw_max), counts
         self.P, self.m, self.off, self.slot0, self.k, self.W0, self.ok = (np.zeros((ticks, n_s), np.int64) for _ in range(7))
-        P = [0] * n_s
+        P = [0] * n_s if start is None else [int(p) for p in start]
+        first = list(P)
         for t in range(ticks):
             for s in range(n_s):
                 ok, m, n, off, slot0, _, _, _, k, _, W0 = plan_each_raw(T, hop, cap, q, K, P[s], int(counts[t, s]),
@@ -59,7 +61,7 @@ class Walk:
                 self.P[t, s], self.m[t, s], self.off[t, s], self.slot0[t, s] = P[s], m, off, slot0
                 self.k[t, s], self.W0[t, s], self.ok[t, s] = k, W0, ok
                 P[s] += n
-        self.fed = np.array(P, np.int64)
+        self.fed = np.array([p - a for p, a in zip(P, first)], np.int64)
 
 
 # ---- the schedule -----------------------------------------------------------------------------------
@@ -147,13 +149,14 @@ class RawDriver:
     its own cursor.  Each tick's slots [S][n_raw_max][C] are NaN beyond the session's count; y is
     prefilled with GUARD and every byte outside the completed rows held to it; cnt_out and win0 are
     held to the restatement of the plan, and positions() to D(raw_positions()).  A count outside
-    0 .. n_raw_max is passed on as it is and consumes nothing."""
+    0 .. n_raw_max is passed on as it is and consumes nothing.  start: the sessions' raw positions
+    before the first tick (0)."""
 
-    def __init__(self, torch, st, x, q, K, stream=None):
+    def __init__(self, torch, st, x, q, K, stream=None, start=None):
         self.torch, self.st, self.x, self.q, self.K, self.stream = torch, st, x, q, K, stream
         d = st.bank.dims
         self.S, self.C, self.T, self.N = st.S, int(x.shape[2]), d.T, d.N
-        self.cur, self.P = [0] * self.S, [0] * self.S
+        self.cur, self.P = [0] * self.S, [0] * self.S if start is None else [int(p) for p in start]
         self.rows = [[] for _ in range(self.S)]
         self.nb = torch.zeros((3,), dtype=torch.int32, device="cuda")
 

@@ -44,22 +44,28 @@ def plan_each(T, hop, cap, pos, cnt, n_max):
 
 class Walk:
     """The plan of every tick of a schedule: arrays [ticks][S] of the position before the tick, the
-    count, k, W0, p0 and at0, and fed [S], the totals."""
+    count, k, W0, p0, at0 and ok, and fed [S], the totals.  start: the sessions' positions before the
+    first tick (0); refusals: a refused count (one that would pass POS_LIMIT) is recorded in ok and
+    moves nothing, where otherwise it is an error of the schedule.  The plan itself is made in
+    Python's integers; every value stored fits an int64."""
 
-    def __init__(self, T, hop, max_push, n_max, counts):
+    def __init__(self, T, hop, max_push, n_max, counts, start=None, refusals=False):
         cap = ss.cap(T, max_push)
         counts = np.asarray(counts, np.int64)
         ticks = len(n_max)
         self.cap, self.n_max, self.counts = cap, tuple(int(v) for v in n_max), counts
         self.pos, self.k, self.W0, self.p0, self.at0 = (np.zeros((ticks, counts.shape[1]), np.int64) for _ in range(5))
-        pos = [0] * counts.shape[1]
+        self.ok = np.ones((ticks, counts.shape[1]), bool)
+        pos = [0] * counts.shape[1] if start is None else [int(p) for p in start]
+        first = list(pos)
         for t in range(ticks):
             for s in range(counts.shape[1]):
                 ok, n, p0, k, at0, W0 = plan_each(T, hop, cap, pos[s], int(counts[t, s]), self.n_max[t])
-                assert ok, (t, s)
+                assert ok or refusals, (t, s)
+                self.ok[t, s] = ok
                 self.pos[t, s], self.k[t, s], self.W0[t, s], self.p0[t, s], self.at0[t, s] = pos[s], k, W0, p0, at0
                 pos[s] += n
-        self.fed = np.array(pos, np.int64)
+        self.fed = np.array([p - a for p, a in zip(pos, first)], np.int64)
 
 
 # ---- the schedule -----------------------------------------------------------------------------------
